@@ -67,7 +67,13 @@ def parse():
     ap.add_argument("--points-per-block", type=int, default=0)
     ap.add_argument("--precision", default="fp64", choices=["fp64", "mixed", "fp32"],
                     help="fp64 = the reference's arithmetic (default, the only parity mode)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64): logl and "
+                         "flags per live point (N > 1: rank 0 writes the gathered logl of all ranks); at most 64 MB")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def algorithmic_bytes_per_launch(ndim, n_epochs, batch):
@@ -532,6 +538,26 @@ def run_extras(out, model, w, theta, B, with_cpu, device_index=0):
         guarded(name, fn)
 
 
+DUMP_LIMIT_BYTES = (64 << 20) - (64 << 10)      # 64 MB in all, .npy headers included
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: per-live-point arrays of one length, written as DIR/<name>.npy in float64.  Above the limit a fixed,
+    seeded sample of rows is written instead, with its row numbers as sample_index.npy.  Returns what the line records."""
+    out = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    n = len(next(iter(out.values())))
+    row_bytes = sum(a[:1].nbytes for a in out.values())
+    if n * row_bytes > DUMP_LIMIT_BYTES:
+        idx = np.sort(np.random.default_rng(20240229).choice(n, DUMP_LIMIT_BYTES // (row_bytes + 8), replace=False))
+        out = {k: a[idx] for k, a in out.items()}
+        out["sample_index"] = idx.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(dirname, f"{k}.npy"), a)
+    return {"dir": os.path.abspath(dirname), "files": sorted(f"{k}.npy" for k in out), "rows": len(out["logl"]),
+            "of_rows": n, "sampled": "sample_index" in out}
+
+
 def build_line(args, w, model, B, world, elapsed, gather, lanes, timed_region_kernel_ms):
     """The contract line (rank 0).  Returns (dict, gpu log-L of the resident batch, kernel seconds)."""
     value = world * B * args.steps / elapsed
@@ -743,8 +769,14 @@ def run_single(args, w, model, theta, B):
     model.dev_mark(1)
     model.dev_sync()
     elapsed = time.perf_counter() - t0
+    dumped = None
+    if args.dump_outputs:                        # what the last timed step left on the device, before anything else runs
+        _, logl, flags = model.dev_download(B, flags=True)
+        dumped = dump_outputs(args.dump_outputs, {"logl": logl, "flags": flags})
     out, gpu_logl, kern_s = build_line(args, w, model, B, 1, elapsed, "none", 1, model.dev_mark_elapsed_ms() / args.steps)
     out["config"]["prewarm"] = warm
+    if dumped:
+        out["dumped_outputs"] = dumped
     if not args.no_extras:
         run_extras(out, model, w, theta, B, not args.no_cpu, args.device_index)
         cls, _ = model_class()
@@ -936,6 +968,10 @@ def _run_multi_body(args, w, model, theta, B, rank, world, device_index, cls, st
         out = line(elapsed, lanes)
         if lanes > 1:
             out["single_lane_evals_per_s"] = single["value"]
+        if args.dump_outputs:                     # the gathered log-L of the last step (inputs are fixed: every step's)
+            model.dev_sync()
+            gathered = model.download_gathered(world * B) if state["gather"] == "rccl" else host_all[0]
+            out["dumped_outputs"] = dump_outputs(args.dump_outputs, {"logl": gathered})
         wd.fallback_line = out                        # from here on only extras can go wrong
     # 5. the two BASELINE configurations that name 8 GPUs, as sharded steps (extras of this line)
     if not args.no_extras:

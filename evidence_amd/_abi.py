@@ -193,14 +193,12 @@ def load():
             f"or `make -C evidence_amd/csrc`. evidence_amd has no CPU fallback.")
     # The HIP runtime maps a process's streams onto GPU_MAX_HW_QUEUES hardware queues (default 4) and reads the variable when it
     # starts.  A handle has seven streams; when a copy stream of the streamed host batches shares the kernels' queue, every
-    # chunk's kernels wait for a download (csrc/rvll_api.hip, stream_reserve: 3.3 against 2.0 ms at 262144 rows).  Ask for 8
-    # unless the user has chosen; results do not depend on it.
+    # chunk's kernels wait for a download (csrc/rvll_api.hip, stream_reserve: 3.3 against 2.0 ms at 262144 rows).  The count
+    # is the caller's choice: evidence_amd and librvll never set it, and results do not depend on it.
     global HW_QUEUES_NOTE
     hip_already = _hip_runtime_loaded()
     chosen = "GPU_MAX_HW_QUEUES" in os.environ
-    if not os.environ.get("RVLL_KEEP_HW_QUEUES"):            # (measurement switch: leave the variable alone, here and in librvll's constructor)
-        os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
-    HW_QUEUES_NOTE = {"GPU_MAX_HW_QUEUES": os.environ.get("GPU_MAX_HW_QUEUES", "unset"), "set_by": "the caller" if chosen else "evidence_amd (default 8)",
+    HW_QUEUES_NOTE = {"GPU_MAX_HW_QUEUES": os.environ.get("GPU_MAX_HW_QUEUES", "unset"), "set_by": "the caller" if chosen else "nobody",
                       "hip_runtime_loaded_before_librvll": hip_already,
                       "in_effect": "unknown: the HIP runtime was already up and reads the variable only when it starts" if hip_already and not chosen
                                    else os.environ.get("GPU_MAX_HW_QUEUES", "unset (runtime default: 4)")}

@@ -1147,9 +1147,8 @@ int stream_reserve(rvll_handle* h, long long rows)
         // lands on the kernels' queue, every chunk's kernels wait for the previous chunk's download: 3.3 against 2.0 ms at
         // 262144 rows — and which stream lands where depends on what the process has done before (inside bench.py streams made
         // here collided and the handle's spare lanes did not; in the standalone probe it was the other way round; stream
-        // priorities changed nothing).  The Python host therefore asks for 8 queues before the runtime starts
-        // (evidence_amd/_abi.py); a C caller sets GPU_MAX_HW_QUEUES=8 in its environment.  Results are the
-        // same either way.
+        // priorities changed nothing).  The queue count is the caller's choice (include/rvll.h, rvll_runtime_info); results
+        // are the same either way.
         HIP_TRY(hipStreamCreateWithFlags(&h->stream_up, hipStreamNonBlocking));
         HIP_TRY(hipStreamCreateWithFlags(&h->stream_down, hipStreamNonBlocking));
     }

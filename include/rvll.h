@@ -381,10 +381,9 @@ int rvll_allgather_host(rvll_handle* h, const double* mine, int64_t n_local, dou
  * ON THAT VARIABLE: the HIP runtime maps a process's streams onto that many hardware queues (default 4) and reads it once, when
  * it starts.  A handle has seven streams; with four queues a copy stream of the streamed host batches
  * (rvll_prior_loglike_batch from 24 MB of rows on) can share the kernels' queue, and a 262144-row call then takes 4.0 ms
- * instead of 2.85 ms (profiles/r04_hw_queues.txt).  Nothing else depends on it (results never do).  librvll therefore asks
- * for 8 ITSELF when it is loaded, unless the variable is set already (or RVLL_KEEP_HW_QUEUES is): that is in time whenever
- * librvll is what brings the HIP runtime into the process; a caller that has made HIP calls before loading librvll exports
- * GPU_MAX_HW_QUEUES=8 itself.  "gpu_max_hw_queues_set_by" in the JSON says which of the two happened.                   */
+ * instead of 2.85 ms with eight (profiles/r04_hw_queues.txt).  Nothing else depends on it (results never do).  librvll
+ * never sets the variable: the count is the caller's choice, and "gpu_max_hw_queues_set_by" in the JSON says whether the
+ * caller's environment has it.                                                                                         */
 int rvll_runtime_info(char* buf, int32_t buflen);
 /* One multi-GPU step is rvll_dev_loglike(B_local) followed by rvll_allgather_logl(B_local): every rank's
  * per-shard log-L (the buffer the kernel just wrote) is all-gathered on the device, rank-major, so that every

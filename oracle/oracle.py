@@ -5,6 +5,7 @@ Kepler solver compiled from /root/reference by `make -C oracle ref`).
 TEST INFRASTRUCTURE ONLY — never imported by evidence_amd/.
 """
 import ctypes as C
+import os
 import subprocess
 from pathlib import Path
 
@@ -25,7 +26,7 @@ _ref = None
 def build(ref=True):
     """Compile the oracle (and, when /root/reference exists, the reference solver)."""
     subprocess.run(["make", "-s", "-C", str(HERE)], check=True)
-    if ref and Path("/root/reference/evidence/rvmodel/trueanomaly.c").exists():
+    if ref and os.path.isfile("/root/reference/evidence/rvmodel/trueanomaly.c"):     # False, not PermissionError, where unreadable
         subprocess.run(["make", "-s", "-C", str(HERE), "ref"], check=True)
 
 

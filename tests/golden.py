@@ -1,5 +1,6 @@
 """Loaders for the committed golden fixtures (tests/golden/*.npz, made by gen_golden.py
 from the reference itself)."""
+import hashlib
 import json
 from pathlib import Path
 
@@ -88,6 +89,32 @@ def prior_sets():
     meta = json.loads((GOLDEN / "priors.json").read_text())
     q = z["q"]
     return q, [(m["name"], m["args"], z[f"p{i}_ppf"], z[f"p{i}_raised"]) for i, m in enumerate(meta["sets"])]
+
+
+# Kepler-solver cases: eccentricities, their mean anomalies and the itmax-abort case (gen_kepler_golden.py stores what the
+# reference's own compiled trueanomaly() returns on exactly these inputs)
+KEPLER_ECCS = (0.0, 0.05, 0.3, 0.6, 0.9, 0.95, 0.98, 0.99, 0.995, 1.3, -0.2)
+
+
+def kepler_mean_anomalies(ecc):
+    return np.random.default_rng(int(abs(ecc) * 1000)).uniform(-7.0e3, 7.0e3, 20000)
+
+
+def kepler_itmax_mean_anomalies():
+    return np.linspace(0.1, 3.0, 50)
+
+
+def sha256(a):
+    """Digest of an array's bytes: equal digests <=> bit-identical arrays (NaN payloads and signed zeros included)."""
+    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+
+def kepler_reference():
+    """{ecc: dict(rc, m_sha256, nu_sha256, nu_sample)}, the sample index and the itmax case (nu, rc) of kepler_ref.npz."""
+    z = np.load(GOLDEN / "kepler_ref.npz")
+    cases = {float(e): dict(rc=int(z["rc"][i]), m_sha256=str(z["m_sha256"][i]), nu_sha256=str(z["nu_sha256"][i]),
+                            nu_sample=z["nu_sample"][i]) for i, e in enumerate(z["ecc"])}
+    return cases, z["sample_index"], (z["itmax_nu"], int(z["itmax_rc"]))
 
 
 def rel_err(a, b):

@@ -10,6 +10,10 @@ import subprocess
 import sys
 from pathlib import Path
 
+import numpy as np
+
+from evidence_amd.synthetic import make_workload
+
 REPO = Path(__file__).resolve().parents[1]
 STUB = "tests.bench_stub:StubModel"
 
@@ -119,3 +123,22 @@ def test_a_rank_of_eight_that_dies_mid_phase_does_not_take_the_line_with_it():
         assert "last completed measurement" in lines[0]["config"]["note"]
     else:
         assert lines[0]["config"]["allgather"] == "rccl-hung"
+
+
+def test_bench_dump_outputs_writes_the_last_steps_log_l_the_same_from_run_to_run(tmp_path):
+    """--dump-outputs DIR (N = 1): after the timed steps, logl.npy / flags.npy in float64 hold what the last step computed over
+    the fixed, seeded live points; two runs with the same arguments write the same arrays."""
+    dumps = []
+    for run in ("a", "b"):
+        r, lines = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--no-cpu", "--no-extras",
+                         "--dump-outputs", str(tmp_path / run)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert len(lines) == 1
+        d = lines[0]
+        assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["config"]["stub_model"] == STUB
+        assert d["dumped_outputs"]["files"] == ["flags.npy", "logl.npy"] and d["dumped_outputs"]["sampled"] is False
+        dumps.append({n: np.load(tmp_path / run / f"{n}.npy") for n in ("logl", "flags")})
+    theta = make_workload(3).sample_theta(16384, seed=1234)
+    assert np.array_equal(dumps[0]["logl"], -(theta * theta).sum(axis=1) - 1.0)        # the stub's stand-in for log-L
+    for n, a in dumps[0].items():
+        assert a.dtype == np.float64 and a.shape == (16384,) and np.array_equal(a, dumps[1][n])

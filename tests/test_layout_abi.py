@@ -118,20 +118,23 @@ def test_oracle_is_not_imported_by_the_product():
             assert "oracle" not in path.read_text().lower(), path
 
 
-def test_the_library_asks_for_its_hardware_queues_itself_unless_the_caller_has_chosen():
-    """the streamed host batches' fast path must not hang on an environment variable the caller has to know
-    about.  librvll's load-time constructor (csrc/rvll_comm.hip) sets GPU_MAX_HW_QUEUES=8 in the process's C environment when
-    it is unset, and leaves a caller's choice alone.  (Fresh processes: the variable is read by the HIP runtime when it starts.)"""
+def test_the_library_leaves_the_hardware_queue_count_to_the_caller():
+    """GPU_MAX_HW_QUEUES is the caller's choice: neither librvll when it is loaded nor evidence_amd's binding sets it, and a
+    caller's value is left as it is (fresh processes: the variable is read by the HIP runtime when it starts)."""
     import subprocess
     import sys
     from evidence_amd import _abi
     code = ("import ctypes, os, sys\n"
             "os.environ.pop('GPU_MAX_HW_QUEUES', None)\n"
             "if sys.argv[2] != '-': os.environ['GPU_MAX_HW_QUEUES'] = sys.argv[2]\n"
-            "ctypes.CDLL(sys.argv[1])\n"
+            "sys.path.insert(0, sys.argv[3])\n"
+            "from evidence_amd import _abi\n"
+            "ctypes.CDLL(sys.argv[1]); _abi.load()\n"
             "libc = ctypes.CDLL(None); libc.getenv.restype = ctypes.c_char_p\n"
-            "print((libc.getenv(b'GPU_MAX_HW_QUEUES') or b'unset').decode())\n")
-    for chosen, want in (("-", "8"), ("2", "2")):
-        out = subprocess.run([sys.executable, "-c", code, str(_abi.LIB_PATH), chosen], capture_output=True, text=True, timeout=120)
+            "print((libc.getenv(b'GPU_MAX_HW_QUEUES') or b'unset').decode(), os.environ.get('GPU_MAX_HW_QUEUES', 'unset'),\n"
+            "      _abi.HW_QUEUES_NOTE['set_by'].replace(' ', '_'))\n")
+    for chosen, want in (("-", "unset unset nobody"), ("2", "2 2 the_caller"), ("1", "1 1 the_caller")):
+        out = subprocess.run([sys.executable, "-c", code, str(_abi.LIB_PATH), chosen, str(REPO)], capture_output=True, text=True,
+                             timeout=120)
         assert out.returncode == 0, out.stderr
         assert out.stdout.strip() == want, (chosen, out.stdout, out.stderr)

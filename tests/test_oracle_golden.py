@@ -1,6 +1,7 @@
 """CPU: the oracle (oracle/rvll_oracle.c) against the golden vectors produced by the
-reference itself, and against the reference's own compiled Kepler solver when
-oracle/_ref is present.  This is what pins the oracle."""
+reference itself, its Kepler solver against the stored output of the reference's own
+compiled solver (and against that build itself when oracle/_ref is present).  This is
+what pins the oracle."""
 import numpy as np
 import pytest
 
@@ -39,27 +40,37 @@ def test_invalid_orbit_sentinel_and_flag():
             assert np.all(got == -1e30) and np.all(flags & 1)
 
 
-@pytest.mark.skipif(orc.load_ref() is None, reason="oracle/_ref not built (needs /root/reference)")
-@pytest.mark.parametrize("ecc", [0.0, 0.05, 0.3, 0.6, 0.9, 0.95, 0.98, 0.99, 0.995, 1.3, -0.2])
+KEPLER_REF, KEPLER_SAMPLE, KEPLER_ITMAX = golden.kepler_reference()
+
+
+@pytest.mark.parametrize("ecc", golden.KEPLER_ECCS)
 def test_kepler_solver_bit_identical_to_reference_build(ecc):
-    M = np.random.default_rng(int(abs(ecc) * 1000)).uniform(-7.0e3, 7.0e3, 20000)
+    M = golden.kepler_mean_anomalies(ecc)
+    ref = KEPLER_REF[ecc]                     # the reference's compiled solver on these very M (gen_kepler_golden.py)
+    assert golden.sha256(M) == ref["m_sha256"]
     mine, rc1 = orc.trueanomaly(M, ecc)
-    ref, rc2 = orc.ref_trueanomaly(M, ecc)
-    assert rc1 == rc2
-    assert np.array_equal(mine, ref)
+    assert rc1 == ref["rc"]
+    assert np.array_equal(mine[KEPLER_SAMPLE].view(np.uint64), ref["nu_sample"].view(np.uint64))
+    assert golden.sha256(mine) == ref["nu_sha256"]
+    if orc.load_ref() is not None:            # and against a local build of the reference's solver, when there is one
+        live, rc2 = orc.ref_trueanomaly(M, ecc)
+        assert rc1 == rc2
+        assert np.array_equal(mine, live)
 
 
-@pytest.mark.skipif(orc.load_ref() is None, reason="oracle/_ref not built (needs /root/reference)")
 def test_itmax_abort_leaves_tail_untouched_like_reference():
     # an unreachable tolerance forces the niteration >= itmax return (trueanomaly.c:32-33)
-    M = np.linspace(0.1, 3.0, 50)
+    M = golden.kepler_itmax_mean_anomalies()
     mine, rc1 = orc.trueanomaly(M, 0.5, itmax=7, tol=0.0)
-    ref, rc2 = orc.ref_trueanomaly(M, 0.5, itmax=7, tol=0.0)
+    ref, rc2 = KEPLER_ITMAX
     assert rc1 == rc2 == -1
     # elements before the first non-converging one are solved, everything after stays 0 (pre-zeroed nu)
     assert np.array_equal(mine, ref)
     first_zero = int(np.argmax(mine == 0.0))
     assert 0 < first_zero < len(M) and np.all(mine[first_zero:] == 0.0) and np.all(mine[:first_zero] != 0.0)
+    if orc.load_ref() is not None:
+        live, rc3 = orc.ref_trueanomaly(M, 0.5, itmax=7, tol=0.0)
+        assert rc3 == -1 and np.array_equal(mine, live)
 
 
 def test_iteration_counts_match_survey():
