@@ -12,8 +12,9 @@ from .data import EpochTable
 from .layout import ModelLayout, compile_layout
 from .priors import PriorError, PriorSpec, prior_constructor
 from .engine import GpuRVModel
+from .nested import run_nested_ensemble
 
 __all__ = ["GpuRVModel", "EpochTable", "ModelLayout", "compile_layout", "PriorSpec", "PriorError",
            "prior_constructor", "RvllError", "RvllLibraryError", "FLAG_INVALID_ORBIT", "FLAG_NONCONVERGED",
-           "FLAG_WANDERED"]
+           "FLAG_WANDERED", "run_nested_ensemble"]
 __version__ = "0.1.0"

@@ -528,6 +528,7 @@ int rvll_destroy(rvll_handle* h)
     stream_free(h);
     dev_free(h->d_walk_steps); dev_free(h->d_walk_wid); dev_free(h->d_walk_start); dev_free(h->d_walk_cost); dev_free(h->d_walk_order); dev_free(h->d_walk_wflag);
     dev_free(h->d_rounds); dev_free(h->d_walk_dirs);
+    dev_free(h->d_walk_run); dev_free(h->d_run_lstar); dev_free(h->d_run_seed); dev_free(h->d_run_chol);
     if (h->pin_rounds) (void)hipHostFree(h->pin_rounds);
     if (h->ev_rounds) (void)hipEventDestroy(h->ev_rounds);
     for (auto& s : h->rounds_streams) if (s) (void)hipStreamDestroy(s);

@@ -141,6 +141,13 @@ struct rvll_handle {
     int32_t *d_walk_steps = nullptr, *d_walk_wid = nullptr, *d_walk_start = nullptr;   // [walk_cap] each
     int32_t *d_walk_cost = nullptr, *d_walk_order = nullptr;                            // [walk_cap] each (two-part walks)
     int32_t* d_walk_wflag = nullptr;            // [walk_cap] 1: the walker's last accepted candidate had a wandering solve (walk_core puts its log-L right)
+    // run mode of the walk (rvll_slice_walk_runs): per row its run (its index inside the run goes in d_walk_wid), per run
+    // lstar, seed and whitening factor
+    long long runs_rows_cap = 0, runs_cap = 0;
+    int32_t* d_walk_run = nullptr;              // [runs_rows_cap]
+    double* d_run_lstar = nullptr;              // [runs_cap]
+    unsigned long long* d_run_seed = nullptr;   // [runs_cap]
+    double* d_run_chol = nullptr;               // [runs_cap, ndim, ndim]
     int wander_exact = 1;                       // wandering solves are redone with correctly rounded sin / cos (rvll_set_wander_exact; RVLL_WANDER_EXACT)
     int walk_spec = 4;                          // candidates a walker may evaluate ahead per iteration (rvll_set_walk_speculation)
     // the walk as rounds of launches (rvll_rounds.hip; walk_rounds in rvll_walk_host.hip): one arena with every group's walker

@@ -110,6 +110,15 @@ struct WalkArgs {
     int rows_per_wg;              // the "rows" form (launch_slice_walk_rows): rows every workgroup owns for the whole launch
     int32_t* wflag;               // [K] or null, out: 1 where the walker's LAST accepted candidate carried RVLL_FLAG_WANDERED (its log-L is
                                   // then put right by the host with the exact redo, which the walk's tiles leave out: walk_core)
+    // RUN MODE (rvll_slice_walk_runs): the walkers of several independent runs in one launch.  run = null: one run, the
+    // scalars seed / lstar and chol above (the kernels' instantiation without run mode: nothing below is read).  Otherwise
+    // row g belongs to run run[g], accepts against run_lstar[run[g]], draws with run_seed[run[g]] and whitens with
+    // run_chol[run[g]] (read from global memory: the walkers of one workgroup may belong to different runs); walker_id
+    // holds the row's index inside its run and walker_base is 0, and cost counts every row's calls (summed by run on the host)
+    const int32_t* run;                  // [K] or null
+    const double* run_lstar;             // [R]
+    const unsigned long long* run_seed;  // [R]
+    const double* run_chol;              // [R, D, D] row-major lower-triangular factors
 };
 constexpr int kWalkCholLds = 48;   // the walk stages a whitening factor of up to 48 x 48 (18 KB) in LDS
 size_t walk_lds_bytes(const LoglikeArgs& a);
@@ -182,6 +191,12 @@ struct RoundsArgs {
     unsigned long long* slots_part;   // [workgroups] slots evaluated (>= calls: candidates ahead that went unused)
     unsigned long long* stamps;       // diagnostic (RVLL_ROUNDS_STAMPS) or null: per round and workgroup 4 x s_memrealtime (100 MHz)
     int stamp_rounds;
+    // run mode (as WalkArgs; null: one run, the scalars seed / lstar and wid0 + walker): per walker of the group
+    const int32_t* run;                  // [K] or null: its run
+    const int32_t* rid;                  // [K] its random-number counter index (its index inside the run)
+    const double* run_lstar;             // [R]
+    const unsigned long long* run_seed;  // [R]
+    int32_t* wcost;                      // [K] += likelihood calls the walker consumed (zeroed by the host before the walk)
 };
 // the directions of every move of every walker, in front of the rounds
 struct RoundsDirs {
@@ -191,6 +206,11 @@ struct RoundsDirs {
     unsigned long long wid0;   // random-number counter index of the first walker
     unsigned long long seed;
     int D, nsteps;
+    // run mode (as WalkArgs; null: one run, seed / chol / wid0 above): per walker its run, its counter index, per run seed and factor
+    const int32_t* run;                  // [K] or null
+    const int32_t* rid;                  // [K]
+    const unsigned long long* run_seed;  // [R]
+    const double* run_chol;              // [R, D, D]
 };
 hipError_t launch_rounds_dirs(const RoundsDirs& g, int max_blocks, hipStream_t stream);
 // what the tiles of a round need beside their LoglikeArgs (a.theta = the group's theta_c)
@@ -206,6 +226,9 @@ size_t rounds_step_lds_bytes(int W, int D, int spec_max);
 int rounds_blocks_per_cu(size_t lds_bytes);
 // a group's round: two launches on the group's stream
 hipError_t launch_rounds_step(const RoundsArgs& g, int round, hipStream_t stream);
+// run mode (g.run != null; rvll_rounds_runs.hip): the directions and the step with every walker's run indirection
+hipError_t launch_rounds_dirs_runs(const RoundsDirs& g, int max_blocks, hipStream_t stream);
+hipError_t launch_rounds_step_runs(const RoundsArgs& g, int round, hipStream_t stream);
 hipError_t launch_rounds_tiles(const LoglikeArgs& a, const RoundsTiles& out, int tiles, int round, hipStream_t stream);
 // the tiles of a round alone, in the CU-wide form: `tiles` 1024-thread workgroups of at most a.PB points (a.CH >= a.PB * a.Ne)
 hipError_t launch_rounds_cu(const LoglikeArgs& a, const RoundsTiles& out, int tiles, int round, hipStream_t stream);

@@ -20,15 +20,18 @@ namespace {
 // Box-Muller normals, the triangular product and the norm of the walkers that start a move were half of a step's 35 us
 // (profiles/r04_rounds_step_stamps.txt).  Same routines, same order of operations as slice_walk_kernel: same bits.
 // One workgroup walks (walker, move) pairs, kDirPairs at a time: a lane per (pair, coordinate).
+// RUNS (run mode, g.run != null): every walker draws with its run's seed and whitens with its run's factor, read from global
+// memory (the pairs of one workgroup may belong to different runs), and its counter index is g.rid[walker].
 constexpr int kDirPairs = 12;
 __host__ __device__ inline size_t dirs_lds_doubles(int D) { return (size_t)2 * kDirPairs * D + (D <= kWalkCholLds ? D * D : 0) + kDirPairs; }
-__device__ __forceinline__ void rounds_dirs(const RoundsDirs& g, double* sm)
+template <bool RUNS>
+__device__ __forceinline__ void rounds_dirs_impl(const RoundsDirs& g, double* sm)
 {
     const int D = g.D, tid = threadIdx.x;
     double* z = sm;                         // [kDirPairs][D] normals
     double* cv = z + kDirPairs * D;         // [kDirPairs][D] chol z
     double* chol_s = cv + kDirPairs * D;
-    const bool chol_in_lds = D <= kWalkCholLds;
+    const bool chol_in_lds = !RUNS && D <= kWalkCholLds;
     double* rn = chol_s + (chol_in_lds ? D * D : 0);     // [kDirPairs] 1 / |chol z|
     if (chol_in_lds) for (int k = tid; k < D * D; k += kThreads) chol_s[k] = g.chol[k];
     const double* chol = chol_in_lds ? chol_s : g.chol;
@@ -38,14 +41,14 @@ __device__ __forceinline__ void rounds_dirs(const RoundsDirs& g, double* sm)
         for (int idx = tid; idx < np * D; idx += kThreads) {
             const int q = idx / D, k = idx - q * D;
             const long long pr = p0 + q, w = pr / g.nsteps, m = pr - w * g.nsteps;
-            const unsigned long long wid = g.wid0 + (unsigned long long)w;
+            const unsigned long long wid = RUNS ? (unsigned long long)g.rid[w] : g.wid0 + (unsigned long long)w;
             const unsigned long long ctr = (wid << 32) | ((unsigned long long)m << 14) | (unsigned)(2 * k);
-            z[idx] = walk_normal(g.seed, ctr);
+            z[idx] = walk_normal(RUNS ? g.run_seed[g.run[w]] : g.seed, ctr);
         }
         __syncthreads();                    // (the first time round: chol_s as well)
         for (int idx = tid; idx < np * D; idx += kThreads) {
             const int q = idx / D, k = idx - q * D;
-            const double* cr = chol + k * D;
+            const double* cr = (RUNS ? g.run_chol + (long long)g.run[(p0 + q) / g.nsteps] * D * D : chol) + k * D;
             const double* zq = z + q * D;
             double a = 0.;
             int j = 0;
@@ -69,6 +72,7 @@ __device__ __forceinline__ void rounds_dirs(const RoundsDirs& g, double* sm)
         __syncthreads();
     }
 }
+__device__ __forceinline__ void rounds_dirs(const RoundsDirs& g, double* sm) { rounds_dirs_impl<false>(g, sm); }
 
 // ---- the step ---------------------------------------------------------------------------------------------------------------
 // LDS of a step workgroup: W walkers' positions, directions (of the move in progress / of the move after it) and a chunk of
@@ -98,7 +102,10 @@ __device__ __forceinline__ StepLds step_views(double* sm, int W, int D, int SM)
 // single wave per SIMD): everything it needs is fetched in ONE round trip at the top — the walkers' words, brackets,
 // positions, the direction of the move in progress and of the one after it, the result records (indexed by walker: the tiles
 // put them there) — then one atomic for the slots.
-__device__ __forceinline__ void rounds_step(const RoundsArgs& g, const int r, const int block, double* sm)
+// RUNS (run mode, g.run != null): a walker accepts against its run's lstar, draws with its run's seed under its counter index
+// g.rid, and adds the calls it consumes to its own g.wcost (the host sums them by run).
+template <bool RUNS>
+__device__ __forceinline__ void rounds_step_impl(const RoundsArgs& g, const int r, const int block, double* sm)
 {
     const int D = g.D, W = g.W, SM = g.spec_max, tid = threadIdx.x, lane = tid & (kWave - 1);
     const long long i0 = (long long)block * W;
@@ -147,6 +154,7 @@ __device__ __forceinline__ void rounds_step(const RoundsArgs& g, const int r, co
         int acc = -1, accw = 0;
         long long used = 0;
         double newl = 0., tacc = 0.;
+        const double lstar_r = RUNS && valid ? g.run_lstar[g.run[i0 + lane]] : 0.;      // (run mode: the walker's run's)
         if (r > 0 && state == 1) {
             const int round0 = round;
             for (int j = 0; j < nsp; ++j) {
@@ -160,7 +168,7 @@ __device__ __forceinline__ void rounds_step(const RoundsArgs& g, const int r, co
                     used = -(long long)round0;
                     break;
                 }
-                if (cl > g.lstar) { state = 0; stp += 1; acc = j; newl = cl; tacc = t; accw = (s.rec_f[lane * SM + j] & RVLL_FLAG_WANDERED) ? 1 : 0; break; }
+                if (cl > (RUNS ? lstar_r : g.lstar)) { state = 0; stp += 1; acc = j; newl = cl; tacc = t; accw = (s.rec_f[lane * SM + j] & RVLL_FLAG_WANDERED) ? 1 : 0; break; }
                 if (t < 0.) tmn = t; else tmx = t;
                 if (++round >= g.max_rounds) { state = 0; stp += 1; break; }     // give the move up, stay put
             }
@@ -199,6 +207,7 @@ __device__ __forceinline__ void rounds_step(const RoundsArgs& g, const int r, co
             g.step[i0 + lane] = stp;
             if (acc >= 0) { g.logl[i0 + lane] = newl; g.wflag[i0 + lane] = accw; }
             if (listed && state == 1) { g.tmin[i0 + lane] = tmn; g.tmax[i0 + lane] = tmx; }
+            if (RUNS && used) g.wcost[i0 + lane] += (int32_t)used;
         }
         if (lane < W) {
             s.st[lane] = listed ? state : 4;  s.lf[lane] = excl;  s.nsp[lane] = S;  s.acc[lane] = valid ? acc : -1;
@@ -284,11 +293,12 @@ __device__ __forceinline__ void rounds_step(const RoundsArgs& g, const int r, co
     if (tid < nw && s.st[tid] <= 1) {
         const int wl = tid;
         double lo = s.tmn[wl], hi = s.tmx[wl];
-        const unsigned long long wid = g.wid0 + (unsigned long long)(i0 + wl);
+        const unsigned long long wid = RUNS ? (unsigned long long)g.rid[i0 + wl] : g.wid0 + (unsigned long long)(i0 + wl);
         const unsigned long long ctr = (wid << 32) | ((unsigned long long)s.stp[wl] << 14) | (unsigned)(8192 + s.rnd[wl]);
         const int f = s.lf[wl], S = s.nsp[wl];
+        const unsigned long long seed = RUNS ? g.run_seed[g.run[i0 + wl]] : g.seed;
         for (int j = 0; j < S; ++j) {
-            const double t = lo + (hi - lo) * uniform01(g.seed, ctr + (unsigned)j);
+            const double t = lo + (hi - lo) * uniform01(seed, ctr + (unsigned)j);
             slot_t[f + j] = t; slot_w[f + j] = wl; slot_def[f + j] = 0;
             g.wt[(i0 + wl) * SM + j] = t;
             g.owner[base + f + j] = (int)((i0 + wl) * SM + j);
@@ -338,6 +348,11 @@ __device__ __forceinline__ void rounds_step(const RoundsArgs& g, const int r, co
         g.wdef[(i0 + wl) * SM + (ls - s.lf[wl])] = slot_def[ls];
     }
     if (stamp) stamp[7] = __builtin_amdgcn_s_memrealtime();
+}
+
+__device__ __forceinline__ void rounds_step(const RoundsArgs& g, const int r, const int block, double* sm)
+{
+    rounds_step_impl<false>(g, r, block, sm);
 }
 
 inline size_t step_lds_bytes(int W, int D, int SM)

@@ -49,7 +49,10 @@ namespace {
 // number of completed moves in steps_done; the host finishes those walkers with the FAT instantiation (full solvers
 // inline, 2 waves per SIMD), whose counter-based random numbers make it retrace the interrupted move exactly — so
 // the pair returns what a FAT-only walk would.
-template <int PREC, bool FAT, int NP = 0>           // NP: the planet count at compile time (rvll_tile.h, eval_item), 0 = a.Np
+// RUNS (run mode, rvll_slice_walk_runs; w.run != null): the rows belong to independent runs, each with its own lstar, seed
+// and whitening factor (WalkArgs).  The factor is read from global memory, per walker that starts a move (the walkers of a
+// workgroup may belong to different runs); the instantiation without it is the one-run walk, instruction for instruction.
+template <int PREC, bool FAT, int NP = 0, bool RUNS = false>   // NP: the planet count at compile time (rvll_tile.h, eval_item), 0 = a.Np
 __global__ __launch_bounds__(kThreads, FAT ? 2 : RVLL_WALK_WAVES) __attribute__((flatten))
 void slice_walk_kernel(const LoglikeArgs a, const WalkArgs w)
 {
@@ -74,7 +77,7 @@ void slice_walk_kernel(const LoglikeArgs a, const WalkArgs w)
     double* cand = smem + cv.contrib;
     double* lo_s = cand + PB * D;
     double* hi_s = lo_s + PB * D;
-    const bool chol_in_lds = D <= kWalkCholLds;
+    const bool chol_in_lds = !RUNS && D <= kWalkCholLds;
     double* chol_s = wl + PB;                              // [D][D] the whitening factor, when it is small enough to stage
     int* act     = reinterpret_cast<int*>(chol_s + (chol_in_lds ? D * D : 0));   // [2][PB] walkers with moves left (local index),
                                                             // compacted; the list of the next iteration is written while this one's is read
@@ -228,14 +231,15 @@ void slice_walk_kernel(const LoglikeArgs a, const WalkArgs w)
             const int pl = starts[i / D], k = i % D;
             const unsigned long long wid = (unsigned long long)(w.walker_base + (w.walker_id ? (long long)w.walker_id[gid[pl]] : (long long)gid[pl]));
             const unsigned long long ctr = (wid << 32) | ((unsigned long long)step_of[pl] << 14) | (unsigned)(2 * k);
-            lo_s[pl * D + k] = walk_normal(w.seed, ctr);
+            lo_s[pl * D + k] = walk_normal(RUNS ? w.run_seed[w.run[gid[pl]]] : w.seed, ctr);
         }
         __syncthreads();
         // ... direction = chol * z (lower triangular), parked in the candidate rows, which are free until the tile ...
         for (int i = tid; i < nstart * D; i += kThreads) {
             const int pl = starts[i / D], k = i % D;
+            const double* cf = RUNS ? w.run_chol + (long long)w.run[gid[pl]] * D * D : chol;
             double acc = 0.;
-            for (int j = 0; j <= k; ++j) acc += chol[k * D + j] * lo_s[pl * D + j];
+            for (int j = 0; j <= k; ++j) acc += cf[k * D + j] * lo_s[pl * D + j];
             cand[pl * D + k] = acc;
         }
         __syncthreads();
@@ -276,8 +280,9 @@ void slice_walk_kernel(const LoglikeArgs a, const WalkArgs w)
             const unsigned long long ctr = (wid << 32) | ((unsigned long long)step_of[pl] << 14) | (unsigned)(8192 + round_of[pl]);
             double lo = tmin[pl], hi = tmax[pl];
             const int first = first_of[pl], S = nsp_of[pl];
+            const unsigned long long seed = RUNS ? w.run_seed[w.run[gid[pl]]] : w.seed;
             for (int j = 0; j < S; ++j) {
-                const double t = lo + (hi - lo) * uniform01(w.seed, ctr + (unsigned)j);
+                const double t = lo + (hi - lo) * uniform01(seed, ctr + (unsigned)j);
                 slot_t[first + j] = t; slot_pl[first + j] = pl;
                 if (t < 0.) lo = t; else hi = t;
             }
@@ -307,6 +312,7 @@ void slice_walk_kernel(const LoglikeArgs a, const WalkArgs w)
         for (int ai = tid; ai < nact; ai += kThreads) {
             const int pl = act[ai];
             const int first = first_of[pl], S = nsp_of[pl];
+            const double lstar = RUNS ? w.run_lstar[w.run[gid[pl]]] : w.lstar;
             int used = 0;
             acc_slot[pl] = -1;
             for (int j = 0; j < S; ++j) {                               // in the order the walker would have met them
@@ -321,7 +327,7 @@ void slice_walk_kernel(const LoglikeArgs a, const WalkArgs w)
                     used = -(round_of[pl] - j);
                     break;
                 }
-                if (cl > w.lstar) {
+                if (cl > lstar) {
                     state[pl] = 2; wl[pl] = cl; acc_slot[pl] = first + j; acc_g[pl] = gid[pl];
                     if (w.wflag) w.wflag[gid[pl]] = (fl & RVLL_FLAG_WANDERED) ? 1 : 0;
                     break;
@@ -791,14 +797,24 @@ hipError_t launch_slice_walk(const LoglikeArgs& a, const WalkArgs& w, bool fat, 
         hipLaunchKernelGGL(KERNEL, dim3((unsigned)nblocks), block, lds, stream, a, w);                               \
     } while (0)
 #define RVLL_WALK(PREC)                                                                                              \
-    if (fat) RVLL_WALK_ONE((slice_walk_kernel<PREC, true>));                                                        \
+    if (runs) {                                                                                                      \
+        if (fat) RVLL_WALK_ONE((slice_walk_kernel<PREC, true, 0, true>));                                           \
+        else     RVLL_WALK_ONE((slice_walk_kernel<PREC, false, 0, true>));                                          \
+    } else if (fat) RVLL_WALK_ONE((slice_walk_kernel<PREC, true>));                                                 \
     else     RVLL_WALK_ONE((slice_walk_kernel<PREC, false>))
+    // run mode: per-run tables and every row's index inside its run, no walker_base
+    const bool runs = w.run != nullptr;
+    if (runs && (!w.run_lstar || !w.run_seed || !w.run_chol || !w.walker_id || w.walker_base != 0)) return hipErrorInvalidValue;
     switch (a.precision) {
     case RVLL_PREC_MIXED: RVLL_WALK(RVLL_PREC_MIXED); break;
     case RVLL_PREC_FP32:  RVLL_WALK(RVLL_PREC_FP32); break;
     default:
 #ifndef RVLL_AB_NO_NP                  // (measurement builds only: without the three-planet instantiation)
-        if (!fat && a.Np == 3) { RVLL_WALK_ONE((slice_walk_kernel<RVLL_PREC_FP64, false, 3>)); break; }
+        if (!fat && a.Np == 3) {
+            if (runs) RVLL_WALK_ONE((slice_walk_kernel<RVLL_PREC_FP64, false, 3, true>));
+            else      RVLL_WALK_ONE((slice_walk_kernel<RVLL_PREC_FP64, false, 3>));
+            break;
+        }
 #endif
         RVLL_WALK(RVLL_PREC_FP64);
         break;
@@ -810,6 +826,7 @@ hipError_t launch_slice_walk(const LoglikeArgs& a, const WalkArgs& w, bool fat, 
 
 hipError_t launch_slice_walk_rows(const LoglikeArgs& a, const WalkArgs& w, bool fat, int nblocks, int nt, hipStream_t stream)
 {
+    if (w.run) return hipErrorInvalidValue;               // (no run mode: rvll_slice_walk_runs refuses the rows forms)
     if (w.K <= 0 || w.nsteps <= 0) return hipSuccess;
     const bool wide = nt != kThreads;
     if ((nt != kThreads && nt != 512 && nt != kCuThreads) || (wide && fat) ||

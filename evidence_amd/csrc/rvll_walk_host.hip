@@ -44,6 +44,27 @@ int walk_reserve(rvll_handle* h, int64_t K)
     return RVLL_OK;
 }
 
+// Run mode of a walk (rvll_slice_walk_runs): the walkers of several independent runs in one walk.  Every row's run is in
+// d_walk_run and its index inside the run in d_walk_wid (the random-number counter index the one-run walk of that run gives
+// it); per run lstar, seed and whitening factor are in d_run_lstar / d_run_seed / d_run_chol.  Every launch of the walk counts
+// the calls of each row in d_walk_cost (the single-kernel forms' per-row cost, the rounds step's per-walker count), and the
+// host adds them up per row: the calls of a run are then those its own walk would report, whichever forms the rows took.
+struct RunWalk {
+    const int32_t* run;                // [K] host copy of d_walk_run
+    const int32_t* rid;                // [K] host copy of d_walk_wid
+    std::vector<long long> row_calls;  // [K] out: likelihood calls every row consumed
+};
+
+// run mode: d_walk_cost [n] down and added to rw->row_calls (at rows[j], or at j when rows is null); synchronises the stream
+int run_calls_add(rvll_handle* h, RunWalk* rw, int64_t n, const int32_t* rows)
+{
+    std::vector<int32_t> c((size_t)n);
+    HIP_TRY(hipMemcpyAsync(c.data(), h->d_walk_cost, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, h->compute));
+    HIP_TRY(hipStreamSynchronize(h->compute));
+    for (int64_t j = 0; j < n; ++j) rw->row_calls[(size_t)(rows ? rows[j] : j)] += c[(size_t)j];
+    return RVLL_OK;
+}
+
 // ---- the walk as rounds of launches (rvll_rounds.h, rvll_kernels.hip) ----------------------------------------------------
 // Which walks take it: RVLL_WALK_ROUNDS = 0 never / 1 whenever the slim prior stage applies.  By default the walks it was
 // measured to win (profiles/r04_rounds_sizes.txt, cfg3, nested sampling end to end, calls/s inside the walk against the
@@ -66,8 +87,10 @@ bool rounds_wanted(int64_t K)
 // completed in d_walk_steps (a walker the slim prior stage deferred: < nsteps), and synchronises the stream.
 // *calls: likelihood calls consumed; *slots: candidates evaluated.
 // Returns RVLL_E_UNSUPPORTED without having launched anything if the step's state does not fit (huge D).
+// rw != null: run mode (RunWalk; d_walk_cost zeroed by the caller receives every walker's calls, the scalars lstar / seed /
+// walker_base are not used)
 int walk_rounds(rvll_handle* h, int64_t K, double lstar, int32_t nsteps, int32_t max_rounds, uint64_t seed, int64_t walker_base,
-                long long* calls, long long* slots)
+                long long* calls, long long* slots, const RunWalk* rw)
 {
     using namespace std::chrono;
     const int D = h->L.ndim;
@@ -171,8 +194,9 @@ int walk_rounds(rvll_handle* h, int64_t K, double lstar, int32_t nsteps, int32_t
             HIP_TRY(hipMalloc(&h->d_walk_dirs, sizeof(double) * need));
             h->walk_dirs_cap = need;
         }
-        const rvll::RoundsDirs dg{h->d_walk_dirs, h->d_walk_chol, (long long)K, (unsigned long long)walker_base, (unsigned long long)seed, D, nsteps};
-        HIP_TRY(rvll::launch_rounds_dirs(dg, 16 * h->n_cu, h->compute));
+        rvll::RoundsDirs dg{h->d_walk_dirs, h->d_walk_chol, (long long)K, (unsigned long long)walker_base, (unsigned long long)seed, D, nsteps};
+        if (rw) { dg.run = h->d_walk_run; dg.rid = h->d_walk_wid; dg.run_seed = h->d_run_seed; dg.run_chol = h->d_run_chol; }
+        HIP_TRY(rw ? rvll::launch_rounds_dirs_runs(dg, 16 * h->n_cu, h->compute) : rvll::launch_rounds_dirs(dg, 16 * h->n_cu, h->compute));
     }
     std::vector<rvll::RoundsArgs> ga((size_t)G);
     std::vector<rvll::LoglikeArgs> la((size_t)G, a);
@@ -212,6 +236,10 @@ int walk_rounds(rvll_handle* h, int64_t K, double lstar, int32_t nsteps, int32_t
         r.wrapped = h->d_walk_wrapped;
         r.D = D;  r.W = W;  r.nsteps = nsteps;  r.max_rounds = max_rounds;  r.spec_max = spec;
         r.seed = seed;  r.lstar = lstar;
+        if (rw) {
+            r.run = h->d_walk_run + row0;  r.rid = h->d_walk_wid + row0;  r.wcost = h->d_walk_cost + row0;
+            r.run_lstar = h->d_run_lstar;  r.run_seed = h->d_run_seed;
+        }
         rvll::LoglikeArgs& l = la[(size_t)g];
         l.theta = r.theta_c[0];  l.logL = res_logl;  l.flags = res_flags;  l.B = C;      // the tiles: theta -> log-L
         ta[(size_t)g] = rvll::RoundsTiles{nullptr, h->pin_rounds_dev + g, r.owner, wres_logl, wres_flags};
@@ -280,6 +308,9 @@ int walk_rounds(rvll_handle* h, int64_t K, double lstar, int32_t nsteps, int32_t
         return cu_form ? rvll::launch_rounds_cu(la[(size_t)g], ta[(size_t)g], tiles, r, s)
                        : rvll::launch_rounds_tiles(la[(size_t)g], ta[(size_t)g], tiles, r, s);
     };
+    auto step_of = [&](int g, int r, hipStream_t s) -> hipError_t {
+        return rw ? rvll::launch_rounds_step_runs(ga[(size_t)g], r, s) : rvll::launch_rounds_step(ga[(size_t)g], r, s);
+    };
     while (ndone < G && status == RVLL_OK) {
         unsigned long long sum = 0;
         bool any = false;
@@ -307,7 +338,7 @@ int walk_rounds(rvll_handle* h, int64_t K, double lstar, int32_t nsteps, int32_t
                     const int r = (int)n_tile[(size_t)g];
                     hipError_t e = hipSuccess;
                     if (prev >= 0) e = hipStreamWaitEvent(gs[(size_t)g], h->ev_chain[prev], 0);
-                    if (e == hipSuccess) e = rvll::launch_rounds_step(ga[(size_t)g], r, gs[(size_t)g]);
+                    if (e == hipSuccess) e = step_of(g, r, gs[(size_t)g]);
                     if (e == hipSuccess) e = hipEventRecord(h->ev_chain[g], gs[(size_t)g]);
                     if (e == hipSuccess) e = tiles_of(g, r, gs[(size_t)g]);
                     if (e != hipSuccess) { status = report_error(RVLL_E_HIP, "rounds walk launch failed: %s", hipGetErrorString(e)); break; }
@@ -331,7 +362,7 @@ int walk_rounds(rvll_handle* h, int64_t K, double lstar, int32_t nsteps, int32_t
                 if (n_tile[(size_t)g] >= r_max) { status = report_error(RVLL_E_HIP, "rounds walk: group %d did not finish in %lld rounds", g, r_max); break; }
                 const int r = (int)n_tile[(size_t)g];
                 const auto tl0 = steady_clock::now();
-                hipError_t e = rvll::launch_rounds_step(ga[(size_t)g], r, gs[(size_t)g]);
+                hipError_t e = step_of(g, r, gs[(size_t)g]);
                 if (e == hipSuccess) e = tiles_of(g, r, gs[(size_t)g]);
                 launch_ns += duration_cast<nanoseconds>(steady_clock::now() - tl0).count();  n_launch += 2;
                 if (e != hipSuccess) { status = report_error(RVLL_E_HIP, "rounds walk launch failed: %s", hipGetErrorString(e)); break; }
@@ -407,12 +438,19 @@ int walk_rounds(rvll_handle* h, int64_t K, double lstar, int32_t nsteps, int32_t
 // The walk of the K rows resident in d_walk_u / d_walk_theta / d_walk_logl (chol and wrapped already uploaded): every
 // launch it takes — the first part, the rest (rows dealt to the workgroups by what they cost so far), the full-solver
 // finish of rows the slim kernel deferred — leaves the end points in those buffers.  Synchronises the compute stream.
+// rw != null: run mode (RunWalk; lstar / seed are not used, walker_base is 0): every launch also counts the calls of each
+// row into rw->row_calls.  The rows form (RVLL_WALK_ROWS) has no run mode.
 int walk_core(rvll_handle* h, int64_t K, double lstar, int32_t nsteps, int32_t max_rounds, uint64_t seed,
-              int64_t walker_base, int64_t* ncalls)
+              int64_t walker_base, int64_t* ncalls, RunWalk* rw = nullptr)
 {
     const size_t D = (size_t)h->L.ndim;
     hipStream_t st = h->compute;
     int rc;
+    if (rw) {
+        const char* e = getenv("RVLL_WALK_ROWS");
+        if (e && atoi(e) >= 1) return report_error(RVLL_E_UNSUPPORTED, "rvll_slice_walk_runs: the rows form (RVLL_WALK_ROWS) has no run mode");
+        HIP_TRY(hipMemsetAsync(h->d_walk_cost, 0, sizeof(int32_t) * (size_t)K, st));
+    }
     HIP_TRY(hipMemsetAsync(h->d_walk_ncalls, 0, kWalkWords * sizeof(unsigned long long), st));
     HIP_TRY(hipMemsetAsync(h->d_walk_wflag, 0, sizeof(int32_t) * (size_t)K, st));
     // the walk keeps per-walker state in LDS next to the tile's carve: shrink the group until both fit
@@ -463,7 +501,7 @@ int walk_core(rvll_handle* h, int64_t K, double lstar, int32_t nsteps, int32_t m
     bool by_rounds = false;
     h->walk_rounds_used = 0;
     if (slim && rounds_wanted(K)) {
-        rc = walk_rounds(h, K, lstar, nsteps, max_rounds, seed, walker_base, &rounds_calls, &rounds_slots);
+        rc = walk_rounds(h, K, lstar, nsteps, max_rounds, seed, walker_base, &rounds_calls, &rounds_slots, rw);
         if (rc == RVLL_OK) by_rounds = true;
         else if (rc != RVLL_E_UNSUPPORTED) return rc;
     }
@@ -474,6 +512,11 @@ int walk_core(rvll_handle* h, int64_t K, double lstar, int32_t nsteps, int32_t m
                      nsteps, max_rounds, (unsigned long long)seed, lstar, h->d_walk_ncalls,
                      h->d_walk_steps, nullptr, nullptr, (long long)walker_base, spec, h->d_walk_ncalls + 1,
                      h->d_walk_ncalls + kWalkWords - 1, nullptr, nullptr, 0, h->d_walk_wflag};
+    if (rw) {
+        w.run = h->d_walk_run;  w.run_lstar = h->d_run_lstar;  w.run_seed = h->d_run_seed;  w.run_chol = h->d_run_chol;
+        w.walker_id = h->d_walk_wid;                   // the row's index inside its run
+        w.cost = h->d_walk_cost;                       // every launch counts every row's calls
+    }
     // no more workgroups than the chip holds at once; freed walker slots draw the remaining rows from a queue
     // (RVLL_WALK_QUEUE, a measurement / test switch: 0 = one workgroup per PB rows, as many residency rounds as that
     // takes; n > 0 = as many workgroups as n compute units hold, so that a small walk goes through the queue too)
@@ -529,6 +572,11 @@ int walk_core(rvll_handle* h, int64_t K, double lstar, int32_t nsteps, int32_t m
         const int64_t K2 = K - nkey0;
         w.nsteps = nsteps;
         w.cost = nullptr;
+        if (rw) {                                      // the first part's calls; the second part counts afresh
+            for (int64_t i = 0; i < K; ++i) rw->row_calls[(size_t)i] += cost[(size_t)i];
+            HIP_TRY(hipMemsetAsync(h->d_walk_cost, 0, sizeof(int32_t) * (size_t)K, st));
+            w.cost = h->d_walk_cost;
+        }
         w.step_start = h->d_walk_steps;    // every row resumes where the first part left it (read before it is rewritten)
         if (K2 > 0 && rows_form) {
             // as many workgroups as the chip holds, every one an equal share of the rows (snake deal of the sorted order,
@@ -599,6 +647,10 @@ int walk_core(rvll_handle* h, int64_t K, double lstar, int32_t nsteps, int32_t m
         w.order = nullptr;
         w.step_start = nullptr;
     }
+    if (rw) {
+        rc = run_calls_add(h, rw, K, nullptr);         // the calls of the single-kernel launch (or its second part), or of the rounds
+        if (rc) return rc;
+    }
     unsigned long long evaluated[kWalkWords] = {};
     h->walk_evaluated = 0;
     std::vector<int32_t> steps(slim ? (size_t)K : 0), wf((size_t)K);
@@ -635,7 +687,14 @@ int walk_core(rvll_handle* h, int64_t K, double lstar, int32_t nsteps, int32_t m
             HIP_TRY(hipMemcpyAsync(h->d_walk_u, su.data(), sizeof(double) * D * M, hipMemcpyHostToDevice, st));
             HIP_TRY(hipMemcpyAsync(h->d_walk_theta, sth.data(), sizeof(double) * D * M, hipMemcpyHostToDevice, st));
             HIP_TRY(hipMemcpyAsync(h->d_walk_logl, sl.data(), sizeof(double) * M, hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(h->d_walk_wid, ids.data(), sizeof(int32_t) * M, hipMemcpyHostToDevice, st));
+            std::vector<int32_t> wid_sub(ids), run_sub;
+            if (rw) {                                  // run mode: the rows' indices inside their runs, and their runs
+                run_sub.resize(M);
+                for (size_t j = 0; j < M; ++j) { wid_sub[j] = rw->rid[(size_t)ids[j]]; run_sub[j] = rw->run[(size_t)ids[j]]; }
+                HIP_TRY(hipMemcpyAsync(h->d_walk_run, run_sub.data(), sizeof(int32_t) * M, hipMemcpyHostToDevice, st));
+                HIP_TRY(hipMemsetAsync(h->d_walk_cost, 0, sizeof(int32_t) * M, st));
+            }
+            HIP_TRY(hipMemcpyAsync(h->d_walk_wid, wid_sub.data(), sizeof(int32_t) * M, hipMemcpyHostToDevice, st));
             HIP_TRY(hipMemcpyAsync(h->d_walk_start, start.data(), sizeof(int32_t) * M, hipMemcpyHostToDevice, st));
             std::vector<int32_t> wf_sub(M);
             for (size_t j = 0; j < M; ++j) wf_sub[j] = wf[(size_t)ids[j]];
@@ -648,6 +707,7 @@ int walk_core(rvll_handle* h, int64_t K, double lstar, int32_t nsteps, int32_t m
             w2.K = (long long)M;
             w2.walker_id = h->d_walk_wid;
             w2.step_start = h->d_walk_start;
+            if (rw) w2.cost = h->d_walk_cost;
             HIP_TRY(rvll::launch_slice_walk(a2, w2, true, max_cus, st));
             HIP_TRY(hipMemcpyAsync(su.data(), h->d_walk_u, sizeof(double) * D * M, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipMemcpyAsync(sth.data(), h->d_walk_theta, sizeof(double) * D * M, hipMemcpyDeviceToHost, st));
@@ -656,6 +716,10 @@ int walk_core(rvll_handle* h, int64_t K, double lstar, int32_t nsteps, int32_t m
             HIP_TRY(hipMemcpyAsync(evaluated, h->d_walk_ncalls, sizeof evaluated, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
             total += (long long)evaluated[0];
+            if (rw) {
+                rc = run_calls_add(h, rw, (int64_t)M, ids.data());
+                if (rc) return rc;
+            }
             h->walk_evaluated += (long long)evaluated[1];
             for (int k = 0; k < 6; ++k) h->walk_phase[k] += evaluated[2 + k];
             for (size_t j = 0; j < M; ++j) {
@@ -704,12 +768,13 @@ int walk_check_args(rvll_handle* h, int64_t K, int32_t nsteps, int32_t max_round
     return RVLL_OK;
 }
 
+// chol may be null (run mode: the factors are the runs')
 int walk_upload_frame(rvll_handle* h, const double* chol, const int32_t* wrapped)
 {
     const size_t D = (size_t)h->L.ndim;
     std::vector<int32_t> wr(D, 0);
     if (wrapped) for (size_t k = 0; k < D; ++k) wr[k] = wrapped[k] != 0;
-    HIP_TRY(hipMemcpyAsync(h->d_walk_chol, chol, sizeof(double) * D * D, hipMemcpyHostToDevice, h->compute));
+    if (chol) HIP_TRY(hipMemcpyAsync(h->d_walk_chol, chol, sizeof(double) * D * D, hipMemcpyHostToDevice, h->compute));
     HIP_TRY(hipMemcpyAsync(h->d_walk_wrapped, wr.data(), sizeof(int32_t) * D, hipMemcpyHostToDevice, h->compute));
     HIP_TRY(hipStreamSynchronize(h->compute));         // wr (and pageable sources) may go out of scope
     return RVLL_OK;
@@ -745,6 +810,73 @@ int rvll_slice_walk(rvll_handle* h, double* cube, double* theta, double* logl, i
     HIP_TRY(hipMemcpyAsync(theta, h->d_walk_theta, sizeof(double) * D * (size_t)K, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(logl, h->d_walk_logl, sizeof(double) * (size_t)K, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
+    return RVLL_OK;
+}
+
+int rvll_slice_walk_runs(rvll_handle* h, double* cube, double* theta, double* logl, const int64_t* run_start, int32_t R,
+                         const double* lstar, const double* chol, const uint64_t* seed, const int32_t* wrapped,
+                         int32_t nsteps, int32_t max_rounds, int64_t* ncalls)
+{
+    int rc = use_device(h);
+    if (rc) return rc;
+    if (R < 0 || (R > 0 && !run_start)) return report_error(RVLL_E_INVALID, "rvll_slice_walk_runs: bad run table");
+    if (ncalls) for (int32_t r = 0; r < R; ++r) ncalls[r] = 0;
+    if (R > 0 && run_start[0] != 0) return report_error(RVLL_E_INVALID, "rvll_slice_walk_runs: run_start[0] must be 0");
+    for (int32_t r = 0; r < R; ++r)
+        if (run_start[r + 1] < run_start[r]) return report_error(RVLL_E_INVALID, "rvll_slice_walk_runs: run_start decreases at run %d", (int)r);
+    const int64_t K = R > 0 ? run_start[R] : 0;
+    rc = walk_check_args(h, K, nsteps, max_rounds, 0);
+    if (rc) return rc;
+    if (K == 0 || nsteps == 0) return RVLL_OK;
+    if (!cube || !theta || !logl || !lstar || !chol || !seed) return report_error(RVLL_E_INVALID, "null buffer");
+    {
+        const char* e = getenv("RVLL_WALK_ROWS");
+        if (e && atoi(e) >= 1) return report_error(RVLL_E_UNSUPPORTED, "rvll_slice_walk_runs: the rows form (RVLL_WALK_ROWS) has no run mode");
+    }
+    const size_t D = (size_t)h->L.ndim;
+    rc = walk_reserve(h, K);
+    if (rc) return rc;
+    hipStream_t st = h->compute;
+    if (K > h->runs_rows_cap) {
+        HIP_TRY(hipStreamSynchronize(st));
+        dev_free(h->d_walk_run);
+        h->runs_rows_cap = 0;
+        HIP_TRY(hipMalloc(&h->d_walk_run, sizeof(int32_t) * (size_t)h->walk_cap));
+        h->runs_rows_cap = h->walk_cap;
+    }
+    if (R > h->runs_cap) {
+        HIP_TRY(hipStreamSynchronize(st));
+        dev_free(h->d_run_lstar); dev_free(h->d_run_seed); dev_free(h->d_run_chol);
+        h->runs_cap = 0;
+        const size_t cap = (size_t)std::max<int32_t>(R, 64);
+        HIP_TRY(hipMalloc(&h->d_run_lstar, sizeof(double) * cap));
+        HIP_TRY(hipMalloc(&h->d_run_seed, sizeof(unsigned long long) * cap));
+        HIP_TRY(hipMalloc(&h->d_run_chol, sizeof(double) * D * D * cap));
+        h->runs_cap = (long long)cap;
+    }
+    std::vector<int32_t> run((size_t)K), rid((size_t)K);
+    for (int32_t r = 0; r < R; ++r)
+        for (int64_t i = run_start[r]; i < run_start[r + 1]; ++i) { run[(size_t)i] = r; rid[(size_t)i] = (int32_t)(i - run_start[r]); }
+    HIP_TRY(hipMemcpyAsync(h->d_walk_u, cube, sizeof(double) * D * (size_t)K, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(h->d_walk_theta, theta, sizeof(double) * D * (size_t)K, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(h->d_walk_logl, logl, sizeof(double) * (size_t)K, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(h->d_walk_run, run.data(), sizeof(int32_t) * (size_t)K, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(h->d_walk_wid, rid.data(), sizeof(int32_t) * (size_t)K, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(h->d_run_lstar, lstar, sizeof(double) * (size_t)R, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(h->d_run_seed, seed, sizeof(uint64_t) * (size_t)R, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(h->d_run_chol, chol, sizeof(double) * D * D * (size_t)R, hipMemcpyHostToDevice, st));
+    rc = walk_upload_frame(h, nullptr, wrapped);       // (synchronises: the host tables above may go out of scope after it)
+    if (rc) return rc;
+    RunWalk rw{run.data(), rid.data(), std::vector<long long>((size_t)K, 0)};
+    rc = walk_core(h, K, 0., nsteps, max_rounds, 0, 0, nullptr, &rw);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(cube, h->d_walk_u, sizeof(double) * D * (size_t)K, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(theta, h->d_walk_theta, sizeof(double) * D * (size_t)K, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(logl, h->d_walk_logl, sizeof(double) * (size_t)K, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (ncalls)
+        for (int32_t r = 0; r < R; ++r)
+            for (int64_t i = run_start[r]; i < run_start[r + 1]; ++i) ncalls[r] += rw.row_calls[(size_t)i];
     return RVLL_OK;
 }
 

@@ -318,6 +318,37 @@ class GpuRVModel:
             int(walker_base), C.byref(ncalls)))
         return cube, theta, logl, int(ncalls.value)
 
+    def slice_walk_runs(self, cube, theta, logl, run_start, lstar, chol, wrapped=None, nsteps=10, max_rounds=200, seeds=()):
+        """The walks of R independent runs in ONE device walk (rvll_slice_walk_runs).  Rows run_start[r] .. run_start[r + 1]
+        of cube / theta / logl are the walkers of run r, which walks inside logL > lstar[r] with the whitening factor
+        chol[r] ([R, ndim, ndim]) and seed seeds[r].  Returns (cube, theta, logl, ncalls[R]); run r's rows and ncalls[r] are
+        bit for bit those of slice_walk(its rows, lstar[r], chol[r], wrapped, nsteps, max_rounds, seeds[r])."""
+        cube = np.array(self._theta2d(cube), dtype=np.float64, order="C")
+        theta = np.array(self._theta2d(theta), dtype=np.float64, order="C")
+        logl = np.array(logl, dtype=np.float64).reshape(-1)
+        k = cube.shape[0]
+        if theta.shape != cube.shape or logl.shape[0] != k:
+            raise ValueError("cube, theta and logl must describe the same walkers")
+        run_start = np.ascontiguousarray(run_start, dtype=np.int64).reshape(-1)
+        nrun = run_start.shape[0] - 1
+        if nrun < 0 or run_start[0] != 0 or run_start[-1] != k or np.any(np.diff(run_start) < 0):
+            raise ValueError("run_start must rise from 0 to the number of walkers")
+        lstar = np.ascontiguousarray(lstar, dtype=np.float64).reshape(-1)
+        seeds = np.array([int(s) & (2 ** 64 - 1) for s in seeds], dtype=np.uint64)
+        if lstar.shape[0] != nrun or seeds.shape[0] != nrun:
+            raise ValueError("lstar and seeds need one entry per run")
+        chol = np.ascontiguousarray(chol, dtype=np.float64)
+        if chol.shape != (nrun, self.ndim, self.ndim):
+            raise ValueError("chol must be [runs, ndim, ndim]")
+        wr = None if wrapped is None else np.ascontiguousarray(np.asarray(wrapped, dtype=bool).astype(np.int32))
+        ncalls = np.zeros(nrun, dtype=np.int64)
+        _abi.check(self._lib.rvll_slice_walk_runs(
+            self._h, _abi.as_dp(cube), _abi.as_dp(theta), _abi.as_dp(logl),
+            run_start.ctypes.data_as(C.POINTER(C.c_int64)), nrun, _abi.as_dp(lstar), _abi.as_dp(chol),
+            seeds.ctypes.data_as(C.POINTER(C.c_uint64)), _abi.as_ip(wr) if wr is not None else None,
+            int(nsteps), int(max_rounds), ncalls.ctypes.data_as(C.POINTER(C.c_int64))))
+        return cube, theta, logl, ncalls
+
     # ---- live set resident on the device (nested.run_nested_slice(..., live=model)) -----------------------------
     def live_init(self, cube):
         """N unit-cube rows -> prior transform -> log-L; the live set stays on the device.  Returns log-L [N]."""

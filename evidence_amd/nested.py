@@ -171,6 +171,29 @@ def _stable_argsort(x):
     return order
 
 
+def _deaths(logz, h, logx, dl, nlive, kbatch):
+    """The kbatch deaths of an iteration in order, live count nlive - i while they die — vectorised (this loop used to cost
+    more than the likelihood calls): X shrinks by exp(-1/(nlive - i)), w_i = (X_{i-1} - X_i) L_i, Z accumulates, and the
+    information H follows from A = sum_j w_j ln L_j / Z = H + ln Z.  dl: the dying points' log-L in ascending order.
+    Returns (logw, logz, h, logx) after them."""
+    logx_seq = logx - np.cumsum(1.0 / (nlive - np.arange(kbatch)))
+    logx_prev = np.concatenate([[logx], logx_seq[:-1]])
+    logw = logx_prev + np.log1p(-np.exp(logx_seq - logx_prev)) + dl
+    logz_seq = np.logaddexp.accumulate(np.concatenate([[logz], logw]))[1:]
+    big = max(logz, float(np.max(logw))) if np.isfinite(logz) else float(np.max(logw))
+    a_prev = np.exp(logz - big) * (h + logz) if np.isfinite(logz) else 0.0
+    a_last = np.exp(big - logz_seq[-1]) * (a_prev + float(np.sum(np.exp(logw - big) * dl)))
+    logz, logx = float(logz_seq[-1]), float(logx_seq[-1])
+    return logw, logz, float(a_last - logz), logx
+
+
+def _whitening(ua):
+    """Lower-triangular factor of the covariance of the unit-cube rows ua (the surviving live points)."""
+    d0 = ua - ua.mean(axis=0)
+    cov = d0.T @ d0 / max(1, len(ua) - 1) + 1e-14 * np.eye(ua.shape[1])
+    return np.linalg.cholesky(cov)
+
+
 def run_nested_slice(prior: Callable, loglike: Callable, ndim: int, nlive: Optional[int] = None, kbatch: Optional[int] = None,
                      nsteps: Optional[int] = None, dlogz: float = 0.5, max_iter: int = 10_000_000,
                      max_calls: int = 50_000_000, wrapped=None, seed: int = 0,
@@ -256,18 +279,7 @@ def run_nested_slice(prior: Callable, loglike: Callable, ndim: int, nlive: Optio
             pending = _helper().submit(live.live_step, order, kbatch, start, lstar, wrapped, nsteps, 200, seed_it)
         else:
             pending = None
-        # the kbatch deaths in order, live count nlive - i while they die — vectorised (this loop used to cost more
-        # than the likelihood calls): X shrinks by exp(-1/(nlive - i)), w_i = (X_{i-1} - X_i) L_i, Z accumulates,
-        # and the information H follows from A = sum_j w_j ln L_j / Z = H + ln Z
-        logx_seq = logx - np.cumsum(1.0 / (nlive - np.arange(kbatch)))
-        logx_prev = np.concatenate([[logx], logx_seq[:-1]])
-        logw = logx_prev + np.log1p(-np.exp(logx_seq - logx_prev)) + dl
-        logz_seq = np.logaddexp.accumulate(np.concatenate([[logz], logw]))[1:]
-        big = max(logz, float(np.max(logw))) if np.isfinite(logz) else float(np.max(logw))
-        a_prev = np.exp(logz - big) * (h + logz) if np.isfinite(logz) else 0.0
-        a_last = np.exp(big - logz_seq[-1]) * (a_prev + float(np.sum(np.exp(logw - big) * dl)))
-        logz, logx = float(logz_seq[-1]), float(logx_seq[-1])
-        h = float(a_last - logz)
+        logw, logz, h, logx = _deaths(logz, h, logx, dl, nlive, kbatch)
         if live is None:
             dead_theta.append(theta[dead])                                                # (index arrays: already copies)
         dead_logl.append(dl); dead_logw.append(logw)
@@ -287,12 +299,7 @@ def run_nested_slice(prior: Callable, loglike: Callable, ndim: int, nlive: Optio
             continue
         alive = order[kbatch:]
         # whitening from the surviving live points
-        chol = None
-        if u is not None:
-            ua = u[alive]
-            d0 = ua - ua.mean(axis=0)
-            cov = d0.T @ d0 / max(1, len(alive) - 1) + 1e-14 * np.eye(ndim)
-            chol = np.linalg.cholesky(cov)
+        chol = _whitening(u[alive]) if u is not None else None
         start = alive[rng.integers(0, len(alive), kbatch)]
         if live is not None:
             # live_chol="host": order and start rows up, the new log-L of the replaced rows down, and the mirror of the rows
@@ -357,3 +364,110 @@ def run_nested_slice(prior: Callable, loglike: Callable, ndim: int, nlive: Optio
     all_logw = np.concatenate(dead_logw + [logw_live]) - logz_final
     return NestedResult(float(logz_final), float(np.sqrt(max(h, 0.0) / nlive)), it, ncall, float(h),
                         all_theta, all_logl, all_logw, timing)
+
+
+class _EnsembleRun:
+    """One run of run_nested_ensemble: the state run_nested_slice keeps in its locals."""
+
+    def __init__(self, seed, nlive, ndim):
+        self.rng = np.random.default_rng(seed)
+        self.u = self.rng.random((nlive, ndim))
+        self.theta = self.logl = None
+        self.ncall = nlive
+        self.dead_theta, self.dead_logl, self.dead_logw = [], [], []
+        self.logz, self.h, self.logx = -np.inf, 0.0, 0.0
+        self.it = 0
+        self.done = False
+        self.timing = {"host_s": 0.0, "walk_s": 0.0, "turns": 0}
+
+
+def run_nested_ensemble(prior: Callable, loglike: Callable, ndim: int, seeds, nlive: Optional[int] = None,
+                        kbatch: Optional[int] = None, nsteps: Optional[int] = None, dlogz: float = 0.5,
+                        max_iter: int = 10_000_000, max_calls: int = 50_000_000, wrapped=None,
+                        walker_runs: Optional[Callable] = None) -> list:
+    """len(seeds) independent runs of run_nested_slice in lockstep, their walks in ONE call per iteration.
+
+    The reference's FIP workflow repeats independent runs of every model and takes the median and spread of ln Z over them
+    (evidence/fip_criterion.py).  One run's walk is a few hundred walkers, far too few to fill a GPU, and a chain of
+    dependent moves whose time is set by latency: the walkers of R runs walk side by side for about the cost of one.
+    `walker_runs(cube, theta, logl, run_start, lstar, chol, wrapped, nsteps, max_rounds, seeds) -> (cube, theta, logl,
+    ncalls[R])` walks the rows run_start[r] .. run_start[r + 1] of run r inside logL > lstar[r] with chol[r] and seeds[r]
+    (GpuRVModel.slice_walk_runs).
+
+    The initial live points of all runs are one prior + loglike call.  Every iteration then does, run by run, the
+    bookkeeping of run_nested_slice's `walker=` path — sort, deaths, evidence and information sums, whitening from the
+    survivors, start rows and walk seed drawn from the run's own default_rng(seed) — and makes one `walker_runs` call for
+    the walkers of every run that is still going.  A run that meets its own stop (dlogz, max_iter, max_calls) leaves the
+    lockstep.  result[r] is run_nested_slice(prior, loglike, ndim, seed=seeds[r], walker=<the same walk for one run>,
+    same settings) bit for bit; its `timing` holds the host seconds of its own bookkeeping, the seconds of the shared walk
+    calls it took part in, and their number."""
+    seeds = [int(s) for s in seeds]
+    if not seeds:
+        raise ValueError("need at least one seed")
+    if walker_runs is None:
+        raise ValueError("walker_runs is required (GpuRVModel.slice_walk_runs)")
+    defaults = ultranest_defaults(ndim)
+    nlive = int(nlive or defaults["nlive"])
+    kbatch = int(kbatch or max(1, nlive // 4))
+    if not 1 <= kbatch < nlive:
+        raise ValueError("need 1 <= kbatch < nlive")
+    nsteps = int(nsteps or defaults["nsteps"])
+    wrapped = None if wrapped is None else np.asarray(wrapped, dtype=bool)
+    runs = [_EnsembleRun(s, nlive, ndim) for s in seeds]
+    theta = np.asarray(prior(np.concatenate([r.u for r in runs])), dtype=np.float64)
+    logl = np.asarray(loglike(theta), dtype=np.float64)
+    for i, r in enumerate(runs):
+        r.theta, r.logl = theta[i * nlive:(i + 1) * nlive].copy(), logl[i * nlive:(i + 1) * nlive].copy()
+    stop_gap = np.log(np.expm1(dlogz))
+    while True:
+        turn = []                                   # (run, dead rows, start rows, lstar, chol, walk seed)
+        for r in runs:
+            if r.done:
+                continue
+            if not (r.it < max_iter and r.ncall < max_calls):
+                r.done = True
+                continue
+            t0 = time.perf_counter()
+            order = _stable_argsort(r.logl)
+            dead = order[:kbatch]
+            lstar = r.logl[dead[-1]]
+            dl = r.logl[dead]
+            logw, r.logz, r.h, r.logx = _deaths(r.logz, r.h, r.logx, dl, nlive, kbatch)
+            r.dead_theta.append(r.theta[dead])
+            r.dead_logl.append(dl); r.dead_logw.append(logw)
+            r.it += kbatch
+            alive = order[kbatch:]
+            chol = _whitening(r.u[alive])
+            start = alive[r.rng.integers(0, len(alive), kbatch)]
+            turn.append((r, dead, start, lstar, chol, int(r.rng.integers(0, 2 ** 62))))
+            r.timing["host_s"] += time.perf_counter() - t0
+        if not turn:
+            break
+        run_start = np.arange(len(turn) + 1, dtype=np.int64) * kbatch
+        t0 = time.perf_counter()
+        wu, wt, wl, used = walker_runs(np.concatenate([r.u[st] for r, _, st, *_ in turn]),
+                                       np.concatenate([r.theta[st] for r, _, st, *_ in turn]),
+                                       np.concatenate([r.logl[st] for r, _, st, *_ in turn]),
+                                       run_start, np.array([t[3] for t in turn]), np.stack([t[4] for t in turn]),
+                                       wrapped, nsteps, 200, [t[5] for t in turn])
+        t_walk = time.perf_counter() - t0
+        for j, (r, dead, *_rest) in enumerate(turn):
+            t0 = time.perf_counter()
+            rows = slice(j * kbatch, (j + 1) * kbatch)
+            r.ncall += int(used[j])
+            r.u[dead], r.theta[dead], r.logl[dead] = wu[rows], wt[rows], wl[rows]
+            if np.max(r.logl) + r.logx < r.logz + stop_gap:
+                r.done = True
+            r.timing["walk_s"] += t_walk
+            r.timing["turns"] += 1
+            r.timing["host_s"] += time.perf_counter() - t0
+    out = []
+    for r in runs:
+        logw_live = r.logx - np.log(nlive) + r.logl
+        logz_final = np.logaddexp(r.logz, _logaddexp_many(logw_live))
+        all_theta = np.vstack([a.reshape(-1, ndim) for a in r.dead_theta] + [r.theta])
+        all_logl = np.concatenate(r.dead_logl + [r.logl])
+        all_logw = np.concatenate(r.dead_logw + [logw_live]) - logz_final
+        out.append(NestedResult(float(logz_final), float(np.sqrt(max(r.h, 0.0) / nlive)), r.it, r.ncall, float(r.h),
+                                all_theta, all_logl, all_logw, r.timing))
+    return out

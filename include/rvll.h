@@ -51,7 +51,8 @@ extern "C" {
 #endif
 
 #define RVLL_VERSION_MAJOR 0
-#define RVLL_VERSION_MINOR 2   /* 0.2: rvll_slice_walk takes walker_base; RVLL_FLAG_WANDERED; resident live set */
+#define RVLL_VERSION_MINOR 3   /* 0.2: rvll_slice_walk takes walker_base; RVLL_FLAG_WANDERED; resident live set
+                                  0.3: rvll_slice_walk_runs */
 
 /* ---- error codes ------------------------------------------------------ */
 #define RVLL_OK             0
@@ -245,6 +246,24 @@ int rvll_prior_loglike_batch(rvll_handle* h, const double* cube, int64_t B,
 int rvll_slice_walk(rvll_handle* h, double* cube, double* theta, double* logl, int64_t K, double lstar,
                     const double* chol, const int32_t* wrapped /*[ndim] or NULL*/, int32_t nsteps,
                     int32_t max_rounds, uint64_t seed, int64_t walker_base, int64_t* ncalls);
+/* The walks of R independent runs of one model in ONE walk (the repeats of a FIP workflow: the same model sampled R times
+ * with different seeds, ln Z and p(k | y) taken over the runs).  One run's walk is a few hundred walkers — a few dozen
+ * workgroups on a chip that holds thousands, its time set by the latency of a chain of dependent moves; the walkers of R runs
+ * walk side by side for about the cost of one.  Walkers are grouped by run: rows run_start[r] .. run_start[r + 1] of
+ * cube / theta / logl [K, ndim], [K, ndim], [K] belong to run r (K = run_start[R], run_start[0] = 0; empty runs are allowed).
+ * Run r has its own lstar[r], whitening factor chol[r] ([R, ndim, ndim] row-major lower-triangular) and seed[r]; wrapped,
+ * nsteps and max_rounds are common.  End points, theta, log-L and ncalls[r] of run r are bit for bit those of
+ * rvll_slice_walk(rows of run r, lstar[r], chol[r], wrapped, nsteps, max_rounds, seed[r], walker_base = 0): the walker at row
+ * run_start[r] + i draws from the counters (seed[r], i, move, draw), and its calls are counted per walker in every form the
+ * walk takes (the single-kernel forms and their parts, the rounds form, the full-solver finish of walkers the slim prior
+ * stage deferred), then summed by run.  ncalls [R] may be NULL.  The measurement switch RVLL_WALK_ROWS (the rows forms) has
+ * no run mode: with it set this returns RVLL_E_UNSUPPORTED.  rvll_slice_walk_evaluated / _rounds report on this walk as on
+ * rvll_slice_walk's.  Needs rvll_set_priors.                                                                                */
+int rvll_slice_walk_runs(rvll_handle* h, double* cube, double* theta, double* logl /*[K, ndim], [K, ndim], [K]*/,
+                         const int64_t* run_start /*[R + 1]*/, int32_t R,
+                         const double* lstar /*[R]*/, const double* chol /*[R, ndim, ndim]*/, const uint64_t* seed /*[R]*/,
+                         const int32_t* wrapped /*[ndim] or NULL*/, int32_t nsteps, int32_t max_rounds,
+                         int64_t* ncalls /*[R] out*/);
 /* A walker's moves are a chain of dependent evaluations; when walkers of a workgroup have finished, the free slots of
  * its tile evaluate, for the walkers that are left, up to max_ahead candidates of the current move per iteration:
  * candidate r+1 is the one the walker draws if candidate r is rejected (the shrunk bracket is known in advance), and
