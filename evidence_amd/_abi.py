@@ -19,7 +19,7 @@ ERROR_NAMES = {
 FLAG_INVALID_ORBIT = 1
 FLAG_NONCONVERGED = 2
 FLAG_WANDERED = 4                  # a Kepler solve took > 8 Newton steps: log-L there is conditioned to ~1e-9 (rvll.h)
-ABI_VERSION = (0, 3)               # RVLL_VERSION_MAJOR / MINOR these bindings were written against
+ABI_VERSION = (0, 4)               # RVLL_VERSION_MAJOR / MINOR these bindings were written against
 
 K_K1, K_LOGK1 = 0, 1
 P_PERIOD, P_LOGPERIOD = 0, 1
@@ -101,6 +101,8 @@ PROTOTYPES = {
                                   C.c_uint64, C.c_int64, C.POINTER(C.c_int64)]),
     "rvll_slice_walk_runs": (C.c_int, [Handle, _dp, _dp, _dp, C.POINTER(C.c_int64), C.c_int32, _dp, _dp,
                                        C.POINTER(C.c_uint64), _ip, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    "rvll_cluster_runs": (C.c_int, [Handle, _dp, C.POINTER(C.c_int64), C.c_int64, _dp, _ip, C.c_int,
+                                    C.POINTER(C.c_uint64), _ip, _ip, _dp]),
     "rvll_live_init": (C.c_int, [Handle, _dp, C.c_int64, _dp]),
     "rvll_live_step": (C.c_int, [Handle, _ip, C.c_int64, _ip, C.c_double, _dp, _ip, C.c_int32, C.c_int32, C.c_uint64,
                                  C.c_int64, C.POINTER(C.c_int64), _dp, _dp]),

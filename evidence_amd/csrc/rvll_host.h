@@ -4,6 +4,7 @@
 //                       streamed host batches, curves, self tests
 //   rvll_walk_host.hip  the sampler's proposal step: the device walk in its forms, the resident live set (rvll_live_*)
 //   rvll_comm.hip       multi-GPU: RCCL communicators, lanes, all-gathers
+//   rvll_cluster_host.hip  MLFriends clustering of many row sets (rvll_cluster_runs)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -180,6 +181,12 @@ struct rvll_handle {
     double sorted_lstar = 0.;
     long long dead_n = 0, dead_cap = 0;
     double *d_dead_theta = nullptr, *d_dead_logl = nullptr;
+
+    // clustering (rvll_cluster_runs): grow-only device blocks for the packed inputs, the forest and per-run maxima, the packed outputs
+    void* d_cl_in = nullptr;
+    void* d_cl_work = nullptr;
+    void* d_cl_out = nullptr;
+    size_t cl_in_cap = 0, cl_work_cap = 0, cl_out_cap = 0;   // bytes
 
     hipEvent_t marks[2] = {nullptr, nullptr};   // rvll_dev_mark: HIP events on lane 0's stream
 

@@ -309,4 +309,29 @@ hipError_t launch_keprv(const LoglikeArgs& a, const double* times, int Nt, unsig
 hipError_t launch_debug_eval(int op, const double* x, const double* y, long long n, double* out, hipStream_t stream);
 hipError_t launch_fill_cube(double* cube, long long n, uint64_t seed, hipStream_t stream);
 
+// ---- MLFriends clustering of many row sets (rvll_cluster.hip; rvll_cluster_runs) ---------------------------
+constexpr int kClusterMaxBoot = 32;
+constexpr int kClusterMaxDims = 64;              // a row's coordinates stay in registers
+constexpr int kClusterSlots = 34;                // per run: the maxima of the 32 bootstraps, the nearest-neighbour maximum, and
+                                                 // the bootstraps with a kept row (low word) and with a left-out row (high word)
+constexpr size_t kClusterTileBytes = 16384;      // LDS of a workgroup's tile of rows
+struct ClusterArgs {
+    const double* cube;          // [N, D]
+    const double* scale;         // [R, D]
+    const long long* run_start;  // [R + 1]
+    const unsigned long long* seeds;   // [R]
+    const int32_t* blocks;       // [nblocks, 2]: (run, first row) of every workgroup of the row kernels
+    long long nblocks;
+    int R, D, nboot, tile_rows;
+    unsigned long long wrapped;  // bit d: dimension d is circular
+    int32_t* parent;             // [N] union-find forest
+    unsigned long long* slots;   // [R, kClusterSlots], zeroed before the launch
+    int32_t* labels;             // [N]
+    int32_t* nclusters;          // [R]
+    double* radius2;             // [R]
+};
+size_t cluster_lds_bytes(int D, int tile_rows);
+int cluster_tile_rows(int D);
+hipError_t launch_cluster(const ClusterArgs& a, hipStream_t stream);
+
 }  // namespace rvll

@@ -349,6 +349,41 @@ class GpuRVModel:
             int(nsteps), int(max_rounds), ncalls.ctypes.data_as(C.POINTER(C.c_int64))))
         return cube, theta, logl, ncalls
 
+    def cluster_runs(self, cube, run_start, scale, wrapped=None, nboot=30, seeds=()):
+        """MLFriends clustering of R independent row sets in one device call (rvll_cluster_runs).  Rows
+        run_start[r] .. run_start[r + 1] of cube ([N, ndim] unit-cube rows) are run r, with metric scale[r] ([R, ndim]) and
+        bootstrap seed seeds[r]; wrapped [ndim] marks circular dimensions.  Returns (labels [N] int32, nclusters [R] int32,
+        radius2 [R] float64), bit for bit those of clustering.cluster_runs."""
+        cube = np.ascontiguousarray(self._theta2d(cube), dtype=np.float64)
+        run_start = np.ascontiguousarray(run_start, dtype=np.int64).reshape(-1)
+        R = run_start.shape[0] - 1
+        if R < 0:
+            raise ValueError("run_start needs at least one entry")
+        scale = np.ascontiguousarray(scale, dtype=np.float64)
+        if scale.size != R * self.ndim:
+            raise ValueError("scale must be [runs, ndim]")
+        seeds = np.array([int(s) & (2 ** 64 - 1) for s in seeds], dtype=np.uint64)
+        if seeds.shape[0] != R:
+            raise ValueError("seeds needs one entry per run")
+        if R > 0 and run_start[-1] != cube.shape[0]:
+            raise ValueError("run_start must end at the number of rows")
+        wr = None if wrapped is None else np.ascontiguousarray(np.asarray(wrapped, dtype=bool).astype(np.int32))
+        labels = np.zeros(cube.shape[0], dtype=np.int32)
+        nclusters = np.zeros(max(R, 0), dtype=np.int32)
+        radius2 = np.zeros(max(R, 0), dtype=np.float64)
+        _abi.check(self._lib.rvll_cluster_runs(
+            self._h, _abi.as_dp(cube), run_start.ctypes.data_as(C.POINTER(C.c_int64)), R, _abi.as_dp(scale),
+            _abi.as_ip(wr) if wr is not None else None, int(nboot), seeds.ctypes.data_as(C.POINTER(C.c_uint64)),
+            _abi.as_ip(labels), _abi.as_ip(nclusters), _abi.as_dp(radius2)))
+        return labels, nclusters, radius2
+
+    def cluster(self, cube, scale, wrapped=None, nboot=30, seed=0):
+        """One run of cluster_runs: (labels [N], nclusters, radius2)."""
+        cube = self._theta2d(cube)
+        labels, nclusters, radius2 = self.cluster_runs(cube, [0, cube.shape[0]], np.reshape(scale, (1, -1)), wrapped,
+                                                       nboot, [seed])
+        return labels, int(nclusters[0]), float(radius2[0])
+
     # ---- live set resident on the device (nested.run_nested_slice(..., live=model)) -----------------------------
     def live_init(self, cube):
         """N unit-cube rows -> prior transform -> log-L; the live set stays on the device.  Returns log-L [N]."""

@@ -31,6 +31,7 @@ class NestedResult:
     logl: np.ndarray
     logwt: np.ndarray            # log posterior weights (normalised)
     timing: dict = None          # resident live set: seconds in the order step, waiting for the live step, and the loop turns
+    nclusters: np.ndarray = None  # clustering=True: the clusters of the survivors, one entry per iteration (None when off)
 
 
 def _logaddexp_many(x):
@@ -187,18 +188,58 @@ def _deaths(logz, h, logx, dl, nlive, kbatch):
     return logw, logz, float(a_last - logz), logx
 
 
+def _covariance(ua):
+    d0 = ua - ua.mean(axis=0)
+    return d0.T @ d0 / max(1, len(ua) - 1) + 1e-14 * np.eye(ua.shape[1])
+
+
 def _whitening(ua):
     """Lower-triangular factor of the covariance of the unit-cube rows ua (the surviving live points)."""
-    d0 = ua - ua.mean(axis=0)
-    cov = d0.T @ d0 / max(1, len(ua) - 1) + 1e-14 * np.eye(ua.shape[1])
-    return np.linalg.cholesky(cov)
+    return np.linalg.cholesky(_covariance(ua))
+
+
+# ---- clustering of the survivors (clustering=True; DESIGN §4e) ---------------------------------------------------------
+_M64 = 2 ** 64 - 1
+_BOOT_MUL = 0x9E3779B97F4A7C15          # bootstrap seed of an iteration: seed * _BOOT_MUL + it
+_GROUP_MUL = 0xD1B54A32D192ED03         # walk seed of cluster c > 0: walk_seed + c * _GROUP_MUL
+
+
+def _cluster_scale(ua):
+    """The clustering metric of the survivors ua: 1 / the per-dimension spread of their covariance (as _whitening forms it)."""
+    return 1.0 / np.sqrt(np.diag(_covariance(ua)))
+
+
+def _cluster_factors(ua, labels, ncl, chol):
+    """The whitening factor of every cluster: its own where it has at least 2 ndim rows, the run's global one otherwise."""
+    if ncl <= 1:
+        return [chol]
+    need = 2 * ua.shape[1]
+    return [_whitening(ua[labels == c]) if np.count_nonzero(labels == c) >= need else chol for c in range(ncl)]
+
+
+def _walk_groups(cw, factors, walk_seed):
+    """The walkers grouped by the cluster of their start row (cw), in label order, stable inside a group: (order, sizes,
+    factors, seeds) of the non-empty groups; group c walks with seed walk_seed (c = 0) or walk_seed + c * _GROUP_MUL."""
+    order = np.argsort(cw, kind="stable")
+    counts = np.bincount(cw, minlength=len(factors))
+    groups = np.flatnonzero(counts)
+    return (order, counts[groups], [factors[c] for c in groups],
+            [walk_seed if c == 0 else (walk_seed + int(c) * _GROUP_MUL) & _M64 for c in groups])
+
+
+def _default_clusterer(clusterer):
+    if clusterer is not None:
+        return clusterer
+    from .clustering import cluster_runs
+    return cluster_runs
 
 
 def run_nested_slice(prior: Callable, loglike: Callable, ndim: int, nlive: Optional[int] = None, kbatch: Optional[int] = None,
                      nsteps: Optional[int] = None, dlogz: float = 0.5, max_iter: int = 10_000_000,
                      max_calls: int = 50_000_000, wrapped=None, seed: int = 0,
                      prior_loglike: Optional[Callable] = None, walker: Optional[Callable] = None,
-                     live=None, live_chol: str = "device") -> NestedResult:
+                     live=None, live_chol: str = "device", clustering: bool = False, nboot: int = 30,
+                     clusterer: Optional[Callable] = None, walker_runs: Optional[Callable] = None) -> NestedResult:
     """Nested sampling with `kbatch` deaths per iteration and batched hit-and-run slice sampling.
 
     `prior_loglike(cubes) -> (theta, logl)`, if given, replaces the prior + loglike pair inside the loop
@@ -222,7 +263,24 @@ def run_nested_slice(prior: Callable, loglike: Callable, ndim: int, nlive: Optio
     current position until a proposal is accepted.  Every shrink round evaluates ALL unfinished walkers in
     one vectorized callback call — one prior + log-L launch on the GPU.  Defaults follow the reference's
     UltraNest wrapper (evidence_amd/settings.py: nlive = 25 ndim, nsteps = 3 ndim, dlogz = 0.5;
-    evidence/ultranest/__init__.py:333-338) and :159-163 (wrapped parameters)."""
+    evidence/ultranest/__init__.py:333-338) and :159-163 (wrapped parameters).
+
+    `clustering=True` (the reference's PolyChord do_clustering / UltraNest's MLFriends regions) clusters the survivors of
+    every iteration (MLFriends with `nboot` bootstraps; `clusterer` = clustering.cluster_runs by default, or
+    GpuRVModel.cluster_runs) and whitens every walker's directions with the covariance of the cluster its start row is in.
+    The draws of the run's generator are those of clustering=False, so a run that finds one cluster every iteration is the
+    unclustered run bit for bit.  `walker_runs` (GpuRVModel.slice_walk_runs) then walks the walkers grouped by cluster in
+    one call; `walker` has a single factor and cannot be combined with clustering, nor can the resident live set."""
+    if clustering and walker is not None:
+        raise ValueError("walker= has one whitening factor for all walkers: with clustering=True pass walker_runs= "
+                         "(GpuRVModel.slice_walk_runs)")
+    if clustering and live is not None:
+        raise ValueError("clustering=True does not work with the resident live set (live=)")
+    if walker is not None and walker_runs is not None:
+        raise ValueError("pass walker= or walker_runs=, not both")
+    if clustering:
+        clusterer = _default_clusterer(clusterer)
+    nclusters = [] if clustering else None
     rng = np.random.default_rng(seed)
     defaults = ultranest_defaults(ndim)
     nlive = int(nlive or defaults["nlive"])
@@ -300,7 +358,8 @@ def run_nested_slice(prior: Callable, loglike: Callable, ndim: int, nlive: Optio
         alive = order[kbatch:]
         # whitening from the surviving live points
         chol = _whitening(u[alive]) if u is not None else None
-        start = alive[rng.integers(0, len(alive), kbatch)]
+        pick = rng.integers(0, len(alive), kbatch)
+        start = alive[pick]
         if live is not None:
             # live_chol="host": order and start rows up, the new log-L of the replaced rows down, and the mirror of the rows
             wl, used = live.live_step(order, kbatch, start, lstar, wrapped, nsteps, 200, int(rng.integers(0, 2 ** 62)), chol=chol)
@@ -311,12 +370,30 @@ def run_nested_slice(prior: Callable, loglike: Callable, ndim: int, nlive: Optio
                 break
             continue
         wu, wt, wl = u[start], theta[start], logl[start]
+        factors = [chol]
+        cw = np.zeros(kbatch, dtype=np.intp)
+        if clustering:
+            ua = u[alive]
+            labels, ncl, _ = clusterer(ua, [0, len(ua)], _cluster_scale(ua)[None, :], wrapped, nboot,
+                                       [(int(seed) * _BOOT_MUL + it) & _M64])
+            nclusters.append(int(ncl[0]))
+            factors = _cluster_factors(ua, labels, int(ncl[0]), chol)
+            cw = np.asarray(labels, dtype=np.intp)[pick]
         if walker is not None:
             wu, wt, wl, used = walker(wu, wt, wl, lstar, chol, wrapped, nsteps, 200, int(rng.integers(0, 2 ** 62)))
             ncall += int(used)
-        for _ in range(0 if walker is not None else nsteps):
+        elif walker_runs is not None:
+            wo, sizes, gf, gseeds = _walk_groups(cw, factors, int(rng.integers(0, 2 ** 62)))
+            gu, gt, gl, used = walker_runs(wu[wo], wt[wo], wl[wo], np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64),
+                                           np.full(len(sizes), lstar), np.stack(gf), wrapped, nsteps, 200, gseeds)
+            wu[wo], wt[wo], wl[wo] = gu, gt, gl
+            ncall += int(np.sum(used))
+        many = len(factors) > 1
+        if many:
+            wfac = np.stack(factors)[cw]                        # each walker's factor: that of its start row's cluster
+        for _ in range(0 if (walker is not None or walker_runs is not None) else nsteps):
             z = rng.standard_normal((kbatch, ndim))
-            d = z @ chol.T
+            d = np.einsum("kij,kj->ki", wfac, z) if many else z @ chol.T
             d /= np.linalg.norm(d, axis=1, keepdims=True)
             tmin, tmax = _chord(wu, d, wrapped)
             todo = np.arange(kbatch)
@@ -363,13 +440,14 @@ def run_nested_slice(prior: Callable, loglike: Callable, ndim: int, nlive: Optio
     all_logl = np.concatenate(dead_logl + [logl])
     all_logw = np.concatenate(dead_logw + [logw_live]) - logz_final
     return NestedResult(float(logz_final), float(np.sqrt(max(h, 0.0) / nlive)), it, ncall, float(h),
-                        all_theta, all_logl, all_logw, timing)
+                        all_theta, all_logl, all_logw, timing, None if nclusters is None else np.array(nclusters, dtype=np.int64))
 
 
 class _EnsembleRun:
     """One run of run_nested_ensemble: the state run_nested_slice keeps in its locals."""
 
     def __init__(self, seed, nlive, ndim):
+        self.seed = seed
         self.rng = np.random.default_rng(seed)
         self.u = self.rng.random((nlive, ndim))
         self.theta = self.logl = None
@@ -379,12 +457,14 @@ class _EnsembleRun:
         self.it = 0
         self.done = False
         self.timing = {"host_s": 0.0, "walk_s": 0.0, "turns": 0}
+        self.nclusters = []
 
 
 def run_nested_ensemble(prior: Callable, loglike: Callable, ndim: int, seeds, nlive: Optional[int] = None,
                         kbatch: Optional[int] = None, nsteps: Optional[int] = None, dlogz: float = 0.5,
                         max_iter: int = 10_000_000, max_calls: int = 50_000_000, wrapped=None,
-                        walker_runs: Optional[Callable] = None) -> list:
+                        walker_runs: Optional[Callable] = None, clustering: bool = False, nboot: int = 30,
+                        clusterer: Optional[Callable] = None) -> list:
     """len(seeds) independent runs of run_nested_slice in lockstep, their walks in ONE call per iteration.
 
     The reference's FIP workflow repeats independent runs of every model and takes the median and spread of ln Z over them
@@ -400,12 +480,18 @@ def run_nested_ensemble(prior: Callable, loglike: Callable, ndim: int, seeds, nl
     the walkers of every run that is still going.  A run that meets its own stop (dlogz, max_iter, max_calls) leaves the
     lockstep.  result[r] is run_nested_slice(prior, loglike, ndim, seed=seeds[r], walker=<the same walk for one run>,
     same settings) bit for bit; its `timing` holds the host seconds of its own bookkeeping, the seconds of the shared walk
-    calls it took part in, and their number."""
+    calls it took part in, and their number.
+
+    clustering=True clusters the survivors of every running run in ONE `clusterer` call per iteration and walks the
+    (run, cluster) groups of walkers in one `walker_runs` call; result[r] is then run_nested_slice(..., clustering=True,
+    walker_runs=...) for seed r, bit for bit, and the runs' timing counts the clustering as host time."""
     seeds = [int(s) for s in seeds]
     if not seeds:
         raise ValueError("need at least one seed")
     if walker_runs is None:
         raise ValueError("walker_runs is required (GpuRVModel.slice_walk_runs)")
+    if clustering:
+        clusterer = _default_clusterer(clusterer)
     defaults = ultranest_defaults(ndim)
     nlive = int(nlive or defaults["nlive"])
     kbatch = int(kbatch or max(1, nlive // 4))
@@ -438,24 +524,35 @@ def run_nested_ensemble(prior: Callable, loglike: Callable, ndim: int, seeds, nl
             r.it += kbatch
             alive = order[kbatch:]
             chol = _whitening(r.u[alive])
-            start = alive[r.rng.integers(0, len(alive), kbatch)]
-            turn.append((r, dead, start, lstar, chol, int(r.rng.integers(0, 2 ** 62))))
+            pick = r.rng.integers(0, len(alive), kbatch)
+            start = alive[pick]
+            turn.append((r, dead, start, lstar, chol, int(r.rng.integers(0, 2 ** 62)), alive, pick))
             r.timing["host_s"] += time.perf_counter() - t0
         if not turn:
             break
-        run_start = np.arange(len(turn) + 1, dtype=np.int64) * kbatch
+        if clustering:
+            turn = _cluster_turn(turn, clusterer, wrapped, nboot)
+        else:
+            turn = [t[:6] + (np.arange(kbatch), [kbatch], [t[4]], [t[5]]) for t in turn]
+        # (run, dead rows, start rows, lstar, chol, walk seed, walker order, group sizes, group factors, group seeds)
+        sizes = np.concatenate([t[7] for t in turn])
+        run_start = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
         t0 = time.perf_counter()
-        wu, wt, wl, used = walker_runs(np.concatenate([r.u[st] for r, _, st, *_ in turn]),
-                                       np.concatenate([r.theta[st] for r, _, st, *_ in turn]),
-                                       np.concatenate([r.logl[st] for r, _, st, *_ in turn]),
-                                       run_start, np.array([t[3] for t in turn]), np.stack([t[4] for t in turn]),
-                                       wrapped, nsteps, 200, [t[5] for t in turn])
+        wu, wt, wl, used = walker_runs(np.concatenate([r.u[st[wo]] for r, _, st, _, _, _, wo, *_ in turn]),
+                                       np.concatenate([r.theta[st[wo]] for r, _, st, _, _, _, wo, *_ in turn]),
+                                       np.concatenate([r.logl[st[wo]] for r, _, st, _, _, _, wo, *_ in turn]),
+                                       run_start, np.repeat([t[3] for t in turn], [len(t[7]) for t in turn]),
+                                       np.stack([f for t in turn for f in t[8]]),
+                                       wrapped, nsteps, 200, [s for t in turn for s in t[9]])
         t_walk = time.perf_counter() - t0
-        for j, (r, dead, *_rest) in enumerate(turn):
+        g = 0
+        for j, (r, dead, _st, _ls, _ch, _sd, wo, gsizes, *_rest) in enumerate(turn):
             t0 = time.perf_counter()
             rows = slice(j * kbatch, (j + 1) * kbatch)
-            r.ncall += int(used[j])
-            r.u[dead], r.theta[dead], r.logl[dead] = wu[rows], wt[rows], wl[rows]
+            r.ncall += int(np.sum(used[g:g + len(gsizes)]))
+            g += len(gsizes)
+            back = dead[wo]                                  # the walkers' rows in group order
+            r.u[back], r.theta[back], r.logl[back] = wu[rows], wt[rows], wl[rows]
             if np.max(r.logl) + r.logx < r.logz + stop_gap:
                 r.done = True
             r.timing["walk_s"] += t_walk
@@ -469,5 +566,29 @@ def run_nested_ensemble(prior: Callable, loglike: Callable, ndim: int, seeds, nl
         all_logl = np.concatenate(r.dead_logl + [r.logl])
         all_logw = np.concatenate(r.dead_logw + [logw_live]) - logz_final
         out.append(NestedResult(float(logz_final), float(np.sqrt(max(r.h, 0.0) / nlive)), r.it, r.ncall, float(r.h),
-                                all_theta, all_logl, all_logw, r.timing))
+                                all_theta, all_logl, all_logw, r.timing,
+                                np.array(r.nclusters, dtype=np.int64) if clustering else None))
+    return out
+
+
+def _cluster_turn(turn, clusterer, wrapped, nboot):
+    """run_nested_ensemble(clustering=True): the survivors of every run of the turn clustered in ONE clusterer call, then per
+    run its walkers grouped by cluster as run_nested_slice groups them.  Appends the group order, sizes, factors and seeds
+    to every turn entry."""
+    t0 = time.perf_counter()
+    uas = [r.u[alive] for r, *_x, alive, _pick in turn]
+    run_start = np.concatenate([[0], np.cumsum([len(ua) for ua in uas])]).astype(np.int64)
+    labels, ncl, _ = clusterer(np.concatenate(uas), run_start, np.stack([_cluster_scale(ua) for ua in uas]), wrapped, nboot,
+                               [(r.seed * _BOOT_MUL + r.it) & _M64 for r, *_x in turn])
+    labels = np.asarray(labels, dtype=np.intp)
+    dt = (time.perf_counter() - t0) / len(turn)
+    out = []
+    for j, (r, dead, start, lstar, chol, wseed, alive, pick) in enumerate(turn):
+        t0 = time.perf_counter()
+        lab = labels[run_start[j]:run_start[j + 1]]
+        r.nclusters.append(int(ncl[j]))
+        factors = _cluster_factors(uas[j], lab, int(ncl[j]), chol)
+        wo, sizes, gf, gseeds = _walk_groups(lab[pick], factors, wseed)
+        out.append((r, dead, start, lstar, chol, wseed, wo, sizes, gf, gseeds))
+        r.timing["host_s"] += dt + time.perf_counter() - t0
     return out

@@ -51,8 +51,9 @@ extern "C" {
 #endif
 
 #define RVLL_VERSION_MAJOR 0
-#define RVLL_VERSION_MINOR 3   /* 0.2: rvll_slice_walk takes walker_base; RVLL_FLAG_WANDERED; resident live set
-                                  0.3: rvll_slice_walk_runs */
+#define RVLL_VERSION_MINOR 4   /* 0.2: rvll_slice_walk takes walker_base; RVLL_FLAG_WANDERED; resident live set
+                                  0.3: rvll_slice_walk_runs
+                                  0.4: rvll_cluster_runs */
 
 /* ---- error codes ------------------------------------------------------ */
 #define RVLL_OK             0
@@ -264,6 +265,16 @@ int rvll_slice_walk_runs(rvll_handle* h, double* cube, double* theta, double* lo
                          const double* lstar /*[R]*/, const double* chol /*[R, ndim, ndim]*/, const uint64_t* seed /*[R]*/,
                          const int32_t* wrapped /*[ndim] or NULL*/, int32_t nsteps, int32_t max_rounds,
                          int64_t* ncalls /*[R] out*/);
+/* MLFriends clustering of R independent row sets in one call (definition: DESIGN §4e).  Rows run_start[r] .. run_start[r+1]
+ * of cube belong to run r; scale [R, ndim] is each run's metric (1 / per-dimension spread); wrapped [ndim] may be NULL;
+ * 0 <= nboot <= 32; seeds [R].  Out: labels [run_start[R]] (cluster of each row inside its run, 0-based, by smallest row),
+ * nclusters [R], radius2 [R].  The result does not depend on scheduling: it is bit for bit that of the numpy definition
+ * (evidence_amd/clustering.py).  An empty run gets nclusters 0 and radius2 0.  RVLL_E_INVALID: nboot outside [0, 32],
+ * run_start not rising from 0, a scale that is not finite and positive, a required pointer NULL; RVLL_E_UNSUPPORTED: ndim
+ * above 64.  Needs no priors.                                                                                               */
+int rvll_cluster_runs(rvll_handle* h, const double* cube /*[N, ndim]*/, const int64_t* run_start /*[R + 1]*/, int64_t R,
+                      const double* scale, const int32_t* wrapped, int nboot, const uint64_t* seeds,
+                      int32_t* labels, int32_t* nclusters, double* radius2);
 /* A walker's moves are a chain of dependent evaluations; when walkers of a workgroup have finished, the free slots of
  * its tile evaluate, for the walkers that are left, up to max_ahead candidates of the current move per iteration:
  * candidate r+1 is the one the walker draws if candidate r is rejected (the shrunk bracket is known in advance), and
