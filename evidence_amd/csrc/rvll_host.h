@@ -181,6 +181,18 @@ struct rvll_handle {
     double sorted_lstar = 0.;
     long long dead_n = 0, dead_cap = 0;
     double *d_dead_theta = nullptr, *d_dead_logl = nullptr;
+    // the resident ensemble (rvll_live_runs_*): R live sets of n rows in d_live_u / _theta / _logl (run r = rows r n .. r n + n - 1;
+    // live_n is 0 meanwhile, so the one-run calls refuse them, and rvll_live_init sets runs_R to 0); the dead store holds the dying
+    // rows of every step in one block of A kdead rows, run a's kdead at a kdead, and runs_dead[r] lists run r's pieces in death order
+    long long runs_R = 0, runs_n = 0;
+    int32_t* d_runs_idx = nullptr;              // [runs_idx_cap]: order [R n] | ranks, dying rows, start rows [R n each] | runs, segments [2 R + 1]
+    long long runs_idx_cap = 0;                 // in ints
+    double* d_runs_mom = nullptr;               // [R] x (moments scratch | mean [D] | covariance [D, D])
+    long long runs_mom_cap = 0;                 // in runs
+    std::vector<int32_t> runs_sorted;           // the runs of the rvll_live_runs_sort whose order d_runs_idx holds (empty: none, or used up)
+    long long runs_sorted_kdead = -1;
+    std::vector<double> runs_sorted_lstar;
+    std::vector<std::vector<std::pair<long long, long long>>> runs_dead;   // [R] (first row in the store, rows)
 
     // clustering (rvll_cluster_runs): grow-only device blocks for the packed inputs, the forest and per-run maxima, the packed outputs
     void* d_cl_in = nullptr;

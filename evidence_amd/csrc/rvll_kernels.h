@@ -245,6 +245,20 @@ size_t sort_temp_bytes(long long n);
 hipError_t launch_sort_logl(const double* logl, long long n, unsigned long long* keys_in, unsigned long long* keys_out, int32_t* rows_in,
                             int32_t* order_out, void* temp, size_t temp_bytes, hipStream_t st);
 hipError_t launch_compose_index(const int32_t* order, long long offset, const int32_t* rank, long long n, int32_t* out, hipStream_t st);
+// the resident ensemble (rvll_live_runs_*): R live sets of n rows, run r = rows r n .. r n + n - 1.  The moments of A row sets in
+// one set of launches (set a: idx[a idx_stride ..], each bit for bit its own launch_moments); every listed run's own order by
+// log-L (order[a n + i]: the row of rank i in run runs[a], as launch_sort_logl orders that run alone); the kdead lowest and the
+// highest log-L of every run ([A][kdead + 1]); and the dying rows, start rows and run-mode walk tables of A kdead walkers
+size_t moments_runs_scratch_doubles(int D);
+hipError_t launch_moments_runs(const double* u, const int32_t* idx, long long idx_stride, int A, long long n, int D, double* scratch,
+                               double* mean, double* cov, hipStream_t st);
+size_t runs_sort_temp_bytes(int A, long long n);
+hipError_t launch_runs_sort(const double* logl, const int32_t* runs, int A, long long n, unsigned long long* keys_in,
+                            unsigned long long* keys_out, int32_t* rows_in, int32_t* seg, int32_t* order_out, void* temp,
+                            size_t temp_bytes, hipStream_t st);
+hipError_t launch_runs_sorted_logl(const double* logl, const int32_t* order, int A, long long n, long long kdead, double* out, hipStream_t st);
+hipError_t launch_runs_compose(const int32_t* order, int A, long long n, long long kdead, const int32_t* rank, int32_t* dying,
+                               int32_t* start, int32_t* run, int32_t* wid, hipStream_t st);
 
 // ---- scalar-call server: a one-workgroup persistent kernel that answers single-point log-L requests through a
 // block of host-coherent pinned memory, so a scalar callback costs a PCIe round trip instead of a kernel launch

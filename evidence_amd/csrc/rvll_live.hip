@@ -7,6 +7,7 @@
 // through PCIe (a fifth of the end-to-end time): these kernels keep all of it in HBM.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <algorithm>
 #include <cstring>
 #include <rocprim/rocprim.hpp>
 #include "rvll_kernels.h"
@@ -43,8 +44,11 @@ void scatter_rows_kernel(const double* src, const int32_t* idx, long long n, int
 // of D, group g summing every (kThreads / D)-th of the block's rows, and the groups' sums are added in group order — a
 // fixed order for a given (n, D).  (One thread per column, as first written, left 237 of 256 threads idle: 63 us per call.)
 __global__ __launch_bounds__(kThreads)
-void moments_sum_kernel(const double* u, const int32_t* idx, long long n, int D, double* part /*[kMomBlocks][D]*/)
+void moments_sum_kernel(const double* u, const int32_t* idx, long long n, int D, double* part /*[kMomBlocks][D]*/,
+                        long long idx_stride, long long part_stride)
 {
+    idx += blockIdx.y * idx_stride;                          // run blockIdx.y of a batch (launch_moments_runs); 0 for one run
+    part += blockIdx.y * part_stride;
     __shared__ double acc[kThreads];
     const int groups = D <= kThreads ? kThreads / D : 1;
     const int g = threadIdx.x / D, d = threadIdx.x - g * D;
@@ -73,8 +77,10 @@ void moments_sum_kernel(const double* u, const int32_t* idx, long long n, int D,
 // order — a fixed order for a given width.  (One thread a column walked 128 dependent loads: 9.5 us a call, two calls a step.)
 constexpr int kFoldCols = kThreads / 4;
 __global__ __launch_bounds__(kThreads)
-void moments_fold_kernel(const double* part, int width, double scale, double* out)
+void moments_fold_kernel(const double* part, int width, double scale, double* out, long long part_stride, long long out_stride)
 {
+    part += blockIdx.y * part_stride;
+    out += blockIdx.y * out_stride;
     __shared__ double q[4][kFoldCols];
     const int c = threadIdx.x % kFoldCols, k = threadIdx.x / kFoldCols;
     const int d = blockIdx.x * kFoldCols + c;
@@ -92,8 +98,11 @@ void moments_fold_kernel(const double* part, int width, double scale, double* ou
 constexpr int kCovRows = 32;
 __global__ __launch_bounds__(kThreads)
 void moments_cov_kernel(const double* u, const int32_t* idx, long long n, int D, const double* mean,
-                        double* part /*[kMomBlocks][D*D]*/)
+                        double* part /*[kMomBlocks][D*D]*/, long long idx_stride, long long part_stride)
 {
+    idx += blockIdx.y * idx_stride;
+    mean += (long long)blockIdx.y * D;
+    part += blockIdx.y * part_stride;
     extern __shared__ double rows[];                         // [kCovRows][D], centred
     double* ms = rows + (size_t)kCovRows * D;                // [D]
     for (int d = threadIdx.x; d < D; d += kThreads) ms[d] = mean[d];
@@ -163,6 +172,51 @@ void compose_index_kernel(const int32_t* order, long long offset, const int32_t*
         out[i] = order[offset + rank[i]];
 }
 
+// ---- the resident ensemble (rvll_live_runs_*): R live sets of n rows, run r = rows r n .. r n + n - 1 ----------------------
+// keys of the A listed runs, packed: element a n + i is row runs[a] n + i (its global row goes with it); segment a of the
+// segmented sort is [a n, a n + n), its offsets in seg[0 .. A]
+__global__ __launch_bounds__(kThreads)
+void runs_sort_keys_kernel(const double* logl, const int32_t* runs, int A, long long n, unsigned long long* keys, int32_t* rows,
+                           int32_t* seg)
+{
+    const long long total = (long long)A * n;
+    for (long long e = (long long)blockIdx.x * kThreads + threadIdx.x; e < total || e <= A; e += (long long)gridDim.x * kThreads) {
+        if (e <= A) seg[e] = (int32_t)(e * n);
+        if (e >= total) continue;
+        const long long a = e / n, g = (long long)runs[a] * n + (e - a * n);
+        const unsigned long long b = (unsigned long long)__double_as_longlong(logl[g]);
+        keys[e] = (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+        rows[e] = (int32_t)g;
+    }
+}
+
+// out[a (kdead + 1) + j] = log-L of run a's rank j (j < kdead), then of its highest (order: [A][n] global rows)
+__global__ __launch_bounds__(kThreads)
+void runs_sorted_logl_kernel(const double* logl, const int32_t* order, int A, long long n, long long kdead, double* out)
+{
+    const long long w = kdead + 1, total = (long long)A * w;
+    for (long long e = (long long)blockIdx.x * kThreads + threadIdx.x; e < total; e += (long long)gridDim.x * kThreads) {
+        const long long a = e / w, j = e - a * w;
+        out[e] = logl[order[a * n + (j < kdead ? j : n - 1)]];
+    }
+}
+
+// walker e = a kdead + i of run a: the row that dies, dying[e] = order[a n + i], the row it starts from, start[e] =
+// order[a n + kdead + rank[e]], and its place in the run-mode walk (run[e] = a, wid[e] = i)
+__global__ __launch_bounds__(kThreads)
+void runs_compose_kernel(const int32_t* order, int A, long long n, long long kdead, const int32_t* rank, int32_t* dying,
+                         int32_t* start, int32_t* run, int32_t* wid)
+{
+    const long long total = (long long)A * kdead;
+    for (long long e = (long long)blockIdx.x * kThreads + threadIdx.x; e < total; e += (long long)gridDim.x * kThreads) {
+        const long long a = e / kdead, i = e - a * kdead;
+        dying[e] = order[a * n + i];
+        start[e] = order[a * n + kdead + rank[e]];
+        run[e] = (int32_t)a;
+        wid[e] = (int32_t)i;
+    }
+}
+
 int blocks_for(long long total)
 {
     long long b = (total + kThreads - 1) / kThreads;
@@ -192,12 +246,34 @@ size_t moments_scratch_doubles(int D) { return (size_t)kMomBlocks * D * D + (siz
 hipError_t launch_moments(const double* u, const int32_t* idx, long long n, int D, double* scratch, double* mean, double* cov,
                           hipStream_t st)
 {
-    if (n <= 0 || D <= 0) return hipErrorInvalidValue;
-    double* part = scratch;
-    hipLaunchKernelGGL(moments_sum_kernel, dim3(kMomBlocks), dim3(kThreads), 0, st, u, idx, n, D, part);
-    hipLaunchKernelGGL(moments_fold_kernel, dim3((D + kFoldCols - 1) / kFoldCols), dim3(kThreads), 0, st, part, D, 1.0 / (double)n, mean);
-    hipLaunchKernelGGL(moments_cov_kernel, dim3(kMomBlocks), dim3(kThreads), sizeof(double) * ((size_t)kCovRows * D + D), st, u, idx, n, D, mean, part);
-    hipLaunchKernelGGL(moments_fold_kernel, dim3((D * D + kFoldCols - 1) / kFoldCols), dim3(kThreads), 0, st, part, D * D, 1.0 / (double)(n > 1 ? n - 1 : 1), cov);
+    return launch_moments_runs(u, idx, 0, 1, n, D, scratch, mean, cov, st);
+}
+
+size_t moments_runs_scratch_doubles(int D) { return (size_t)kMomBlocks * D * D; }
+
+// The moments of A row sets in one set of four launches: set a is the rows idx[a idx_stride .. a idx_stride + n) of u, with
+// scratch [A][moments_runs_scratch_doubles(D)], mean [A][D], cov [A][D*D].  Block (b, a) does what block b of launch_moments
+// does for set a alone — same partition of the same rows, same order of every sum — so each set's mean and covariance are
+// those of its own launch_moments, bit for bit.  (More than 65535 sets: several grids, one after the other.)
+hipError_t launch_moments_runs(const double* u, const int32_t* idx, long long idx_stride, int A, long long n, int D, double* scratch,
+                               double* mean, double* cov, hipStream_t st)
+{
+    if (n <= 0 || D <= 0 || A <= 0) return hipErrorInvalidValue;
+    const long long ps = (long long)moments_runs_scratch_doubles(D);
+    for (int a0 = 0; a0 < A; a0 += 65535) {
+        const int na = std::min(A - a0, 65535);
+        const int32_t* ix = idx + (long long)a0 * idx_stride;
+        double* part = scratch + (long long)a0 * ps;
+        double* m = mean + (long long)a0 * D;
+        double* c = cov + (long long)a0 * D * D;
+        hipLaunchKernelGGL(moments_sum_kernel, dim3(kMomBlocks, na), dim3(kThreads), 0, st, u, ix, n, D, part, idx_stride, ps);
+        hipLaunchKernelGGL(moments_fold_kernel, dim3((D + kFoldCols - 1) / kFoldCols, na), dim3(kThreads), 0, st, part, D, 1.0 / (double)n,
+                           m, ps, (long long)D);
+        hipLaunchKernelGGL(moments_cov_kernel, dim3(kMomBlocks, na), dim3(kThreads), sizeof(double) * ((size_t)kCovRows * D + D), st, u, ix,
+                           n, D, m, part, idx_stride, ps);
+        hipLaunchKernelGGL(moments_fold_kernel, dim3((D * D + kFoldCols - 1) / kFoldCols, na), dim3(kThreads), 0, st, part, D * D,
+                           1.0 / (double)(n > 1 ? n - 1 : 1), c, ps, (long long)D * D);
+    }
     return hipGetLastError();
 }
 
@@ -227,6 +303,48 @@ hipError_t launch_compose_index(const int32_t* order, long long offset, const in
 {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(compose_index_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, st, order, offset, rank, n, out);
+    return hipGetLastError();
+}
+
+// ---- the resident ensemble ----------------------------------------------------------------------------------------------------
+// Every listed run's own stable ascending order of its log-L, as global rows, in one segmented radix sort over the A n packed
+// keys: order_out[a n + i] = the row of rank i in run runs[a] — what launch_sort_logl gives that run alone (a stable order by
+// (key, row) is unique).  keys / rows: A n scratch each (keys twice that), seg: A + 1 ints, runs: A ints on the device.
+size_t runs_sort_temp_bytes(int A, long long n)
+{
+    size_t bytes = 0;
+    unsigned long long* k = nullptr;
+    int32_t* v = nullptr;
+    (void)rocprim::segmented_radix_sort_pairs(nullptr, bytes, k, k, v, v, (unsigned int)(A * n), (unsigned int)A, v, v + 1, 0, 64,
+                                              (hipStream_t) nullptr);
+    return bytes;
+}
+
+hipError_t launch_runs_sort(const double* logl, const int32_t* runs, int A, long long n, unsigned long long* keys_in,
+                            unsigned long long* keys_out, int32_t* rows_in, int32_t* seg, int32_t* order_out, void* temp,
+                            size_t temp_bytes, hipStream_t st)
+{
+    if (A <= 0 || n <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(runs_sort_keys_kernel, dim3(blocks_for((long long)A * n + 1)), dim3(kThreads), 0, st, logl, runs, A, n, keys_in,
+                       rows_in, seg);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return rocprim::segmented_radix_sort_pairs(temp, temp_bytes, keys_in, keys_out, rows_in, order_out, (unsigned int)(A * n),
+                                               (unsigned int)A, seg, seg + 1, 0, 64, st);
+}
+
+hipError_t launch_runs_sorted_logl(const double* logl, const int32_t* order, int A, long long n, long long kdead, double* out, hipStream_t st)
+{
+    hipLaunchKernelGGL(runs_sorted_logl_kernel, dim3(blocks_for((long long)A * (kdead + 1))), dim3(kThreads), 0, st, logl, order, A, n,
+                       kdead, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_runs_compose(const int32_t* order, int A, long long n, long long kdead, const int32_t* rank, int32_t* dying,
+                               int32_t* start, int32_t* run, int32_t* wid, hipStream_t st)
+{
+    hipLaunchKernelGGL(runs_compose_kernel, dim3(blocks_for((long long)A * kdead)), dim3(kThreads), 0, st, order, A, n, kdead, rank,
+                       dying, start, run, wid);
     return hipGetLastError();
 }
 

@@ -65,6 +65,84 @@ int run_calls_add(rvll_handle* h, RunWalk* rw, int64_t n, const int32_t* rows)
     return RVLL_OK;
 }
 
+// the walk's buffers for K rows in run mode, and the tables of R runs (grown on demand)
+int runs_reserve(rvll_handle* h, int64_t K, int64_t R)
+{
+    const size_t D = (size_t)h->L.ndim;
+    int rc = walk_reserve(h, K);
+    if (rc) return rc;
+    hipStream_t st = h->compute;
+    if (K > h->runs_rows_cap) {
+        HIP_TRY(hipStreamSynchronize(st));
+        dev_free(h->d_walk_run);
+        h->runs_rows_cap = 0;
+        HIP_TRY(hipMalloc(&h->d_walk_run, sizeof(int32_t) * (size_t)h->walk_cap));
+        h->runs_rows_cap = h->walk_cap;
+    }
+    if (R > h->runs_cap) {
+        HIP_TRY(hipStreamSynchronize(st));
+        dev_free(h->d_run_lstar); dev_free(h->d_run_seed); dev_free(h->d_run_chol);
+        h->runs_cap = 0;
+        const size_t cap = (size_t)std::max<int64_t>(R, 64);
+        HIP_TRY(hipMalloc(&h->d_run_lstar, sizeof(double) * cap));
+        HIP_TRY(hipMalloc(&h->d_run_seed, sizeof(unsigned long long) * cap));
+        HIP_TRY(hipMalloc(&h->d_run_chol, sizeof(double) * D * D * cap));
+        h->runs_cap = (long long)cap;
+    }
+    return RVLL_OK;
+}
+
+// The whitening factor of the resident live set: the lower Cholesky - Banachiewicz factor of cov + 1e-14 on the diagonal (as
+// evidence_amd/nested.py adds), factor [D, D] zero above the diagonal.  Host arithmetic (19 x 19 at most in practice), shared by
+// rvll_live_step and rvll_live_runs_step so that the two cannot drift apart.  False: not positive definite.
+bool whitening_factor(const double* cov, size_t D, double* factor)
+{
+    std::fill(factor, factor + D * D, 0.);
+    for (size_t j = 0; j < D; ++j) {
+        for (size_t l = 0; l <= j; ++l) {
+            double sum = cov[j * D + l] + (j == l ? 1e-14 : 0.);
+            for (size_t m = 0; m < l; ++m) sum -= factor[j * D + m] * factor[l * D + m];
+            if (j == l) {
+                if (!(sum > 0.)) return false;
+                factor[j * D + j] = std::sqrt(sum);
+            } else {
+                factor[j * D + l] = sum / factor[l * D + l];
+            }
+        }
+    }
+    return true;
+}
+
+// room in the dead store for `add` more rows (grown to at least dead_n + 4 grow rows, the rows kept)
+int dead_reserve(rvll_handle* h, long long add, long long grow, const char* who)
+{
+    if (h->dead_n + add <= h->dead_cap) return RVLL_OK;
+    const size_t D = (size_t)h->L.ndim;
+    hipStream_t st = h->compute;
+    const long long cap = std::max<long long>(2 * h->dead_cap, h->dead_n + 4 * grow);
+    double *nt = nullptr, *nl = nullptr;
+    HIP_TRY(hipMalloc(&nt, sizeof(double) * D * (size_t)cap));
+    {
+        const hipError_t e = hipMalloc(&nl, sizeof(double) * (size_t)cap);
+        if (e != hipSuccess) {
+            (void)hipFree(nt);
+            return report_error(e == hipErrorOutOfMemory ? RVLL_E_NOMEM : RVLL_E_HIP, "%s: dead store: %s", who, hipGetErrorString(e));
+        }
+    }
+    if (h->dead_n) {
+        hipError_t e = hipMemcpyAsync(nt, h->d_dead_theta, sizeof(double) * D * (size_t)h->dead_n, hipMemcpyDeviceToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(nl, h->d_dead_logl, sizeof(double) * (size_t)h->dead_n, hipMemcpyDeviceToDevice, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) {
+            (void)hipFree(nt); (void)hipFree(nl);
+            return report_error(RVLL_E_HIP, "%s: dead store: %s", who, hipGetErrorString(e));
+        }
+    }
+    dev_free(h->d_dead_theta); dev_free(h->d_dead_logl);
+    h->d_dead_theta = nt; h->d_dead_logl = nl; h->dead_cap = cap;
+    return RVLL_OK;
+}
+
 // ---- the walk as rounds of launches (rvll_rounds.h, rvll_kernels.hip) ----------------------------------------------------
 // Which walks take it: RVLL_WALK_ROUNDS = 0 never / 1 whenever the slim prior stage applies.  By default the walks it was
 // measured to win (profiles/r04_rounds_sizes.txt, cfg3, nested sampling end to end, calls/s inside the walk against the
@@ -780,6 +858,41 @@ int walk_upload_frame(rvll_handle* h, const double* chol, const int32_t* wrapped
     return RVLL_OK;
 }
 
+// N unit-cube rows -> prior transform -> log-L into the resident live buffers d_live_u / _theta / _logl (grown on demand);
+// logl_out [N] may be NULL.  Shared by the one-run live set and the ensemble; the caller keeps the state.
+int live_load(rvll_handle* h, const double* cube, int64_t N, double* logl_out)
+{
+    const size_t D = (size_t)std::max(1, h->L.ndim);
+    int rc = rvll_dev_upload_cube(h, cube, N);
+    if (rc) return rc;
+    rc = rvll_dev_prior_loglike(h, N);
+    if (rc) return rc;
+    rc = rvll_dev_sync(h);
+    if (rc) return rc;
+    rc = use_device(h);                                  // (elements the table-only prior stage handed over are redone here)
+    if (rc) return rc;
+    if (N > h->live_cap) {
+        dev_free(h->d_live_u); dev_free(h->d_live_theta); dev_free(h->d_live_logl); dev_free(h->d_live_idx);
+        dev_free(h->d_sort_keys); dev_free(h->d_sort_rows);
+        h->live_cap = 0;
+        HIP_TRY(hipMalloc(&h->d_live_u, sizeof(double) * D * (size_t)N));
+        HIP_TRY(hipMalloc(&h->d_live_theta, sizeof(double) * D * (size_t)N));
+        HIP_TRY(hipMalloc(&h->d_live_logl, sizeof(double) * (size_t)N));
+        HIP_TRY(hipMalloc(&h->d_live_idx, sizeof(int32_t) * 2 * (size_t)N));
+        HIP_TRY(hipMalloc(&h->d_sort_keys, sizeof(unsigned long long) * 2 * (size_t)N));
+        HIP_TRY(hipMalloc(&h->d_sort_rows, sizeof(int32_t) * (size_t)N));
+        h->live_cap = N;
+    }
+    if (!h->d_live_mom) HIP_TRY(hipMalloc(&h->d_live_mom, sizeof(double) * (rvll::moments_scratch_doubles((int)D) + D + D * D)));
+    hipStream_t st = h->compute;
+    HIP_TRY(hipMemcpyAsync(h->d_live_u, h->d_cube, sizeof(double) * D * (size_t)N, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(h->d_live_theta, h->d_theta, sizeof(double) * D * (size_t)N, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(h->d_live_logl, h->d_logL2[h->logl_last], sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice, st));
+    if (logl_out) HIP_TRY(hipMemcpyAsync(logl_out, h->d_live_logl, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return RVLL_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -834,26 +947,9 @@ int rvll_slice_walk_runs(rvll_handle* h, double* cube, double* theta, double* lo
         if (e && atoi(e) >= 1) return report_error(RVLL_E_UNSUPPORTED, "rvll_slice_walk_runs: the rows form (RVLL_WALK_ROWS) has no run mode");
     }
     const size_t D = (size_t)h->L.ndim;
-    rc = walk_reserve(h, K);
+    rc = runs_reserve(h, K, R);
     if (rc) return rc;
     hipStream_t st = h->compute;
-    if (K > h->runs_rows_cap) {
-        HIP_TRY(hipStreamSynchronize(st));
-        dev_free(h->d_walk_run);
-        h->runs_rows_cap = 0;
-        HIP_TRY(hipMalloc(&h->d_walk_run, sizeof(int32_t) * (size_t)h->walk_cap));
-        h->runs_rows_cap = h->walk_cap;
-    }
-    if (R > h->runs_cap) {
-        HIP_TRY(hipStreamSynchronize(st));
-        dev_free(h->d_run_lstar); dev_free(h->d_run_seed); dev_free(h->d_run_chol);
-        h->runs_cap = 0;
-        const size_t cap = (size_t)std::max<int32_t>(R, 64);
-        HIP_TRY(hipMalloc(&h->d_run_lstar, sizeof(double) * cap));
-        HIP_TRY(hipMalloc(&h->d_run_seed, sizeof(unsigned long long) * cap));
-        HIP_TRY(hipMalloc(&h->d_run_chol, sizeof(double) * D * D * cap));
-        h->runs_cap = (long long)cap;
-    }
     std::vector<int32_t> run((size_t)K), rid((size_t)K);
     for (int32_t r = 0; r < R; ++r)
         for (int64_t i = run_start[r]; i < run_start[r + 1]; ++i) { run[(size_t)i] = r; rid[(size_t)i] = (int32_t)(i - run_start[r]); }
@@ -892,34 +988,9 @@ int rvll_live_init(rvll_handle* h, const double* cube, int64_t N, double* logl_o
     h->live_n = 0;
     h->dead_n = 0;
     h->sorted_kdead = -1;
-    const size_t D = (size_t)std::max(1, h->L.ndim);
-    rc = rvll_dev_upload_cube(h, cube, N);
+    h->runs_R = 0;                                       // (and no ensemble's either)
+    rc = live_load(h, cube, N, logl_out);
     if (rc) return rc;
-    rc = rvll_dev_prior_loglike(h, N);
-    if (rc) return rc;
-    rc = rvll_dev_sync(h);
-    if (rc) return rc;
-    rc = use_device(h);                                  // (elements the table-only prior stage handed over are redone here)
-    if (rc) return rc;
-    if (N > h->live_cap) {
-        dev_free(h->d_live_u); dev_free(h->d_live_theta); dev_free(h->d_live_logl); dev_free(h->d_live_idx);
-        dev_free(h->d_sort_keys); dev_free(h->d_sort_rows);
-        h->live_cap = 0;
-        HIP_TRY(hipMalloc(&h->d_live_u, sizeof(double) * D * (size_t)N));
-        HIP_TRY(hipMalloc(&h->d_live_theta, sizeof(double) * D * (size_t)N));
-        HIP_TRY(hipMalloc(&h->d_live_logl, sizeof(double) * (size_t)N));
-        HIP_TRY(hipMalloc(&h->d_live_idx, sizeof(int32_t) * 2 * (size_t)N));
-        HIP_TRY(hipMalloc(&h->d_sort_keys, sizeof(unsigned long long) * 2 * (size_t)N));
-        HIP_TRY(hipMalloc(&h->d_sort_rows, sizeof(int32_t) * (size_t)N));
-        h->live_cap = N;
-    }
-    if (!h->d_live_mom) HIP_TRY(hipMalloc(&h->d_live_mom, sizeof(double) * (rvll::moments_scratch_doubles((int)D) + D + D * D)));
-    hipStream_t st = h->compute;
-    HIP_TRY(hipMemcpyAsync(h->d_live_u, h->d_cube, sizeof(double) * D * (size_t)N, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipMemcpyAsync(h->d_live_theta, h->d_theta, sizeof(double) * D * (size_t)N, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipMemcpyAsync(h->d_live_logl, h->d_logL2[h->logl_last], sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice, st));
-    if (logl_out) HIP_TRY(hipMemcpyAsync(logl_out, h->d_live_logl, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
     h->live_n = N;
     h->dead_n = 0;
     return RVLL_OK;
@@ -976,29 +1047,8 @@ int rvll_live_step(rvll_handle* h, const int32_t* order, int64_t kdead, const in
         HIP_TRY(hipMemcpyAsync(d_start, start, sizeof(int32_t) * (size_t)kdead, hipMemcpyHostToDevice, st));
     }
     // the points that die (rows order[0 .. kdead)) go to the dead store before their rows are overwritten
-    if (h->dead_n + kdead > h->dead_cap) {
-        const long long cap = std::max<long long>(2 * h->dead_cap, h->dead_n + 4 * kdead);
-        double *nt = nullptr, *nl = nullptr;
-        HIP_TRY(hipMalloc(&nt, sizeof(double) * D * (size_t)cap));
-        {
-            const hipError_t e = hipMalloc(&nl, sizeof(double) * (size_t)cap);
-            if (e != hipSuccess) {
-                (void)hipFree(nt);
-                return report_error(e == hipErrorOutOfMemory ? RVLL_E_NOMEM : RVLL_E_HIP, "rvll_live_step: dead store: %s", hipGetErrorString(e));
-            }
-        }
-        if (h->dead_n) {
-            hipError_t e = hipMemcpyAsync(nt, h->d_dead_theta, sizeof(double) * D * (size_t)h->dead_n, hipMemcpyDeviceToDevice, st);
-            if (e == hipSuccess) e = hipMemcpyAsync(nl, h->d_dead_logl, sizeof(double) * (size_t)h->dead_n, hipMemcpyDeviceToDevice, st);
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-            if (e != hipSuccess) {
-                (void)hipFree(nt); (void)hipFree(nl);
-                return report_error(RVLL_E_HIP, "rvll_live_step: dead store: %s", hipGetErrorString(e));
-            }
-        }
-        dev_free(h->d_dead_theta); dev_free(h->d_dead_logl);
-        h->d_dead_theta = nt; h->d_dead_logl = nl; h->dead_cap = cap;
-    }
+    rc = dead_reserve(h, kdead, kdead, "rvll_live_step");
+    if (rc) return rc;
     HIP_TRY(rvll::launch_gather_rows(h->d_live_theta, d_order, kdead, Di, h->d_dead_theta + (size_t)h->dead_n * D, st));
     HIP_TRY(rvll::launch_gather_rows(h->d_live_logl, d_order, kdead, 1, h->d_dead_logl + h->dead_n, st));
     // (dead_n moves on when the step has succeeded, at the bottom: a step that fails below — a covariance that is not positive
@@ -1016,18 +1066,8 @@ int rvll_live_step(rvll_handle* h, const int32_t* order, int64_t kdead, const in
         std::vector<double> cov(D * D);
         HIP_TRY(hipMemcpyAsync(cov.data(), d_cov, sizeof(double) * D * D, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
-        for (size_t j = 0; j < D; ++j) {                 // Cholesky - Banachiewicz, lower triangle
-            for (size_t l = 0; l <= j; ++l) {
-                double sum = cov[j * D + l] + (j == l ? 1e-14 : 0.);
-                for (size_t m = 0; m < l; ++m) sum -= factor[j * D + m] * factor[l * D + m];
-                if (j == l) {
-                    if (!(sum > 0.)) return report_error(RVLL_E_INVALID, "rvll_live_step: the live points' covariance is not positive definite");
-                    factor[j * D + j] = std::sqrt(sum);
-                } else {
-                    factor[j * D + l] = sum / factor[l * D + l];
-                }
-            }
-        }
+        if (!whitening_factor(cov.data(), D, factor.data()))
+            return report_error(RVLL_E_INVALID, "rvll_live_step: the live points' covariance is not positive definite");
     }
     if (chol_out) memcpy(chol_out, factor.data(), sizeof(double) * D * D);
     // the walkers start from rows start[0 .. kdead)
@@ -1106,6 +1146,7 @@ int rvll_live_dead(rvll_handle* h, int64_t* n_dead, double* theta, double* logl)
     int rc = use_device(h);
     if (rc) return rc;
     if (!n_dead) return report_error(RVLL_E_INVALID, "n_dead is null");
+    if (h->runs_R > 0) return report_error(RVLL_E_INVALID, "rvll_live_dead: the resident rows are an ensemble's (rvll_live_runs_dead)");
     const int64_t have = h->dead_n, want = (theta || logl) ? std::min<int64_t>(*n_dead, have) : 0;
     *n_dead = have;
     const size_t D = (size_t)h->L.ndim;
@@ -1118,6 +1159,238 @@ int rvll_live_dead(rvll_handle* h, int64_t* n_dead, double* theta, double* logl)
     }
     if (want > 0 && logl) HIP_TRY(hipMemcpyAsync(logl, h->d_dead_logl, sizeof(double) * (size_t)want, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
+    return RVLL_OK;
+}
+
+// ---- the resident ensemble: R independent live sets in one handle (rvll_live_runs_*) ----------------------------------------
+int rvll_live_runs_init(rvll_handle* h, const double* cube, int32_t R, int64_t n, double* logl_out)
+{
+    int rc = use_device(h);
+    if (rc) return rc;
+    if (!h->have_priors) return report_error(RVLL_E_NOPRIORS, "rvll_set_priors has not been called");
+    if (R < 1 || n < 2 || (int64_t)R * n >= (1LL << 31) || !cube) return report_error(RVLL_E_INVALID, "rvll_live_runs_init: bad arguments");
+    // a new ensemble starts here: no earlier live set — one run's or an ensemble's — is left looking valid, whatever fails below
+    h->live_n = 0;
+    h->dead_n = 0;
+    h->sorted_kdead = -1;
+    h->runs_R = 0;
+    h->runs_sorted.clear();
+    h->runs_sorted_kdead = -1;
+    const int64_t N = (int64_t)R * n;
+    rc = live_load(h, cube, N, logl_out);
+    if (rc) return rc;
+    const int Di = h->L.ndim;
+    const size_t D = (size_t)Di;
+    const long long idx_need = 4 * N + 2 * (long long)R + 1;
+    if (idx_need > h->runs_idx_cap) {
+        dev_free(h->d_runs_idx);
+        h->runs_idx_cap = 0;
+        HIP_TRY(hipMalloc(&h->d_runs_idx, sizeof(int32_t) * (size_t)idx_need));
+        h->runs_idx_cap = idx_need;
+    }
+    if (R > h->runs_mom_cap) {
+        dev_free(h->d_runs_mom);
+        h->runs_mom_cap = 0;
+        HIP_TRY(hipMalloc(&h->d_runs_mom, sizeof(double) * (rvll::moments_runs_scratch_doubles(Di) + D + D * D) * (size_t)R));
+        h->runs_mom_cap = R;
+    }
+    h->runs_dead.assign((size_t)R, {});
+    h->runs_n = n;
+    h->runs_R = R;
+    return RVLL_OK;
+}
+
+namespace {
+// the listed runs of a rvll_live_runs_sort / _step: distinct, ascending, below R
+int runs_check(rvll_handle* h, const int32_t* runs, int32_t A, int64_t kdead, const char* who)
+{
+    if (h->runs_R < 1) return report_error(RVLL_E_INVALID, "%s: rvll_live_runs_init has not been called", who);
+    if (!runs || A < 1 || A > h->runs_R) return report_error(RVLL_E_INVALID, "%s: bad run list", who);
+    if (kdead < 1 || kdead >= h->runs_n) return report_error(RVLL_E_INVALID, "%s: kdead must be in [1, n)", who);
+    for (int32_t a = 0; a < A; ++a)
+        if (runs[a] < 0 || runs[a] >= h->runs_R || (a > 0 && runs[a] <= runs[a - 1]))
+            return report_error(RVLL_E_INVALID, "%s: runs must be distinct, ascending and below R (runs[%d] = %d)", who, (int)a, (int)runs[a]);
+    return RVLL_OK;
+}
+}  // namespace
+
+int rvll_live_runs_sort(rvll_handle* h, const int32_t* runs, int32_t A, int64_t kdead, double* dead_logl, double* lstar,
+                        double* max_logl)
+{
+    int rc = use_device(h);
+    if (rc) return rc;
+    rc = runs_check(h, runs, A, kdead, "rvll_live_runs_sort");
+    if (rc) return rc;
+    if (!dead_logl || !lstar || !max_logl) return report_error(RVLL_E_INVALID, "rvll_live_runs_sort: bad arguments");
+    h->runs_sorted.clear();
+    h->runs_sorted_kdead = -1;
+    const long long n = h->runs_n, R = h->runs_R;
+    hipStream_t st = h->compute;
+    const size_t need = rvll::runs_sort_temp_bytes(A, n);
+    if (need > h->sort_temp_bytes) {
+        HIP_TRY(hipStreamSynchronize(st));
+        dev_free(h->d_sort_temp);
+        h->sort_temp_bytes = 0;
+        HIP_TRY(hipMalloc(&h->d_sort_temp, need));
+        h->sort_temp_bytes = need;
+    }
+    int32_t* d_order = h->d_runs_idx;                    // [A n]: the listed runs' orders, packed
+    int32_t* d_runs = h->d_runs_idx + 4 * R * n;         // [A], then the segments [A + 1]
+    int32_t* d_seg = d_runs + R;
+    rc = walk_reserve(h, (int64_t)A * (kdead + 1));      // (the walk's log-L scratch takes the rows that come down)
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(d_runs, runs, sizeof(int32_t) * (size_t)A, hipMemcpyHostToDevice, st));
+    HIP_TRY(rvll::launch_runs_sort(h->d_live_logl, d_runs, A, n, h->d_sort_keys, h->d_sort_keys + h->live_cap, h->d_sort_rows, d_seg,
+                                   d_order, h->d_sort_temp, h->sort_temp_bytes, st));
+    HIP_TRY(rvll::launch_runs_sorted_logl(h->d_live_logl, d_order, A, n, kdead, h->d_walk_logl, st));
+    std::vector<double> got((size_t)A * (size_t)(kdead + 1));
+    HIP_TRY(hipMemcpyAsync(got.data(), h->d_walk_logl, sizeof(double) * got.size(), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    std::vector<double> ls((size_t)A);
+    for (int32_t a = 0; a < A; ++a) {
+        const double* g = got.data() + (size_t)a * (size_t)(kdead + 1);
+        memcpy(dead_logl + (size_t)a * (size_t)kdead, g, sizeof(double) * (size_t)kdead);
+        ls[(size_t)a] = lstar[a] = g[kdead - 1];
+        max_logl[a] = g[kdead];
+    }
+    h->runs_sorted.assign(runs, runs + A);
+    h->runs_sorted_kdead = kdead;
+    h->runs_sorted_lstar = ls;
+    return RVLL_OK;
+}
+
+int rvll_live_runs_step(rvll_handle* h, const int32_t* runs, int32_t A, int64_t kdead, const int32_t* ranks, const double* lstar,
+                        const int32_t* wrapped, int32_t nsteps, int32_t max_rounds, const uint64_t* seeds, int64_t* ncalls,
+                        double* logl_new, double* chol_out)
+{
+    int rc = use_device(h);
+    if (rc) return rc;
+    if (ncalls && A > 0) for (int32_t a = 0; a < A; ++a) ncalls[a] = 0;
+    rc = runs_check(h, runs, A, kdead, "rvll_live_runs_step");
+    if (rc) return rc;
+    if (!ranks || !lstar || !seeds || !logl_new) return report_error(RVLL_E_INVALID, "rvll_live_runs_step: bad arguments");
+    const long long n = h->runs_n, R = h->runs_R;
+    const int64_t K = (int64_t)A * kdead;
+    rc = walk_check_args(h, K, nsteps, max_rounds, 0);
+    if (rc) return rc;
+    if (h->runs_sorted_kdead != kdead || h->runs_sorted.size() != (size_t)A || !std::equal(runs, runs + A, h->runs_sorted.begin()))
+        return report_error(RVLL_E_INVALID, "rvll_live_runs_step: no rvll_live_runs_sort of these runs with kdead = %lld precedes", (long long)kdead);
+    for (int32_t a = 0; a < A; ++a)
+        if (!(lstar[a] == h->runs_sorted_lstar[(size_t)a]))
+            return report_error(RVLL_E_INVALID, "rvll_live_runs_step: lstar[%d] is not the one rvll_live_runs_sort returned", (int)a);
+    for (int64_t i = 0; i < K; ++i)
+        if (ranks[i] < 0 || ranks[i] >= n - kdead)
+            return report_error(RVLL_E_INVALID, "rvll_live_runs_step: ranks[%lld] is not a rank among the survivors", (long long)i);
+    h->runs_sorted.clear();                              // (used up, whatever happens below: the step changes the rows)
+    h->runs_sorted_kdead = -1;
+    const int Di = h->L.ndim;
+    const size_t D = (size_t)Di;
+    if (h->dead_n + K >= (1LL << 31)) return report_error(RVLL_E_NOMEM, "rvll_live_runs_step: the dead store is full (2^31 rows)");
+    rc = runs_reserve(h, K, A);
+    if (rc) return rc;
+    rc = dead_reserve(h, K, K, "rvll_live_runs_step");
+    if (rc) return rc;
+    hipStream_t st = h->compute;
+    int32_t* d_order = h->d_runs_idx;                    // [A n] from the sort
+    int32_t* d_rank = d_order + R * n;                   // [A kdead] each
+    int32_t* d_dying = d_rank + R * n;
+    int32_t* d_start = d_dying + R * n;
+    HIP_TRY(hipMemcpyAsync(d_rank, ranks, sizeof(int32_t) * (size_t)K, hipMemcpyHostToDevice, st));
+    HIP_TRY(rvll::launch_runs_compose(d_order, A, n, kdead, d_rank, d_dying, d_start, h->d_walk_run, h->d_walk_wid, st));
+    // the dying rows, run a's at a kdead of this step's block, go to the dead store before their rows are overwritten (dead_n
+    // and the runs' pieces move on only when the step has succeeded, at the bottom: a failed step leaves every run as it was)
+    HIP_TRY(rvll::launch_gather_rows(h->d_live_theta, d_dying, K, Di, h->d_dead_theta + (size_t)h->dead_n * D, st));
+    HIP_TRY(rvll::launch_gather_rows(h->d_live_logl, d_dying, K, 1, h->d_dead_logl + h->dead_n, st));
+    // whitening: every run's survivors (ranks kdead .. n) in one set of moments launches, A covariances down in one copy
+    double* d_part = h->d_runs_mom;
+    double* d_mean = d_part + rvll::moments_runs_scratch_doubles(Di) * (size_t)A;
+    double* d_cov = d_mean + D * (size_t)A;
+    HIP_TRY(rvll::launch_moments_runs(h->d_live_u, d_order + kdead, n, A, n - kdead, Di, d_part, d_mean, d_cov, st));
+    std::vector<double> cov(D * D * (size_t)A), factor(D * D * (size_t)A);
+    HIP_TRY(hipMemcpyAsync(cov.data(), d_cov, sizeof(double) * cov.size(), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int32_t a = 0; a < A; ++a)
+        if (!whitening_factor(cov.data() + D * D * (size_t)a, D, factor.data() + D * D * (size_t)a))
+            return report_error(RVLL_E_INVALID, "rvll_live_runs_step: the live points' covariance of run %d is not positive definite", (int)runs[a]);
+    if (chol_out) memcpy(chol_out, factor.data(), sizeof(double) * factor.size());
+    // the walkers (walker i of listed run a is row a kdead + i of the walk) start from their rows ...
+    HIP_TRY(rvll::launch_gather_rows(h->d_live_u, d_start, K, Di, h->d_walk_u, st));
+    HIP_TRY(rvll::launch_gather_rows(h->d_live_theta, d_start, K, Di, h->d_walk_theta, st));
+    HIP_TRY(rvll::launch_gather_rows(h->d_live_logl, d_start, K, 1, h->d_walk_logl, st));
+    HIP_TRY(hipMemcpyAsync(h->d_run_lstar, lstar, sizeof(double) * (size_t)A, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(h->d_run_seed, seeds, sizeof(uint64_t) * (size_t)A, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(h->d_run_chol, factor.data(), sizeof(double) * factor.size(), hipMemcpyHostToDevice, st));
+    rc = walk_upload_frame(h, nullptr, wrapped);         // (synchronises: `factor` may go out of scope after it)
+    if (rc) return rc;
+    std::vector<int32_t> run((size_t)K), rid((size_t)K);
+    for (int64_t e = 0; e < K; ++e) { run[(size_t)e] = (int32_t)(e / kdead); rid[(size_t)e] = (int32_t)(e % kdead); }
+    RunWalk rw{run.data(), rid.data(), std::vector<long long>((size_t)K, 0)};
+    rc = walk_core(h, K, 0., nsteps, max_rounds, 0, 0, nullptr, &rw);
+    if (rc) return rc;
+    // ... and their end points replace the dying rows
+    HIP_TRY(rvll::launch_scatter_rows(h->d_walk_u, d_dying, K, Di, h->d_live_u, st));
+    HIP_TRY(rvll::launch_scatter_rows(h->d_walk_theta, d_dying, K, Di, h->d_live_theta, st));
+    HIP_TRY(rvll::launch_scatter_rows(h->d_walk_logl, d_dying, K, 1, h->d_live_logl, st));
+    HIP_TRY(hipMemcpyAsync(logl_new, h->d_walk_logl, sizeof(double) * (size_t)K, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (ncalls)
+        for (int64_t e = 0; e < K; ++e) ncalls[e / kdead] += rw.row_calls[(size_t)e];
+    for (int32_t a = 0; a < A; ++a) h->runs_dead[(size_t)runs[a]].emplace_back(h->dead_n + (long long)a * kdead, (long long)kdead);
+    h->dead_n += K;
+    return RVLL_OK;
+}
+
+int rvll_live_runs_get(rvll_handle* h, int32_t run, double* cube, double* theta, double* logl)
+{
+    int rc = use_device(h);
+    if (rc) return rc;
+    if (h->runs_R < 1) return report_error(RVLL_E_INVALID, "rvll_live_runs_init has not been called");
+    if (run < 0 || run >= h->runs_R) return report_error(RVLL_E_INVALID, "rvll_live_runs_get: run %d out of range", (int)run);
+    const size_t D = (size_t)h->L.ndim, n = (size_t)h->runs_n, r0 = (size_t)run * n;
+    hipStream_t st = h->compute;
+    if (cube) HIP_TRY(hipMemcpyAsync(cube, h->d_live_u + r0 * D, sizeof(double) * D * n, hipMemcpyDeviceToHost, st));
+    if (theta) HIP_TRY(hipMemcpyAsync(theta, h->d_live_theta + r0 * D, sizeof(double) * D * n, hipMemcpyDeviceToHost, st));
+    if (logl) HIP_TRY(hipMemcpyAsync(logl, h->d_live_logl + r0, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return RVLL_OK;
+}
+
+int rvll_live_runs_dead(rvll_handle* h, int32_t run, int64_t* n_dead, double* theta, double* logl)
+{
+    int rc = use_device(h);
+    if (rc) return rc;
+    if (!n_dead) return report_error(RVLL_E_INVALID, "n_dead is null");
+    if (h->runs_R < 1) return report_error(RVLL_E_INVALID, "rvll_live_runs_init has not been called");
+    if (run < 0 || run >= h->runs_R) return report_error(RVLL_E_INVALID, "rvll_live_runs_dead: run %d out of range", (int)run);
+    const auto& pieces = h->runs_dead[(size_t)run];
+    int64_t have = 0;
+    for (const auto& p : pieces) have += p.second;
+    const int64_t want = (theta || logl) ? std::min<int64_t>(*n_dead, have) : 0;
+    *n_dead = have;
+    if (want <= 0) return RVLL_OK;
+    // the run's rows of the store in death order, gathered through the walk's buffers a chunk at a time, one download per array
+    std::vector<int32_t> rows;
+    rows.reserve((size_t)want);
+    for (const auto& p : pieces)
+        for (long long i = 0; i < p.second && (int64_t)rows.size() < want; ++i) rows.push_back((int32_t)(p.first + i));
+    rc = walk_reserve(h, 1);
+    if (rc) return rc;
+    const int Di = h->L.ndim;
+    const size_t D = (size_t)Di;
+    hipStream_t st = h->compute;
+    for (int64_t lo = 0; lo < want; lo += h->walk_cap) {
+        const int64_t m = std::min<int64_t>(h->walk_cap, want - lo);
+        HIP_TRY(hipMemcpyAsync(h->d_walk_order, rows.data() + lo, sizeof(int32_t) * (size_t)m, hipMemcpyHostToDevice, st));
+        if (theta) {
+            HIP_TRY(rvll::launch_gather_rows(h->d_dead_theta, h->d_walk_order, m, Di, h->d_walk_theta, st));
+            HIP_TRY(hipMemcpyAsync(theta + (size_t)lo * D, h->d_walk_theta, sizeof(double) * D * (size_t)m, hipMemcpyDeviceToHost, st));
+        }
+        if (logl) {
+            HIP_TRY(rvll::launch_gather_rows(h->d_dead_logl, h->d_walk_order, m, 1, h->d_walk_logl, st));
+            HIP_TRY(hipMemcpyAsync(logl + lo, h->d_walk_logl, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, st));
+        }
+        HIP_TRY(hipStreamSynchronize(st));
+    }
     return RVLL_OK;
 }
 

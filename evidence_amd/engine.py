@@ -131,6 +131,7 @@ class GpuRVModel:
         self._s_out_p, self._s_flag_p = _abi.as_dp(self._s_out), _abi.as_ip(self._s_flag)
         self.priordict = None
         self._live_n = 0                       # rows of the resident live set (live_init)
+        self._runs = None                      # (R, n) of the resident ensemble (live_runs_init)
         if priordict is not None:
             self.set_priors(priordict)
 
@@ -389,6 +390,7 @@ class GpuRVModel:
         """N unit-cube rows -> prior transform -> log-L; the live set stays on the device.  Returns log-L [N]."""
         cube = self._theta2d(cube)
         logl = np.empty(cube.shape[0], dtype=np.float64)
+        self._runs = None
         _abi.check(self._lib.rvll_live_init(self._h, _abi.as_dp(cube), cube.shape[0], _abi.as_dp(logl)))
         self._live_n = cube.shape[0]
         return logl
@@ -460,6 +462,98 @@ class GpuRVModel:
         if n:
             cnt = C.c_int64(n)
             _abi.check(self._lib.rvll_live_dead(self._h, C.byref(cnt), _abi.as_dp(th), _abi.as_dp(ll)))
+        return th, ll
+
+    # ---- the resident ensemble: R live sets in one handle (nested.run_nested_ensemble(..., live=model)) -----------------
+    def live_runs_init(self, cube, nruns):
+        """R = nruns independent live sets of n rows each (cube [R n, ndim]; run r = rows r n .. r n + n - 1) -> prior
+        transform -> log-L, resident on the device (rvll_live_runs_init).  Replaces any resident live set.  Returns log-L [R, n]."""
+        cube = np.ascontiguousarray(self._theta2d(cube), dtype=np.float64)
+        nruns = int(nruns)
+        if nruns < 1 or cube.shape[0] % nruns:
+            raise ValueError("cube must hold nruns live sets of equally many rows")
+        n = cube.shape[0] // nruns
+        logl = np.empty((nruns, n), dtype=np.float64)
+        self._live_n = 0
+        _abi.check(self._lib.rvll_live_runs_init(self._h, _abi.as_dp(cube), nruns, n, _abi.as_dp(logl)))
+        self._runs = (nruns, n)
+        return logl
+
+    def _runs_list(self, runs):
+        if getattr(self, "_runs", None) is None:
+            raise RuntimeError("live_runs_init has not been called")
+        runs = np.ascontiguousarray(runs, dtype=np.int32).reshape(-1)
+        if runs.size < 1:
+            raise ValueError("need at least one run")
+        return runs
+
+    def live_runs_sort(self, runs, kdead):
+        """Sort every listed run's live points by log-L ON THE DEVICE (rvll_live_runs_sort): returns (log-L of each run's kdead
+        lowest in ascending order [A, kdead], lstar [A], the highest log-L [A])."""
+        runs = self._runs_list(runs)
+        kdead = int(kdead)
+        dead = np.empty((runs.size, kdead), dtype=np.float64)
+        lstar, top = np.empty(runs.size), np.empty(runs.size)
+        _abi.check(self._lib.rvll_live_runs_sort(self._h, _abi.as_ip(runs), runs.size, kdead, _abi.as_dp(dead), _abi.as_dp(lstar),
+                                                 _abi.as_dp(top)))
+        return dead, lstar, top
+
+    def live_runs_step(self, runs, kdead, ranks, lstar, wrapped=None, nsteps=10, max_rounds=200, seeds=(), return_chol=False):
+        """One iteration of every listed run on the resident ensemble (rvll_live_runs_step), after live_runs_sort of the same
+        runs: ranks [A, kdead] among each run's survivors, lstar [A] as live_runs_sort returned them, seeds [A].  Returns
+        (logl_new [A, kdead], ncalls [A]) (+ the whitening factors [A, ndim, ndim] with return_chol); run a's part is bit for
+        bit what live_step(None, kdead, ranks[a], lstar[a], ..., seeds[a]) gives a model that holds only that run."""
+        runs = self._runs_list(runs)
+        kdead = int(kdead)
+        A = runs.size
+        ranks = np.ascontiguousarray(ranks, dtype=np.int32)
+        lstar = np.ascontiguousarray(lstar, dtype=np.float64).reshape(-1)
+        seeds = np.array([int(s) & (2 ** 64 - 1) for s in seeds], dtype=np.uint64)
+        if ranks.shape != (A, kdead):
+            raise ValueError("ranks must be [runs, kdead]")
+        if lstar.shape != (A,) or seeds.shape != (A,):
+            raise ValueError("lstar and seeds need one entry per run")
+        wr = None if wrapped is None else np.ascontiguousarray(np.asarray(wrapped, dtype=bool).astype(np.int32))
+        logl_new = np.empty((A, kdead), dtype=np.float64)
+        ncalls = np.zeros(A, dtype=np.int64)
+        used = np.empty((A, self.ndim, self.ndim)) if return_chol else None
+        _abi.check(self._lib.rvll_live_runs_step(
+            self._h, _abi.as_ip(runs), A, kdead, _abi.as_ip(ranks), _abi.as_dp(lstar), _abi.as_ip(wr) if wr is not None else None,
+            int(nsteps), int(max_rounds), seeds.ctypes.data_as(C.POINTER(C.c_uint64)), ncalls.ctypes.data_as(C.POINTER(C.c_int64)),
+            _abi.as_dp(logl_new), _abi.as_dp(used) if used is not None else None))
+        return (logl_new, ncalls, used) if return_chol else (logl_new, ncalls)
+
+    def live_runs_get(self, run, cube=True, theta=True, logl=True, theta_out=None):
+        """(cube, theta, logl) of run `run`'s live set as it stands (None for the ones switched off); theta_out: a C-contiguous
+        [n, ndim] float64 array (or view) to receive theta in place."""
+        self._runs_list([run])
+        n = self._runs[1]
+        u = np.empty((n, self.ndim)) if cube else None
+        th = (theta_out if theta_out is not None else np.empty((n, self.ndim))) if theta else None
+        ll = np.empty(n) if logl else None
+        if th is not None and (th.shape != (n, self.ndim) or th.dtype != np.float64 or not th.flags.c_contiguous):
+            raise ValueError("theta_out must be a C-contiguous float64 array of shape (n, ndim)")
+        _abi.check(self._lib.rvll_live_runs_get(self._h, int(run), _abi.as_dp(u) if cube else None,
+                                                _abi.as_dp(th) if theta else None, _abi.as_dp(ll) if logl else None))
+        return u, th, ll
+
+    def live_runs_dead_count(self, run):
+        self._runs_list([run])
+        n = C.c_int64(0)
+        _abi.check(self._lib.rvll_live_runs_dead(self._h, int(run), C.byref(n), None, None))
+        return int(n.value)
+
+    def live_runs_dead(self, run, theta_out=None):
+        """(theta, logl) of every point of run `run` that died so far, in the order they died; theta_out: a C-contiguous
+        [n_dead, ndim] float64 array (or view) to receive theta in place."""
+        n = self.live_runs_dead_count(run)
+        th = theta_out if theta_out is not None else np.empty((n, self.ndim))
+        if th.shape != (n, self.ndim) or th.dtype != np.float64 or not th.flags.c_contiguous:
+            raise ValueError("theta_out must be a C-contiguous float64 array of shape (n_dead, ndim)")
+        ll = np.empty(n)
+        if n:
+            cnt = C.c_int64(n)
+            _abi.check(self._lib.rvll_live_runs_dead(self._h, int(run), C.byref(cnt), _abi.as_dp(th), _abi.as_dp(ll)))
         return th, ll
 
     def scalar_server(self, enable=True):

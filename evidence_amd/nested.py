@@ -188,6 +188,26 @@ def _deaths(logz, h, logx, dl, nlive, kbatch):
     return logw, logz, float(a_last - logz), logx
 
 
+def _deaths_runs(logz, h, logx, dl, nlive, kbatch):
+    """_deaths for A runs at once — the resident ensemble, whose running runs are all at the same iteration and so share logx
+    and the shell widths: logz, h [A], dl [A, kbatch] (each row ascending).  Row a gives the bits _deaths gives for
+    (logz[a], h[a], logx, dl[a]): the same elementwise operations in the same order, and row reductions (logaddexp.accumulate,
+    sum along the last axis) that follow the 1-D order (tests/test_nested_resident_ensemble_host.py checks it bitwise).
+    Returns (logw [A, kbatch], logz [A], h [A], logx)."""
+    logx_seq = logx - np.cumsum(1.0 / (nlive - np.arange(kbatch)))
+    logx_prev = np.concatenate([[logx], logx_seq[:-1]])
+    logw = logx_prev + np.log1p(-np.exp(logx_seq - logx_prev)) + dl
+    logz_seq = np.logaddexp.accumulate(np.concatenate([logz[:, None], logw], axis=1), axis=1)[:, 1:]
+    fin = np.isfinite(logz)
+    top = np.max(logw, axis=1)
+    big = np.where(fin & ~(top > logz), logz, top)                 # max(logz, top) as Python's max picks it; top alone at -inf
+    with np.errstate(invalid="ignore"):
+        a_prev = np.where(fin, np.exp(logz - big) * (h + logz), 0.0)
+    logz_new = logz_seq[:, -1].copy()
+    a_last = np.exp(big - logz_new) * (a_prev + np.sum(np.exp(logw - big[:, None]) * dl, axis=1))
+    return logw, logz_new, a_last - logz_new, float(logx_seq[-1])
+
+
 def _covariance(ua):
     d0 = ua - ua.mean(axis=0)
     return d0.T @ d0 / max(1, len(ua) - 1) + 1e-14 * np.eye(ua.shape[1])
@@ -464,7 +484,7 @@ def run_nested_ensemble(prior: Callable, loglike: Callable, ndim: int, seeds, nl
                         kbatch: Optional[int] = None, nsteps: Optional[int] = None, dlogz: float = 0.5,
                         max_iter: int = 10_000_000, max_calls: int = 50_000_000, wrapped=None,
                         walker_runs: Optional[Callable] = None, clustering: bool = False, nboot: int = 30,
-                        clusterer: Optional[Callable] = None) -> list:
+                        clusterer: Optional[Callable] = None, live=None) -> list:
     """len(seeds) independent runs of run_nested_slice in lockstep, their walks in ONE call per iteration.
 
     The reference's FIP workflow repeats independent runs of every model and takes the median and spread of ln Z over them
@@ -484,10 +504,23 @@ def run_nested_ensemble(prior: Callable, loglike: Callable, ndim: int, seeds, nl
 
     clustering=True clusters the survivors of every running run in ONE `clusterer` call per iteration and walks the
     (run, cluster) groups of walkers in one `walker_runs` call; result[r] is then run_nested_slice(..., clustering=True,
-    walker_runs=...) for seed r, bit for bit, and the runs' timing counts the clustering as host time."""
+    walker_runs=...) for seed r, bit for bit, and the runs' timing counts the clustering as host time.
+
+    `live` (a GpuRVModel) keeps the live sets of ALL runs resident on the device (GpuRVModel.live_runs_*: rvll_live_runs_*,
+    DESIGN §4d): per iteration one call sorts every running run and one call whitens and walks them all; `prior`, `loglike`
+    and `walker_runs` are unused and may be None.  result[r] is then run_nested_slice(None, None, ndim, seed=seeds[r],
+    live=<a model of that run alone>, same settings) bit for bit, and its timing holds its share of the host seconds of each
+    turn (sort, draws, evidence sums), the seconds of the shared step calls it took part in, and their number.  Not with
+    clustering=True nor walker_runs."""
     seeds = [int(s) for s in seeds]
     if not seeds:
         raise ValueError("need at least one seed")
+    if live is not None:
+        if clustering:
+            raise ValueError("clustering=True does not work with the resident live sets (live=)")
+        if walker_runs is not None:
+            raise ValueError("pass walker_runs= or live=, not both")
+        return _ensemble_resident(live, ndim, seeds, nlive, kbatch, nsteps, dlogz, max_iter, max_calls, wrapped)
     if walker_runs is None:
         raise ValueError("walker_runs is required (GpuRVModel.slice_walk_runs)")
     if clustering:
@@ -591,4 +624,73 @@ def _cluster_turn(turn, clusterer, wrapped, nboot):
         wo, sizes, gf, gseeds = _walk_groups(lab[pick], factors, wseed)
         out.append((r, dead, start, lstar, chol, wseed, wo, sizes, gf, gseeds))
         r.timing["host_s"] += dt + time.perf_counter() - t0
+    return out
+
+
+def _ensemble_resident(live, ndim, seeds, nlive, kbatch, nsteps, dlogz, max_iter, max_calls, wrapped):
+    """run_nested_ensemble(live=model): the device_order branch of run_nested_slice for every seed, the runs' live sets resident
+    side by side (run r = rows r nlive .. r nlive + nlive - 1 of the ensemble), their bookkeeping vectorised across runs."""
+    defaults = ultranest_defaults(ndim)
+    nlive = int(nlive or defaults["nlive"])
+    kbatch = int(kbatch or max(1, nlive // 4))
+    if not 1 <= kbatch < nlive:
+        raise ValueError("need 1 <= kbatch < nlive")
+    nsteps = int(nsteps or defaults["nsteps"])
+    wrapped = None if wrapped is None else np.asarray(wrapped, dtype=bool)
+    R = len(seeds)
+    rngs = [np.random.default_rng(s) for s in seeds]
+    live.live_runs_init(np.concatenate([g.random((nlive, ndim)) for g in rngs]), R)
+    ncall = np.full(R, nlive, dtype=np.int64)
+    logz, h = np.full(R, -np.inf), np.zeros(R)
+    logx_run, niter = np.zeros(R), np.zeros(R, dtype=np.int64)
+    done = np.zeros(R, dtype=bool)
+    timing = [{"host_s": 0.0, "walk_s": 0.0, "turns": 0} for _ in range(R)]
+    stop_gap = np.log(np.expm1(dlogz))
+    it, logx = 0, 0.0                               # every running run is at the same iteration
+    turns = []                                      # (runs, dying log-L [A, kbatch], their log-weights) of every turn
+    while it < max_iter:
+        act = np.flatnonzero(~done & (ncall < max_calls))
+        if not act.size:
+            break
+        t0 = time.perf_counter()
+        dl, lstar, top = live.live_runs_sort(act, kbatch)
+        ranks = np.empty((act.size, kbatch), dtype=np.int64)
+        walk_seeds = []
+        for j, r in enumerate(act):                 # the draws of the standalone run, from the run's own generator
+            ranks[j] = rngs[r].integers(0, nlive - kbatch, kbatch)
+            walk_seeds.append(int(rngs[r].integers(0, 2 ** 62)))
+        t1 = time.perf_counter()
+        wl, used = live.live_runs_step(act, kbatch, ranks, lstar, wrapped, nsteps, 200, walk_seeds)
+        t2 = time.perf_counter()
+        logw, logz[act], h[act], logx = _deaths_runs(logz[act], h[act], logx, dl, nlive, kbatch)
+        turns.append((act, dl, logw))
+        it += kbatch
+        ncall[act] += used
+        wmax = np.max(wl, axis=1)
+        top = np.where(wmax > top, wmax, top)       # max(top, max(wl)) as the standalone run takes it
+        done[act[top + logx < logz[act] + stop_gap]] = True
+        niter[act], logx_run[act] = it, logx
+        host = (time.perf_counter() - t2 + t1 - t0) / act.size
+        for r in act:
+            tr = timing[r]
+            tr["host_s"] += host
+            tr["walk_s"] += t2 - t1
+            tr["turns"] += 1
+    dead_logl, dead_logw = [[] for _ in range(R)], [[] for _ in range(R)]
+    for act, dl, logw in turns:
+        for j, r in enumerate(act):
+            dead_logl[r].append(dl[j]); dead_logw[r].append(logw[j])
+    out = []
+    for r in range(R):
+        logl = live.live_runs_get(r, cube=False, theta=False)[2]
+        logw_live = logx_run[r] - np.log(nlive) + logl
+        logz_final = np.logaddexp(logz[r], _logaddexp_many(logw_live))
+        ndead = live.live_runs_dead_count(r)
+        all_theta = np.empty((ndead + nlive, ndim))
+        live.live_runs_dead(r, theta_out=all_theta[:ndead])
+        live.live_runs_get(r, cube=False, logl=False, theta_out=all_theta[ndead:])
+        all_logl = np.concatenate(dead_logl[r] + [logl])
+        all_logw = np.concatenate(dead_logw[r] + [logw_live]) - logz_final
+        out.append(NestedResult(float(logz_final), float(np.sqrt(max(h[r], 0.0) / nlive)), int(niter[r]), int(ncall[r]), float(h[r]),
+                                all_theta, all_logl, all_logw, timing[r], None))
     return out

@@ -51,9 +51,10 @@ extern "C" {
 #endif
 
 #define RVLL_VERSION_MAJOR 0
-#define RVLL_VERSION_MINOR 4   /* 0.2: rvll_slice_walk takes walker_base; RVLL_FLAG_WANDERED; resident live set
+#define RVLL_VERSION_MINOR 5   /* 0.2: rvll_slice_walk takes walker_base; RVLL_FLAG_WANDERED; resident live set
                                   0.3: rvll_slice_walk_runs
-                                  0.4: rvll_cluster_runs */
+                                  0.4: rvll_cluster_runs
+                                  0.5: rvll_live_runs_* (resident ensemble) */
 
 /* ---- error codes ------------------------------------------------------ */
 #define RVLL_OK             0
@@ -332,6 +333,36 @@ int rvll_live_step(rvll_handle* h, const int32_t* order /*[N], or NULL after rvl
 int rvll_live_sort(rvll_handle* h, int64_t kdead, double* dead_logl /*[kdead]*/, double* lstar, double* max_logl);
 int rvll_live_get(rvll_handle* h, double* cube, double* theta, double* logl);
 int rvll_live_dead(rvll_handle* h, int64_t* n_dead, double* theta, double* logl);
+/* The resident ENSEMBLE: R independent nested-sampling runs of n live points each, all resident in one handle, sorted, whitened
+ * and walked together (nested.run_nested_ensemble(..., live=model)).  A listed run a of rvll_live_runs_step does
+ * exactly what rvll_live_step(order = NULL, chol = NULL, walker_base = 0) after rvll_live_sort does for a handle that holds only
+ * that run, bit for bit; the walkers of all listed runs walk in one run-mode walk (as rvll_slice_walk_runs), walker i of run a
+ * being row i of run a there.  An ensemble and the one-run live set exclude each other: rvll_live_runs_init empties the one-run
+ * state (rvll_live_step / _sort / _get then refuse, rvll_live_dead returns RVLL_E_INVALID while an ensemble is loaded), and
+ * rvll_live_init empties the ensemble.
+ *
+ * rvll_live_runs_init  cube [R n, ndim]: run r is rows r n .. r n + n - 1; prior transform and log-L in one pass; logl_out [R n]
+ *                      (may be NULL).  Every run's dead store is emptied.  R >= 1, n >= 2, R n < 2^31.
+ * rvll_live_runs_sort  for the A listed runs (runs [A]: distinct, ascending, < R) the stable ascending order of their log-L (ties by
+ *                      row, as rvll_live_sort), kept on the device; dead_logl [A, kdead] the kdead lowest of every run in order,
+ *                      lstar [A] the kdead-th lowest, max_logl [A] the highest.  1 <= kdead < n.
+ * rvll_live_runs_step  follows a rvll_live_runs_sort of the same runs and kdead, with the lstar it returned; ranks [A, kdead] are
+ *                      ranks among run a's survivors (0 .. n - kdead - 1); seeds [A]; ncalls [A] (may be NULL) and logl_new
+ *                      [A, kdead] out; chol_out [A, ndim, ndim] (may be NULL) receives every run's whitening factor.  The dying rows
+ *                      go to their runs' dead stores last: a step that fails (a covariance that is not positive definite, a walk
+ *                      that fails) leaves every run as it was.
+ * rvll_live_runs_get   run r's live set as it stands (any pointer may be NULL).
+ * rvll_live_runs_dead  as rvll_live_dead, for run r: its dead rows in the order they died.
+ * Errors: RVLL_E_INVALID (arguments, call order), RVLL_E_NOMEM.                                                            */
+int rvll_live_runs_init(rvll_handle* h, const double* cube /*[R n, ndim]*/, int32_t R, int64_t n, double* logl_out /*[R n] or NULL*/);
+int rvll_live_runs_sort(rvll_handle* h, const int32_t* runs /*[A]*/, int32_t A, int64_t kdead, double* dead_logl /*[A, kdead]*/,
+                        double* lstar /*[A]*/, double* max_logl /*[A]*/);
+int rvll_live_runs_step(rvll_handle* h, const int32_t* runs /*[A]*/, int32_t A, int64_t kdead, const int32_t* ranks /*[A, kdead]*/,
+                        const double* lstar /*[A]*/, const int32_t* wrapped /*[ndim] or NULL*/, int32_t nsteps, int32_t max_rounds,
+                        const uint64_t* seeds /*[A]*/, int64_t* ncalls /*[A] or NULL*/, double* logl_new /*[A, kdead]*/,
+                        double* chol_out /*[A, ndim, ndim] or NULL*/);
+int rvll_live_runs_get(rvll_handle* h, int32_t run, double* cube, double* theta, double* logl);
+int rvll_live_runs_dead(rvll_handle* h, int32_t run, int64_t* n_dead, double* theta, double* logl);
 
 /* ---- scalar-callback latency ------------------------------------------------------------------------- */
 /* PolyChord's loglike(theta) is irreducibly scalar (evidence/polychord/__init__.py:166-171): one theta per call.
