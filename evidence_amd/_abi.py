@@ -19,7 +19,7 @@ ERROR_NAMES = {
 FLAG_INVALID_ORBIT = 1
 FLAG_NONCONVERGED = 2
 FLAG_WANDERED = 4                  # a Kepler solve took > 8 Newton steps: log-L there is conditioned to ~1e-9 (rvll.h)
-ABI_VERSION = (0, 5)               # RVLL_VERSION_MAJOR / MINOR these bindings were written against
+ABI_VERSION = (0, 6)               # RVLL_VERSION_MAJOR / MINOR these bindings were written against
 
 K_K1, K_LOGK1 = 0, 1
 P_PERIOD, P_LOGPERIOD = 0, 1
@@ -115,6 +115,10 @@ PROTOTYPES = {
                                       C.POINTER(C.c_uint64), C.POINTER(C.c_int64), _dp, _dp]),
     "rvll_live_runs_get": (C.c_int, [Handle, C.c_int32, _dp, _dp, _dp]),
     "rvll_live_runs_dead": (C.c_int, [Handle, C.c_int32, C.POINTER(C.c_int64), _dp, _dp]),
+    "rvll_live_runs_step_clustered": (C.c_int, [Handle, _ip, C.c_int32, C.c_int64, _ip, _dp, _ip, C.c_int32, C.c_int32,
+                                                C.POINTER(C.c_uint64), C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_int64),
+                                                _dp, _ip]),
+    "rvll_live_runs_clusters": (C.c_int, [Handle, C.c_int32, C.POINTER(C.c_int64), _ip, _ip, _dp, _dp, _dp]),
     "rvll_scalar_server": (C.c_int, [Handle, C.c_int32]),
     "rvll_loglike_batch": (C.c_int, [Handle, _dp, C.c_int64, _dp, _ip]),
     "rvll_prior_batch": (C.c_int, [Handle, _dp, C.c_int64, _dp]),

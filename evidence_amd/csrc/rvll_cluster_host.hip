@@ -1,5 +1,6 @@
 // rvll_cluster_host.hip — host side of the clustering of live points (rvll_cluster_runs; include/rvll.h): argument
-// checks, the workgroup table, grow-only device blocks, one upload and one download per call.  The kernels are in
+// checks, the workgroup table, grow-only device blocks, one upload and one download per call, around a core on device pointers
+// that the clustered step of the resident ensemble (rvll_live_runs_step_clustered) also calls.  The kernels are in
 // rvll_cluster.hip.
 #include "rvll_host.h"
 
@@ -25,6 +26,83 @@ int reserve(rvll_handle* h, void** p, size_t* cap, size_t bytes)
 }
 
 }  // namespace
+
+namespace rvll {
+namespace host {
+
+std::vector<int32_t> cluster_blocks(const int64_t* run_start, int64_t R)
+{
+    std::vector<int32_t> blocks;
+    for (int64_t r = 0; r < R; ++r)
+        for (int64_t i = run_start[r]; i < run_start[r + 1]; i += 64) { blocks.push_back((int32_t)r); blocks.push_back((int32_t)i); }
+    return blocks;
+}
+
+// packed inputs: cube, scale, run_start, seeds, block table; work: forest, per-run maxima; packed outputs: radius2, nclusters, labels
+ClusterLayout cluster_layout(int64_t N, int64_t R, int D, size_t block_ints)
+{
+    ClusterLayout L{};
+    L.o_cube = 0;
+    L.o_scale = up16(L.o_cube + sizeof(double) * (size_t)N * D);
+    L.o_start = up16(L.o_scale + sizeof(double) * (size_t)R * D);
+    L.o_seed = up16(L.o_start + sizeof(int64_t) * (size_t)(R + 1));
+    L.o_blk = up16(L.o_seed + sizeof(uint64_t) * (size_t)R);
+    L.in_bytes = up16(L.o_blk + sizeof(int32_t) * block_ints);
+    L.w_slots = up16(sizeof(int32_t) * (size_t)N);
+    L.work_bytes = L.w_slots + sizeof(unsigned long long) * rvll::kClusterSlots * (size_t)R;
+    L.p_ncl = up16(sizeof(double) * (size_t)R);
+    L.p_lab = up16(L.p_ncl + sizeof(int32_t) * (size_t)R);
+    L.out_bytes = up16(L.p_lab + sizeof(int32_t) * (size_t)N);
+    L.N = N; L.R = R; L.nblocks = (long long)(block_ints / 2);
+    return L;
+}
+
+int cluster_reserve(rvll_handle* h, const ClusterLayout& L, const char* who)
+{
+    if (L.in_bytes + L.work_bytes + L.out_bytes > kClusterMaxBytes)
+        return report_error(RVLL_E_NOMEM, "%s: %zu bytes of device memory exceed the clustering's budget", who,
+                            L.in_bytes + L.work_bytes + L.out_bytes);
+    int rc = reserve(h, &h->d_cl_in, &h->cl_in_cap, L.in_bytes);
+    if (!rc) rc = reserve(h, &h->d_cl_work, &h->cl_work_cap, L.work_bytes);
+    if (!rc) rc = reserve(h, &h->d_cl_out, &h->cl_out_cap, L.out_bytes);
+    return rc;
+}
+
+rvll::ClusterArgs cluster_args(rvll_handle* h, const ClusterLayout& L, int D, int nboot, const int32_t* wrapped)
+{
+    unsigned long long wmask = 0;
+    if (wrapped)
+        for (int d = 0; d < D; ++d) if (wrapped[d]) wmask |= 1ull << d;
+    char* din = static_cast<char*>(h->d_cl_in);
+    char* dwork = static_cast<char*>(h->d_cl_work);
+    char* dout = static_cast<char*>(h->d_cl_out);
+    rvll::ClusterArgs a{};
+    a.cube = reinterpret_cast<const double*>(din + L.o_cube);
+    a.scale = reinterpret_cast<const double*>(din + L.o_scale);
+    a.run_start = reinterpret_cast<const long long*>(din + L.o_start);
+    a.seeds = reinterpret_cast<const unsigned long long*>(din + L.o_seed);
+    a.blocks = reinterpret_cast<const int32_t*>(din + L.o_blk);
+    a.nblocks = L.nblocks;
+    a.R = (int)L.R; a.D = D; a.nboot = nboot; a.tile_rows = rvll::cluster_tile_rows(D);
+    a.wrapped = wmask;
+    a.parent = reinterpret_cast<int32_t*>(dwork);
+    a.slots = reinterpret_cast<unsigned long long*>(dwork + L.w_slots);
+    a.radius2 = reinterpret_cast<double*>(dout);
+    a.nclusters = reinterpret_cast<int32_t*>(dout + L.p_ncl);
+    a.labels = reinterpret_cast<int32_t*>(dout + L.p_lab);
+    return a;
+}
+
+// the clustering itself, on inputs already in the device blocks: the per-run maxima zeroed, the three kernels; asynchronous
+int cluster_core(rvll_handle* h, const rvll::ClusterArgs& a)
+{
+    HIP_TRY(hipMemsetAsync(a.slots, 0, sizeof(unsigned long long) * rvll::kClusterSlots * (size_t)a.R, h->compute));
+    HIP_TRY(rvll::launch_cluster(a, h->compute));
+    return RVLL_OK;
+}
+
+}  // namespace host
+}  // namespace rvll
 
 extern "C" {
 
@@ -53,65 +131,29 @@ int rvll_cluster_runs(rvll_handle* h, const double* cube, const int64_t* run_sta
     for (int64_t k = 0; k < R * D; ++k)
         if (!(std::isfinite(scale[k]) && scale[k] > 0.0))
             return report_error(RVLL_E_INVALID, "rvll_cluster_runs: scale[%lld] is not finite and positive", (long long)k);
-    unsigned long long wmask = 0;
-    if (wrapped)
-        for (int d = 0; d < D; ++d) if (wrapped[d]) wmask |= 1ull << d;
-
     // workgroups of the row kernels: 64 rows of one run each
-    std::vector<int32_t> blocks;
-    for (int64_t r = 0; r < R; ++r)
-        for (int64_t i = run_start[r]; i < run_start[r + 1]; i += 64) { blocks.push_back((int32_t)r); blocks.push_back((int32_t)i); }
-    const long long nblocks = (long long)blocks.size() / 2;
-
-    // packed inputs: cube, scale, run_start, seeds, block table
-    const size_t o_cube = 0, o_scale = up16(o_cube + sizeof(double) * (size_t)N * D);
-    const size_t o_start = up16(o_scale + sizeof(double) * (size_t)R * D), o_seed = up16(o_start + sizeof(int64_t) * (size_t)(R + 1));
-    const size_t o_blk = up16(o_seed + sizeof(uint64_t) * (size_t)R), in_bytes = up16(o_blk + sizeof(int32_t) * blocks.size());
-    // work: forest, per-run maxima; packed outputs: radius2, nclusters, labels
-    const size_t w_slots = up16(sizeof(int32_t) * (size_t)N), work_bytes = w_slots + sizeof(unsigned long long) * rvll::kClusterSlots * (size_t)R;
-    const size_t p_ncl = up16(sizeof(double) * (size_t)R), p_lab = up16(p_ncl + sizeof(int32_t) * (size_t)R);
-    const size_t out_bytes = up16(p_lab + sizeof(int32_t) * (size_t)N);
-    if (in_bytes + work_bytes + out_bytes > kClusterMaxBytes)
-        return report_error(RVLL_E_NOMEM, "rvll_cluster_runs: %zu bytes of device memory exceed the clustering's budget",
-                            in_bytes + work_bytes + out_bytes);
-    rc = reserve(h, &h->d_cl_in, &h->cl_in_cap, in_bytes);
-    if (!rc) rc = reserve(h, &h->d_cl_work, &h->cl_work_cap, work_bytes);
-    if (!rc) rc = reserve(h, &h->d_cl_out, &h->cl_out_cap, out_bytes);
+    const std::vector<int32_t> blocks = cluster_blocks(run_start, R);
+    const ClusterLayout L = cluster_layout(N, R, D, blocks.size());
+    rc = cluster_reserve(h, L, "rvll_cluster_runs");
     if (rc) return rc;
 
-    std::vector<char> in(in_bytes), out(out_bytes);
-    if (N > 0) memcpy(in.data() + o_cube, cube, sizeof(double) * (size_t)N * D);
-    memcpy(in.data() + o_scale, scale, sizeof(double) * (size_t)R * D);
-    memcpy(in.data() + o_start, run_start, sizeof(int64_t) * (size_t)(R + 1));
-    memcpy(in.data() + o_seed, seeds, sizeof(uint64_t) * (size_t)R);
-    if (!blocks.empty()) memcpy(in.data() + o_blk, blocks.data(), sizeof(int32_t) * blocks.size());
+    std::vector<char> in(L.in_bytes), out(L.out_bytes);
+    if (N > 0) memcpy(in.data() + L.o_cube, cube, sizeof(double) * (size_t)N * D);
+    memcpy(in.data() + L.o_scale, scale, sizeof(double) * (size_t)R * D);
+    memcpy(in.data() + L.o_start, run_start, sizeof(int64_t) * (size_t)(R + 1));
+    memcpy(in.data() + L.o_seed, seeds, sizeof(uint64_t) * (size_t)R);
+    if (!blocks.empty()) memcpy(in.data() + L.o_blk, blocks.data(), sizeof(int32_t) * blocks.size());
 
     hipStream_t st = h->compute;
-    char* din = static_cast<char*>(h->d_cl_in);
-    char* dwork = static_cast<char*>(h->d_cl_work);
-    char* dout = static_cast<char*>(h->d_cl_out);
-    rvll::ClusterArgs a{};
-    a.cube = reinterpret_cast<const double*>(din + o_cube);
-    a.scale = reinterpret_cast<const double*>(din + o_scale);
-    a.run_start = reinterpret_cast<const long long*>(din + o_start);
-    a.seeds = reinterpret_cast<const unsigned long long*>(din + o_seed);
-    a.blocks = reinterpret_cast<const int32_t*>(din + o_blk);
-    a.nblocks = nblocks;
-    a.R = (int)R; a.D = D; a.nboot = nboot; a.tile_rows = rvll::cluster_tile_rows(D);
-    a.wrapped = wmask;
-    a.parent = reinterpret_cast<int32_t*>(dwork);
-    a.slots = reinterpret_cast<unsigned long long*>(dwork + w_slots);
-    a.radius2 = reinterpret_cast<double*>(dout);
-    a.nclusters = reinterpret_cast<int32_t*>(dout + p_ncl);
-    a.labels = reinterpret_cast<int32_t*>(dout + p_lab);
-    HIP_TRY(hipMemcpyAsync(din, in.data(), in_bytes, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(a.slots, 0, sizeof(unsigned long long) * rvll::kClusterSlots * (size_t)R, st));
-    HIP_TRY(rvll::launch_cluster(a, st));
-    HIP_TRY(hipMemcpyAsync(out.data(), dout, out_bytes, hipMemcpyDeviceToHost, st));
+    const rvll::ClusterArgs a = cluster_args(h, L, D, nboot, wrapped);
+    HIP_TRY(hipMemcpyAsync(h->d_cl_in, in.data(), L.in_bytes, hipMemcpyHostToDevice, st));
+    rc = cluster_core(h, a);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out.data(), h->d_cl_out, L.out_bytes, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     memcpy(radius2, out.data(), sizeof(double) * (size_t)R);
-    memcpy(nclusters, out.data() + p_ncl, sizeof(int32_t) * (size_t)R);
-    if (N > 0) memcpy(labels, out.data() + p_lab, sizeof(int32_t) * (size_t)N);
+    memcpy(nclusters, out.data() + L.p_ncl, sizeof(int32_t) * (size_t)R);
+    if (N > 0) memcpy(labels, out.data() + L.p_lab, sizeof(int32_t) * (size_t)N);
     return RVLL_OK;
 }
 

@@ -199,6 +199,18 @@ struct rvll_handle {
     void* d_cl_work = nullptr;
     void* d_cl_out = nullptr;
     size_t cl_in_cap = 0, cl_work_cap = 0, cl_out_cap = 0;   // bytes
+    // the clustered step of the resident ensemble (rvll_live_runs_step_clustered): grow-only block of the per-(run, cluster) segments
+    // — (offset, rows) [S][2], fold scales [S][2], mean [S][D], covariance [S][D, D] — and what the last clustered step found, for
+    // rvll_live_runs_clusters: per listed run the survivors' labels in rank order [A m], the metric scale [A D], the cluster count,
+    // the factors the walk used (one per cluster, or the run's own when it has one cluster), and the seconds between its syncs
+    void* d_clseg = nullptr;
+    size_t clseg_cap = 0;                       // bytes
+    int32_t cl_A = 0;                           // listed runs of the last clustered step (0: none since the ensemble was loaded)
+    long long cl_m = 0;                         // survivors per run
+    std::vector<int32_t> cl_labels, cl_ncl;
+    std::vector<double> cl_scale;
+    std::vector<std::vector<double>> cl_factors;
+    double cl_phase_s[3] = {0., 0., 0.};        // clustering + label sort, per-cluster moments, walk
 
     hipEvent_t marks[2] = {nullptr, nullptr};   // rvll_dev_mark: HIP events on lane 0's stream
 
@@ -233,6 +245,19 @@ int build_args(rvll_handle* h, const double* d_theta, double* d_logL, int32_t* d
 void make_fused(const rvll_handle* h, const double* d_cube, double* d_theta_out, rvll::LoglikeArgs* a);
 int download_rows(rvll_handle* h, void* dst, const void* src_dev, size_t bytes);
 void comm_release(rvll_handle* h);                  // rvll_comm.hip: destroy the handle's communicators
+// rvll_cluster_host.hip: the clustering's device blocks (d_cl_in: cube, scale, run_start, seeds, block table; d_cl_work: forest,
+// per-run maxima; d_cl_out: radius2, nclusters, labels) and its core on inputs already there (asynchronous)
+struct ClusterLayout {
+    size_t o_cube, o_scale, o_start, o_seed, o_blk, in_bytes;
+    size_t w_slots, work_bytes;
+    size_t p_ncl, p_lab, out_bytes;
+    long long N, R, nblocks;
+};
+std::vector<int32_t> cluster_blocks(const int64_t* run_start, int64_t R);   // (run, first row) of every 64 rows of one run
+ClusterLayout cluster_layout(int64_t N, int64_t R, int D, size_t block_ints);
+int cluster_reserve(rvll_handle* h, const ClusterLayout& L, const char* who);
+rvll::ClusterArgs cluster_args(rvll_handle* h, const ClusterLayout& L, int D, int nboot, const int32_t* wrapped);
+int cluster_core(rvll_handle* h, const rvll::ClusterArgs& a);
 constexpr size_t kDownloadStagedMin = 32u << 20, kDeadStagedMin = 8u << 20;
 
 }  // namespace host

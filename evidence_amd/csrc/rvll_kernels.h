@@ -259,6 +259,16 @@ hipError_t launch_runs_sort(const double* logl, const int32_t* runs, int A, long
 hipError_t launch_runs_sorted_logl(const double* logl, const int32_t* order, int A, long long n, long long kdead, double* out, hipStream_t st);
 hipError_t launch_runs_compose(const int32_t* order, int A, long long n, long long kdead, const int32_t* rank, int32_t* dying,
                                int32_t* start, int32_t* run, int32_t* wid, hipStream_t st);
+// the clustered step (rvll_live_runs_step_clustered): every listed run's survivors packed in rank order (dst [A m, D], m = n - kdead;
+// slot[e] = e; seg[a] = a m, a <= A), their stable order by cluster label per run (one segmented radix sort), and the moments of S
+// ragged segments (seg [S][2] = offset into idx, rows; sc [S][2] = the two fold scales), each bit for bit its own launch_moments
+hipError_t launch_runs_survivors(const double* u, const int32_t* order, int A, long long n, long long kdead, int D, double* dst,
+                                 int32_t* slot, int32_t* seg, hipStream_t st);
+size_t label_sort_temp_bytes(int A, long long total);
+hipError_t launch_label_sort(const int32_t* labels, int32_t* labels_out, const int32_t* slot_in, int32_t* slot_out, int A, long long total,
+                             const int32_t* seg, void* temp, size_t temp_bytes, hipStream_t st);
+hipError_t launch_moments_segs(const double* u, const int32_t* idx, const long long* seg, const double* sc, int S, int D, double* scratch,
+                               int chunk, double* mean, double* cov, hipStream_t st);
 
 // ---- scalar-call server: a one-workgroup persistent kernel that answers single-point log-L requests through a
 // block of host-coherent pinned memory, so a scalar callback costs a PCIe round trip instead of a kernel launch

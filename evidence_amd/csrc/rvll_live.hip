@@ -43,11 +43,18 @@ void scatter_rows_kernel(const double* src, const int32_t* idx, long long n, int
 // partial column sums of the rows idx[0..n): block b takes rows b, b + kMomBlocks, ...; its threads are kThreads / D groups
 // of D, group g summing every (kThreads / D)-th of the block's rows, and the groups' sums are added in group order — a
 // fixed order for a given (n, D).  (One thread per column, as first written, left 237 of 256 threads idle: 63 us per call.)
+// kSeg: set blockIdx.y is segment y0 + blockIdx.y of a table of (offset, rows) pairs (launch_moments_segs) instead of a stride.
+template <bool kSeg>
 __global__ __launch_bounds__(kThreads)
 void moments_sum_kernel(const double* u, const int32_t* idx, long long n, int D, double* part /*[kMomBlocks][D]*/,
-                        long long idx_stride, long long part_stride)
+                        long long idx_stride, long long part_stride, const long long* seg, long long y0)
 {
-    idx += blockIdx.y * idx_stride;                          // run blockIdx.y of a batch (launch_moments_runs); 0 for one run
+    if (kSeg) {
+        idx += seg[2 * (y0 + blockIdx.y)];
+        n = seg[2 * (y0 + blockIdx.y) + 1];
+    } else {
+        idx += blockIdx.y * idx_stride;                      // run blockIdx.y of a batch (launch_moments_runs); 0 for one run
+    }
     part += blockIdx.y * part_stride;
     __shared__ double acc[kThreads];
     const int groups = D <= kThreads ? kThreads / D : 1;
@@ -75,10 +82,14 @@ void moments_sum_kernel(const double* u, const int32_t* idx, long long n, int D,
 
 // out[d] = (sum over blocks) * scale: four threads a column, each a quarter of the blocks in block order, the quarters added in
 // order — a fixed order for a given width.  (One thread a column walked 128 dependent loads: 9.5 us a call, two calls a step.)
+// kSeg: the scale is segment (y0 + blockIdx.y)'s, sc[2 (y0 + blockIdx.y)].
 constexpr int kFoldCols = kThreads / 4;
+template <bool kSeg>
 __global__ __launch_bounds__(kThreads)
-void moments_fold_kernel(const double* part, int width, double scale, double* out, long long part_stride, long long out_stride)
+void moments_fold_kernel(const double* part, int width, double scale, double* out, long long part_stride, long long out_stride,
+                         const double* sc, long long y0)
 {
+    if (kSeg) scale = sc[2 * (y0 + blockIdx.y)];
     part += blockIdx.y * part_stride;
     out += blockIdx.y * out_stride;
     __shared__ double q[4][kFoldCols];
@@ -96,11 +107,18 @@ void moments_fold_kernel(const double* part, int width, double scale, double* ou
 // kCovRows at a time (read from HBM row by row, every (j, l) pair waited ~2 us for each of its block's rows: 51 us a call at
 // 16384 rows; the sums are the same terms in the same order)
 constexpr int kCovRows = 32;
+template <bool kSeg>
 __global__ __launch_bounds__(kThreads)
 void moments_cov_kernel(const double* u, const int32_t* idx, long long n, int D, const double* mean,
-                        double* part /*[kMomBlocks][D*D]*/, long long idx_stride, long long part_stride)
+                        double* part /*[kMomBlocks][D*D]*/, long long idx_stride, long long part_stride, const long long* seg,
+                        long long y0)
 {
-    idx += blockIdx.y * idx_stride;
+    if (kSeg) {
+        idx += seg[2 * (y0 + blockIdx.y)];
+        n = seg[2 * (y0 + blockIdx.y) + 1];
+    } else {
+        idx += blockIdx.y * idx_stride;
+    }
     mean += (long long)blockIdx.y * D;
     part += blockIdx.y * part_stride;
     extern __shared__ double rows[];                         // [kCovRows][D], centred
@@ -217,6 +235,23 @@ void runs_compose_kernel(const int32_t* order, int A, long long n, long long kde
     }
 }
 
+// the clustered step (rvll_live_runs_step_clustered): listed run a's survivors, ranks kdead .. n - 1, packed in rank order as rows
+// a m .. a m + m - 1 (m = n - kdead) of the clustering's row buffer; slot[e] = e (the values of the (label, rank) sort) and
+// seg[a] = a m, a <= A (its segments)
+__global__ __launch_bounds__(kThreads)
+void runs_survivors_kernel(const double* u, const int32_t* order, int A, long long n, long long kdead, int D, double* dst,
+                           int32_t* slot, int32_t* seg)
+{
+    const long long m = n - kdead, total = (long long)A * m * D;
+    for (long long e = (long long)blockIdx.x * kThreads + threadIdx.x; e < total || e <= A; e += (long long)gridDim.x * kThreads) {
+        if (e <= A) seg[e] = (int32_t)(e * m);
+        if (e >= total) continue;
+        const long long r = e / D, d = e - r * D, a = r / m;
+        dst[e] = u[(long long)order[a * n + kdead + (r - a * m)] * D + d];
+        if (d == 0) slot[r] = (int32_t)r;
+    }
+}
+
 int blocks_for(long long total)
 {
     long long b = (total + kThreads - 1) / kThreads;
@@ -266,13 +301,14 @@ hipError_t launch_moments_runs(const double* u, const int32_t* idx, long long id
         double* part = scratch + (long long)a0 * ps;
         double* m = mean + (long long)a0 * D;
         double* c = cov + (long long)a0 * D * D;
-        hipLaunchKernelGGL(moments_sum_kernel, dim3(kMomBlocks, na), dim3(kThreads), 0, st, u, ix, n, D, part, idx_stride, ps);
-        hipLaunchKernelGGL(moments_fold_kernel, dim3((D + kFoldCols - 1) / kFoldCols, na), dim3(kThreads), 0, st, part, D, 1.0 / (double)n,
-                           m, ps, (long long)D);
-        hipLaunchKernelGGL(moments_cov_kernel, dim3(kMomBlocks, na), dim3(kThreads), sizeof(double) * ((size_t)kCovRows * D + D), st, u, ix,
-                           n, D, m, part, idx_stride, ps);
-        hipLaunchKernelGGL(moments_fold_kernel, dim3((D * D + kFoldCols - 1) / kFoldCols, na), dim3(kThreads), 0, st, part, D * D,
-                           1.0 / (double)(n > 1 ? n - 1 : 1), c, ps, (long long)D * D);
+        hipLaunchKernelGGL(moments_sum_kernel<false>, dim3(kMomBlocks, na), dim3(kThreads), 0, st, u, ix, n, D, part, idx_stride, ps,
+                           nullptr, 0LL);
+        hipLaunchKernelGGL(moments_fold_kernel<false>, dim3((D + kFoldCols - 1) / kFoldCols, na), dim3(kThreads), 0, st, part, D,
+                           1.0 / (double)n, m, ps, (long long)D, nullptr, 0LL);
+        hipLaunchKernelGGL(moments_cov_kernel<false>, dim3(kMomBlocks, na), dim3(kThreads), sizeof(double) * ((size_t)kCovRows * D + D), st,
+                           u, ix, n, D, m, part, idx_stride, ps, nullptr, 0LL);
+        hipLaunchKernelGGL(moments_fold_kernel<false>, dim3((D * D + kFoldCols - 1) / kFoldCols, na), dim3(kThreads), 0, st, part, D * D,
+                           1.0 / (double)(n > 1 ? n - 1 : 1), c, ps, (long long)D * D, nullptr, 0LL);
     }
     return hipGetLastError();
 }
@@ -345,6 +381,64 @@ hipError_t launch_runs_compose(const int32_t* order, int A, long long n, long lo
 {
     hipLaunchKernelGGL(runs_compose_kernel, dim3(blocks_for((long long)A * kdead)), dim3(kThreads), 0, st, order, A, n, kdead, rank,
                        dying, start, run, wid);
+    return hipGetLastError();
+}
+
+// ---- the clustered step of the resident ensemble ------------------------------------------------------------------------------
+hipError_t launch_runs_survivors(const double* u, const int32_t* order, int A, long long n, long long kdead, int D, double* dst,
+                                 int32_t* slot, int32_t* seg, hipStream_t st)
+{
+    if (A <= 0 || kdead >= n || D <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(runs_survivors_kernel, dim3(blocks_for((long long)A * (n - kdead) * D + 1)), dim3(kThreads), 0, st, u, order, A,
+                       n, kdead, D, dst, slot, seg);
+    return hipGetLastError();
+}
+
+// Every run's stable order by cluster label: one segmented radix sort of the A m labels (values: slots a m + j in rank order, so ties
+// keep rank order), segment a = [seg[a], seg[a + 1]).  The labels are below 2^31.
+size_t label_sort_temp_bytes(int A, long long total)
+{
+    size_t bytes = 0;
+    unsigned int* k = nullptr;
+    int32_t* v = nullptr;
+    (void)rocprim::segmented_radix_sort_pairs(nullptr, bytes, k, k, v, v, (unsigned int)total, (unsigned int)A, v, v + 1, 0, 32,
+                                              (hipStream_t) nullptr);
+    return bytes;
+}
+
+hipError_t launch_label_sort(const int32_t* labels, int32_t* labels_out, const int32_t* slot_in, int32_t* slot_out, int A, long long total,
+                             const int32_t* seg, void* temp, size_t temp_bytes, hipStream_t st)
+{
+    if (A <= 0 || total <= 0) return hipErrorInvalidValue;
+    return rocprim::segmented_radix_sort_pairs(temp, temp_bytes, reinterpret_cast<const unsigned int*>(labels),
+                                               reinterpret_cast<unsigned int*>(labels_out), slot_in, slot_out, (unsigned int)total,
+                                               (unsigned int)A, seg, seg + 1, 0, 32, st);
+}
+
+// The moments of S ragged segments in one set of four launches per chunk of up to `chunk` segments: segment s is the rows
+// idx[seg[2 s] .. seg[2 s] + seg[2 s + 1]) of u, sc[2 s] = 1 / rows and sc[2 s + 1] = 1 / (rows - 1) (rows > 1) its fold scales as
+// launch_moments forms them.  Block (b, s) does what block b of launch_moments does for segment s alone, so each segment's mean
+// [S][D] and covariance [S][D, D] are those of its own launch_moments, bit for bit.  seg, sc on the device; scratch: chunk x
+// moments_runs_scratch_doubles(D) doubles (the chunks reuse it, in stream order).
+hipError_t launch_moments_segs(const double* u, const int32_t* idx, const long long* seg, const double* sc, int S, int D, double* scratch,
+                               int chunk, double* mean, double* cov, hipStream_t st)
+{
+    if (S <= 0 || D <= 0 || chunk <= 0) return hipErrorInvalidValue;
+    const long long ps = (long long)moments_runs_scratch_doubles(D);
+    chunk = std::min(chunk, 65535);
+    for (int s0 = 0; s0 < S; s0 += chunk) {
+        const int ns = std::min(S - s0, chunk);
+        double* m = mean + (long long)s0 * D;
+        double* c = cov + (long long)s0 * D * D;
+        hipLaunchKernelGGL(moments_sum_kernel<true>, dim3(kMomBlocks, ns), dim3(kThreads), 0, st, u, idx, 0LL, D, scratch, 0LL, ps, seg,
+                           (long long)s0);
+        hipLaunchKernelGGL(moments_fold_kernel<true>, dim3((D + kFoldCols - 1) / kFoldCols, ns), dim3(kThreads), 0, st, scratch, D, 0.0,
+                           m, ps, (long long)D, sc, (long long)s0);
+        hipLaunchKernelGGL(moments_cov_kernel<true>, dim3(kMomBlocks, ns), dim3(kThreads), sizeof(double) * ((size_t)kCovRows * D + D), st,
+                           u, idx, 0LL, D, m, scratch, 0LL, ps, seg, (long long)s0);
+        hipLaunchKernelGGL(moments_fold_kernel<true>, dim3((D * D + kFoldCols - 1) / kFoldCols, ns), dim3(kThreads), 0, st, scratch,
+                           D * D, 0.0, c, ps, (long long)D * D, sc + 1, (long long)s0);
+    }
     return hipGetLastError();
 }
 

@@ -989,6 +989,7 @@ int rvll_live_init(rvll_handle* h, const double* cube, int64_t N, double* logl_o
     h->dead_n = 0;
     h->sorted_kdead = -1;
     h->runs_R = 0;                                       // (and no ensemble's either)
+    h->cl_A = 0;
     rc = live_load(h, cube, N, logl_out);
     if (rc) return rc;
     h->live_n = N;
@@ -1176,6 +1177,7 @@ int rvll_live_runs_init(rvll_handle* h, const double* cube, int32_t R, int64_t n
     h->runs_R = 0;
     h->runs_sorted.clear();
     h->runs_sorted_kdead = -1;
+    h->cl_A = 0;
     const int64_t N = (int64_t)R * n;
     rc = live_load(h, cube, N, logl_out);
     if (rc) return rc;
@@ -1337,6 +1339,275 @@ int rvll_live_runs_step(rvll_handle* h, const int32_t* runs, int32_t A, int64_t 
         for (int64_t e = 0; e < K; ++e) ncalls[e / kdead] += rw.row_calls[(size_t)e];
     for (int32_t a = 0; a < A; ++a) h->runs_dead[(size_t)runs[a]].emplace_back(h->dead_n + (long long)a * kdead, (long long)kdead);
     h->dead_n += K;
+    return RVLL_OK;
+}
+
+// The clustered step ("Clustering inside the resident ensemble").  Host synchronisations before the walk: the global
+// covariances (as rvll_live_runs_step), the labels and cluster counts, and — only when some run has more than one cluster with at
+// least 2 ndim rows — the per-cluster covariances; then those of the walk and the final download, as rvll_live_runs_step.
+int rvll_live_runs_step_clustered(rvll_handle* h, const int32_t* runs, int32_t A, int64_t kdead, const int32_t* ranks,
+                                  const double* lstar, const int32_t* wrapped, int32_t nsteps, int32_t max_rounds,
+                                  const uint64_t* seeds, int32_t nboot, const uint64_t* boot_seeds, int64_t* ncalls,
+                                  double* logl_new, int32_t* nclusters)
+{
+    const char* who = "rvll_live_runs_step_clustered";
+    int rc = use_device(h);
+    if (rc) return rc;
+    if (ncalls && A > 0) for (int32_t a = 0; a < A; ++a) ncalls[a] = 0;
+    rc = runs_check(h, runs, A, kdead, who);
+    if (rc) return rc;
+    if (!ranks || !lstar || !seeds || !logl_new || !boot_seeds || !nclusters) return report_error(RVLL_E_INVALID, "%s: bad arguments", who);
+    if (nboot < 0 || nboot > rvll::kClusterMaxBoot)
+        return report_error(RVLL_E_INVALID, "%s: nboot = %d is outside [0, %d]", who, (int)nboot, rvll::kClusterMaxBoot);
+    const int Di = h->L.ndim;
+    if (Di < 1 || Di > rvll::kClusterMaxDims)
+        return report_error(RVLL_E_UNSUPPORTED, "%s: %d parameters (the clustering takes 1 .. %d)", who, Di, rvll::kClusterMaxDims);
+    const long long n = h->runs_n, R = h->runs_R, m = n - kdead;
+    const int64_t K = (int64_t)A * kdead, M = (int64_t)A * m;
+    rc = walk_check_args(h, K, nsteps, max_rounds, 0);
+    if (rc) return rc;
+    if (h->runs_sorted_kdead != kdead || h->runs_sorted.size() != (size_t)A || !std::equal(runs, runs + A, h->runs_sorted.begin()))
+        return report_error(RVLL_E_INVALID, "%s: no rvll_live_runs_sort of these runs with kdead = %lld precedes", who, (long long)kdead);
+    for (int32_t a = 0; a < A; ++a)
+        if (!(lstar[a] == h->runs_sorted_lstar[(size_t)a]))
+            return report_error(RVLL_E_INVALID, "%s: lstar[%d] is not the one rvll_live_runs_sort returned", who, (int)a);
+    for (int64_t i = 0; i < K; ++i)
+        if (ranks[i] < 0 || ranks[i] >= m)
+            return report_error(RVLL_E_INVALID, "%s: ranks[%lld] is not a rank among the survivors", who, (long long)i);
+    h->runs_sorted.clear();                              // (used up, whatever happens below: the step changes the rows)
+    h->runs_sorted_kdead = -1;
+    const size_t D = (size_t)Di;
+    if (h->dead_n + K >= (1LL << 31)) return report_error(RVLL_E_NOMEM, "%s: the dead store is full (2^31 rows)", who);
+    rc = runs_reserve(h, K, K);                          // (group tables for up to A kdead groups: one walker each)
+    if (rc) return rc;
+    rc = dead_reserve(h, K, K, who);
+    if (rc) return rc;
+    // the clustering's blocks: rows a m .. a m + m - 1 are listed run a's survivors in rank order; the workgroup table depends on
+    // (A, m) alone
+    std::vector<int64_t> cstart((size_t)A + 1);
+    for (int32_t a = 0; a <= A; ++a) cstart[(size_t)a] = (int64_t)a * m;
+    const std::vector<int32_t> blocks = cluster_blocks(cstart.data(), A);
+    const ClusterLayout L = cluster_layout(M, A, Di, blocks.size());
+    rc = cluster_reserve(h, L, who);
+    if (rc) return rc;
+    hipStream_t st = h->compute;
+    const size_t need = rvll::label_sort_temp_bytes(A, M);
+    if (need > h->sort_temp_bytes) {
+        HIP_TRY(hipStreamSynchronize(st));
+        dev_free(h->d_sort_temp);
+        h->sort_temp_bytes = 0;
+        HIP_TRY(hipMalloc(&h->d_sort_temp, need));
+        h->sort_temp_bytes = need;
+    }
+    int32_t* d_order = h->d_runs_idx;                    // [A n] from the sort
+    int32_t* d_rank = d_order + R * n;                   // [A kdead] each: ranks, then the walkers in group order
+    int32_t* d_dying = d_rank + R * n;
+    int32_t* d_start = d_dying + R * n;
+    int32_t* d_seg = d_start + R * n + R;                // [A + 1]: the sort's segments, now the label sort's (a m)
+    // the sort keys' block as ints [4 live_cap]: labels in (label, rank) order | their slots | the walkers' start rows | their
+    // dying rows, in group order (live_cap >= R n >= A m, A kdead)
+    int32_t* kscr = reinterpret_cast<int32_t*>(h->d_sort_keys);
+    const long long lc = h->live_cap;
+    int32_t *d_lab_sorted = kscr, *d_slot_sorted = kscr + lc, *d_gstart = kscr + 2 * lc, *d_gdying = kscr + 3 * lc;
+    HIP_TRY(hipMemcpyAsync(d_rank, ranks, sizeof(int32_t) * (size_t)K, hipMemcpyHostToDevice, st));
+    HIP_TRY(rvll::launch_runs_compose(d_order, A, n, kdead, d_rank, d_dying, d_start, h->d_walk_run, h->d_walk_wid, st));
+    // the dying rows go to the dead store before their rows are overwritten; committed at the bottom, as rvll_live_runs_step
+    HIP_TRY(rvll::launch_gather_rows(h->d_live_theta, d_dying, K, Di, h->d_dead_theta + (size_t)h->dead_n * D, st));
+    HIP_TRY(rvll::launch_gather_rows(h->d_live_logl, d_dying, K, 1, h->d_dead_logl + h->dead_n, st));
+    // 1. the global moments, exactly as rvll_live_runs_step; the survivors packed for the clustering meanwhile
+    double* d_part = h->d_runs_mom;
+    double* d_mean = d_part + rvll::moments_runs_scratch_doubles(Di) * (size_t)A;
+    double* d_cov = d_mean + D * (size_t)A;
+    HIP_TRY(rvll::launch_moments_runs(h->d_live_u, d_order + kdead, n, A, m, Di, d_part, d_mean, d_cov, st));
+    char* din = static_cast<char*>(h->d_cl_in);
+    double* d_surv = reinterpret_cast<double*>(din + L.o_cube);
+    HIP_TRY(rvll::launch_runs_survivors(h->d_live_u, d_order, A, n, kdead, Di, d_surv, h->d_sort_rows, d_seg, st));
+    std::vector<double> cov(D * D * (size_t)A), gfac(D * D * (size_t)A);
+    HIP_TRY(hipMemcpyAsync(cov.data(), d_cov, sizeof(double) * cov.size(), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));                   // sync 1
+    const auto t1 = std::chrono::steady_clock::now();
+    for (int32_t a = 0; a < A; ++a)
+        if (!whitening_factor(cov.data() + D * D * (size_t)a, D, gfac.data() + D * D * (size_t)a))
+            return report_error(RVLL_E_INVALID, "%s: the live points' covariance of run %d is not positive definite", who, (int)runs[a]);
+    // 2. the metric (evidence_amd/nested.py's _cluster_scale of the device covariance), the bootstrap seeds and the block table go
+    // up behind the packed survivors; clustering, then every run's (label, rank) order
+    std::vector<double> scale(D * (size_t)A);
+    for (int32_t a = 0; a < A; ++a)
+        for (size_t d = 0; d < D; ++d) scale[(size_t)a * D + d] = 1.0 / std::sqrt(cov[(size_t)a * D * D + d * D + d] + 1e-14);
+    std::vector<char> in(L.in_bytes - L.o_scale);
+    memcpy(in.data(), scale.data(), sizeof(double) * scale.size());
+    memcpy(in.data() + (L.o_start - L.o_scale), cstart.data(), sizeof(int64_t) * cstart.size());
+    memcpy(in.data() + (L.o_seed - L.o_scale), boot_seeds, sizeof(uint64_t) * (size_t)A);
+    if (!blocks.empty()) memcpy(in.data() + (L.o_blk - L.o_scale), blocks.data(), sizeof(int32_t) * blocks.size());
+    HIP_TRY(hipMemcpyAsync(din + L.o_scale, in.data(), in.size(), hipMemcpyHostToDevice, st));
+    const rvll::ClusterArgs ca = cluster_args(h, L, Di, nboot, wrapped);
+    rc = cluster_core(h, ca);
+    if (rc) return rc;
+    HIP_TRY(rvll::launch_label_sort(ca.labels, d_lab_sorted, h->d_sort_rows, d_slot_sorted, A, M, d_seg, h->d_sort_temp,
+                                    h->sort_temp_bytes, st));
+    std::vector<char> out(L.out_bytes);
+    HIP_TRY(hipMemcpyAsync(out.data(), h->d_cl_out, L.out_bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));                   // sync 2
+    const auto t2 = std::chrono::steady_clock::now();
+    const int32_t* ncl = reinterpret_cast<const int32_t*>(out.data() + L.p_ncl);
+    const int32_t* lab = reinterpret_cast<const int32_t*>(out.data() + L.p_lab);
+    // 3. per (run, cluster) its rows, and where it starts in the run's (label, rank) order; the clusters of at least 2 ndim rows of
+    // the runs with more than one cluster are the segments of one segmented moments pass
+    std::vector<std::vector<long long>> cnt((size_t)A);
+    std::vector<long long> segtab;
+    std::vector<double> segsc;
+    std::vector<std::pair<int32_t, int32_t>> seg_of;     // (listed run, cluster)
+    for (int32_t a = 0; a < A; ++a) {
+        const int32_t k = ncl[a];
+        if (k < 1 || k > m) return report_error(RVLL_E_HIP, "%s: the clustering of run %d returned %d clusters", who, (int)runs[a], (int)k);
+        cnt[(size_t)a].assign((size_t)k, 0);
+        for (long long j = 0; j < m; ++j) {
+            const int32_t c = lab[a * m + j];
+            if (c < 0 || c >= k) return report_error(RVLL_E_HIP, "%s: label %d of run %d is out of range", who, (int)c, (int)runs[a]);
+            ++cnt[(size_t)a][(size_t)c];
+        }
+        if (k == 1) continue;
+        long long off = (long long)a * m;
+        for (int32_t c = 0; c < k; ++c) {
+            const long long rows = cnt[(size_t)a][(size_t)c];
+            if (rows >= 2 * (long long)Di) {
+                segtab.push_back(off); segtab.push_back(rows);
+                segsc.push_back(1.0 / (double)rows); segsc.push_back(1.0 / (double)(rows > 1 ? rows - 1 : 1));
+                seg_of.emplace_back(a, c);
+            }
+            off += rows;
+        }
+    }
+    const int S = (int)seg_of.size();
+    std::vector<double> segcov(D * D * (size_t)S);
+    if (S > 0) {
+        const size_t o_sc = sizeof(long long) * 2 * (size_t)S, o_mean = o_sc + sizeof(double) * 2 * (size_t)S;
+        const size_t o_cov = o_mean + sizeof(double) * D * (size_t)S, bytes = o_cov + sizeof(double) * D * D * (size_t)S;
+        if (bytes > h->clseg_cap) {
+            HIP_TRY(hipStreamSynchronize(st));
+            if (h->d_clseg) { (void)hipFree(h->d_clseg); h->d_clseg = nullptr; }
+            h->clseg_cap = 0;
+            HIP_TRY(hipMalloc(&h->d_clseg, 2 * bytes));
+            h->clseg_cap = 2 * bytes;
+        }
+        std::vector<char> tab(o_mean);
+        memcpy(tab.data(), segtab.data(), o_sc);
+        memcpy(tab.data() + o_sc, segsc.data(), o_mean - o_sc);
+        char* dseg = static_cast<char*>(h->d_clseg);
+        HIP_TRY(hipMemcpyAsync(dseg, tab.data(), tab.size(), hipMemcpyHostToDevice, st));
+        // (the global moments' scratch, mean and covariance are spent: their block holds runs_mom_cap scratches)
+        HIP_TRY(rvll::launch_moments_segs(d_surv, d_slot_sorted, reinterpret_cast<const long long*>(dseg),
+                                          reinterpret_cast<const double*>(dseg + o_sc), S, Di, d_part, (int)std::min<long long>(h->runs_mom_cap, 65535),
+                                          reinterpret_cast<double*>(dseg + o_mean), reinterpret_cast<double*>(dseg + o_cov), st));
+        HIP_TRY(hipMemcpyAsync(segcov.data(), dseg + o_cov, sizeof(double) * segcov.size(), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));               // sync 3
+    }
+    const auto t3 = std::chrono::steady_clock::now();
+    // 4. the factors of every run: the global one alone (one cluster), else one per cluster — its own or the global one
+    std::vector<std::vector<double>> fac((size_t)A);
+    for (int32_t a = 0; a < A; ++a) {
+        const size_t k = ncl[a] > 1 ? (size_t)ncl[a] : 1;
+        fac[(size_t)a].resize(D * D * k);
+        for (size_t c = 0; c < k; ++c) memcpy(fac[(size_t)a].data() + D * D * c, gfac.data() + D * D * (size_t)a, sizeof(double) * D * D);
+    }
+    for (int s = 0; s < S; ++s) {
+        const int32_t a = seg_of[(size_t)s].first, c = seg_of[(size_t)s].second;
+        if (!whitening_factor(segcov.data() + D * D * (size_t)s, D, fac[(size_t)a].data() + D * D * (size_t)c))
+            return report_error(RVLL_E_INVALID, "%s: the covariance of cluster %d of run %d is not positive definite", who, (int)c, (int)runs[a]);
+    }
+    // 5. the walker groups (nested.py's _walk_groups): per run, the non-empty clusters of the start rows in label order, walkers in
+    // their order inside a group; walk row e is walker perm[e] = a kdead + i
+    std::vector<int32_t> perm((size_t)K), grun((size_t)K), grid((size_t)K);
+    std::vector<double> glstar, gchol;
+    std::vector<uint64_t> gseed;
+    {
+        int64_t e = 0;
+        std::vector<int32_t> wc((size_t)kdead);
+        std::vector<long long> first;
+        for (int32_t a = 0; a < A; ++a) {
+            const size_t k = cnt[(size_t)a].size();
+            first.assign(k + 1, 0);
+            for (int64_t i = 0; i < kdead; ++i) {
+                wc[(size_t)i] = lab[a * m + ranks[(size_t)a * kdead + i]];
+                ++first[(size_t)wc[(size_t)i] + 1];
+            }
+            for (size_t c = 0; c < k; ++c) first[c + 1] += first[c];
+            std::vector<int32_t> gof(k, -1);             // group number of cluster c (-1: no walker starts in it)
+            for (size_t c = 0; c < k; ++c) {
+                if (first[c + 1] == first[c]) continue;
+                gof[c] = (int32_t)glstar.size();
+                glstar.push_back(lstar[a]);
+                gseed.push_back(c == 0 ? seeds[a] : seeds[a] + (uint64_t)c * 0xD1B54A32D192ED03ull);
+                gchol.insert(gchol.end(), fac[(size_t)a].begin() + D * D * c, fac[(size_t)a].begin() + D * D * (c + 1));
+            }
+            std::vector<long long> at(first.begin(), first.end() - 1);
+            for (int64_t i = 0; i < kdead; ++i) {
+                const size_t c = (size_t)wc[(size_t)i];
+                const long long r = at[c]++;
+                const int64_t row = e + r;
+                perm[(size_t)row] = (int32_t)((int64_t)a * kdead + i);
+                grun[(size_t)row] = gof[c];
+                grid[(size_t)row] = (int32_t)(r - first[c]);
+            }
+            e += kdead;
+        }
+    }
+    HIP_TRY(hipMemcpyAsync(d_rank, perm.data(), sizeof(int32_t) * (size_t)K, hipMemcpyHostToDevice, st));
+    HIP_TRY(rvll::launch_compose_index(d_start, 0, d_rank, K, d_gstart, st));
+    HIP_TRY(rvll::launch_compose_index(d_dying, 0, d_rank, K, d_gdying, st));
+    HIP_TRY(hipMemcpyAsync(h->d_walk_run, grun.data(), sizeof(int32_t) * (size_t)K, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(h->d_walk_wid, grid.data(), sizeof(int32_t) * (size_t)K, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(h->d_run_lstar, glstar.data(), sizeof(double) * glstar.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(h->d_run_seed, gseed.data(), sizeof(uint64_t) * gseed.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(h->d_run_chol, gchol.data(), sizeof(double) * gchol.size(), hipMemcpyHostToDevice, st));
+    // 6. one run-mode walk for every group of every run, the end points back to the dying rows
+    HIP_TRY(rvll::launch_gather_rows(h->d_live_u, d_gstart, K, Di, h->d_walk_u, st));
+    HIP_TRY(rvll::launch_gather_rows(h->d_live_theta, d_gstart, K, Di, h->d_walk_theta, st));
+    HIP_TRY(rvll::launch_gather_rows(h->d_live_logl, d_gstart, K, 1, h->d_walk_logl, st));
+    rc = walk_upload_frame(h, nullptr, wrapped);         // (synchronises: the host tables above may go out of scope after it)
+    if (rc) return rc;
+    RunWalk rw{grun.data(), grid.data(), std::vector<long long>((size_t)K, 0)};
+    rc = walk_core(h, K, 0., nsteps, max_rounds, 0, 0, nullptr, &rw);
+    if (rc) return rc;
+    HIP_TRY(rvll::launch_scatter_rows(h->d_walk_u, d_gdying, K, Di, h->d_live_u, st));
+    HIP_TRY(rvll::launch_scatter_rows(h->d_walk_theta, d_gdying, K, Di, h->d_live_theta, st));
+    HIP_TRY(rvll::launch_scatter_rows(h->d_walk_logl, d_gdying, K, 1, h->d_live_logl, st));
+    std::vector<double> wl((size_t)K);
+    HIP_TRY(hipMemcpyAsync(wl.data(), h->d_walk_logl, sizeof(double) * (size_t)K, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const auto t4 = std::chrono::steady_clock::now();
+    for (int64_t e = 0; e < K; ++e) {
+        logl_new[perm[(size_t)e]] = wl[(size_t)e];
+        if (ncalls) ncalls[perm[(size_t)e] / kdead] += rw.row_calls[(size_t)e];
+    }
+    for (int32_t a = 0; a < A; ++a) nclusters[a] = ncl[a];
+    h->cl_A = A;
+    h->cl_m = m;
+    h->cl_labels.assign(lab, lab + M);
+    h->cl_ncl.assign(ncl, ncl + A);
+    h->cl_scale = std::move(scale);
+    h->cl_factors = std::move(fac);
+    h->cl_phase_s[0] = std::chrono::duration<double>(t2 - t1).count();
+    h->cl_phase_s[1] = std::chrono::duration<double>(t3 - t2).count();
+    h->cl_phase_s[2] = std::chrono::duration<double>(t4 - t3).count();
+    for (int32_t a = 0; a < A; ++a) h->runs_dead[(size_t)runs[a]].emplace_back(h->dead_n + (long long)a * kdead, (long long)kdead);
+    h->dead_n += K;
+    return RVLL_OK;
+}
+
+int rvll_live_runs_clusters(rvll_handle* h, int32_t a, int64_t* nsurv, int32_t* nclusters, int32_t* labels, double* scale, double* factors,
+                            double* phase_s)
+{
+    if (!h) return report_error(RVLL_E_INVALID, "null handle");
+    if (h->cl_A < 1) return report_error(RVLL_E_INVALID, "rvll_live_runs_clusters: no rvll_live_runs_step_clustered since the live sets were loaded");
+    if (a < 0 || a >= h->cl_A) return report_error(RVLL_E_INVALID, "rvll_live_runs_clusters: listed run %d of %d", (int)a, (int)h->cl_A);
+    const size_t D = (size_t)h->L.ndim, m = (size_t)h->cl_m;
+    if (nsurv) *nsurv = (int64_t)m;
+    if (nclusters) *nclusters = h->cl_ncl[(size_t)a];
+    if (labels) memcpy(labels, h->cl_labels.data() + (size_t)a * m, sizeof(int32_t) * m);
+    if (scale) memcpy(scale, h->cl_scale.data() + (size_t)a * D, sizeof(double) * D);
+    if (factors) memcpy(factors, h->cl_factors[(size_t)a].data(), sizeof(double) * h->cl_factors[(size_t)a].size());
+    if (phase_s) for (int k = 0; k < 3; ++k) phase_s[k] = h->cl_phase_s[k];
     return RVLL_OK;
 }
 

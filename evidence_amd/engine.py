@@ -523,6 +523,51 @@ class GpuRVModel:
             _abi.as_dp(logl_new), _abi.as_dp(used) if used is not None else None))
         return (logl_new, ncalls, used) if return_chol else (logl_new, ncalls)
 
+    def live_runs_step_clustered(self, runs, kdead, ranks, lstar, wrapped=None, nsteps=10, max_rounds=200, seeds=(), nboot=30,
+                                 boot_seeds=()):
+        """live_runs_step with the survivors of every listed run clustered on the device (rvll_live_runs_step_clustered; DESIGN
+        §4e): run a's walkers are grouped by the cluster of their start row and whitened by that cluster's covariance, the
+        clustering bootstrapped with boot_seeds[a].  Returns (logl_new [A, kdead] in walker order, ncalls [A], nclusters [A])."""
+        runs = self._runs_list(runs)
+        kdead = int(kdead)
+        A = runs.size
+        ranks = np.ascontiguousarray(ranks, dtype=np.int32)
+        lstar = np.ascontiguousarray(lstar, dtype=np.float64).reshape(-1)
+        seeds = np.array([int(s) & (2 ** 64 - 1) for s in seeds], dtype=np.uint64)
+        boot_seeds = np.array([int(s) & (2 ** 64 - 1) for s in boot_seeds], dtype=np.uint64)
+        if ranks.shape != (A, kdead):
+            raise ValueError("ranks must be [runs, kdead]")
+        if lstar.shape != (A,) or seeds.shape != (A,) or boot_seeds.shape != (A,):
+            raise ValueError("lstar, seeds and boot_seeds need one entry per run")
+        wr = None if wrapped is None else np.ascontiguousarray(np.asarray(wrapped, dtype=bool).astype(np.int32))
+        logl_new = np.empty((A, kdead), dtype=np.float64)
+        ncalls = np.zeros(A, dtype=np.int64)
+        nclusters = np.zeros(A, dtype=np.int32)
+        _abi.check(self._lib.rvll_live_runs_step_clustered(
+            self._h, _abi.as_ip(runs), A, kdead, _abi.as_ip(ranks), _abi.as_dp(lstar), _abi.as_ip(wr) if wr is not None else None,
+            int(nsteps), int(max_rounds), seeds.ctypes.data_as(C.POINTER(C.c_uint64)), int(nboot),
+            boot_seeds.ctypes.data_as(C.POINTER(C.c_uint64)), ncalls.ctypes.data_as(C.POINTER(C.c_int64)), _abi.as_dp(logl_new),
+            _abi.as_ip(nclusters)))
+        return logl_new, ncalls, nclusters
+
+    def live_runs_clusters(self, a):
+        """What the last live_runs_step_clustered found for its listed run a (rvll_live_runs_clusters): (labels [n - kdead] of the
+        survivors in rank order, scale [ndim], factors [max(nclusters, 1), ndim, ndim] — the walk's factor of every cluster)."""
+        m, k = C.c_int64(0), C.c_int32(0)
+        _abi.check(self._lib.rvll_live_runs_clusters(self._h, int(a), C.byref(m), C.byref(k), None, None, None, None))
+        labels = np.empty(m.value, dtype=np.int32)
+        scale = np.empty(self.ndim)
+        factors = np.empty((max(k.value, 1), self.ndim, self.ndim))
+        _abi.check(self._lib.rvll_live_runs_clusters(self._h, int(a), None, None, _abi.as_ip(labels), _abi.as_dp(scale),
+                                                     _abi.as_dp(factors), None))
+        return labels, scale, factors
+
+    def live_runs_cluster_phases(self):
+        """Host seconds between the synchronisations of the last clustered step: {"cluster_s", "moments_s", "walk_s"}."""
+        ph = np.empty(3)
+        _abi.check(self._lib.rvll_live_runs_clusters(self._h, 0, None, None, None, None, None, _abi.as_dp(ph)))
+        return {"cluster_s": float(ph[0]), "moments_s": float(ph[1]), "walk_s": float(ph[2])}
+
     def live_runs_get(self, run, cube=True, theta=True, logl=True, theta_out=None):
         """(cube, theta, logl) of run `run`'s live set as it stands (None for the ones switched off); theta_out: a C-contiguous
         [n, ndim] float64 array (or view) to receive theta in place."""

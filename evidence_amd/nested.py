@@ -247,6 +247,19 @@ def _walk_groups(cw, factors, walk_seed):
             [walk_seed if c == 0 else (walk_seed + int(c) * _GROUP_MUL) & _M64 for c in groups])
 
 
+def _check_resident_clustering(live, clusterer, live_chol, nboot):
+    """The arguments that clustering=True with the resident live sets (live=) refuses."""
+    if not hasattr(live, "live_runs_step_clustered"):
+        raise ValueError("clustering=True with live= needs the resident ensemble's clustered step (GpuRVModel.live_runs_step_clustered)")
+    if clusterer is not None:
+        raise ValueError("clusterer= does not apply with live=: the resident live sets are clustered on the device")
+    if live_chol != "device":
+        raise ValueError('live_chol="host" does not work with clustering=True: the resident clustered step whitens on the device')
+    from .clustering import MAX_BOOT
+    if not 0 <= int(nboot) <= MAX_BOOT:
+        raise ValueError(f"nboot must be in [0, {MAX_BOOT}]")
+
+
 def _default_clusterer(clusterer):
     if clusterer is not None:
         return clusterer
@@ -290,12 +303,19 @@ def run_nested_slice(prior: Callable, loglike: Callable, ndim: int, nlive: Optio
     GpuRVModel.cluster_runs) and whitens every walker's directions with the covariance of the cluster its start row is in.
     The draws of the run's generator are those of clustering=False, so a run that finds one cluster every iteration is the
     unclustered run bit for bit.  `walker_runs` (GpuRVModel.slice_walk_runs) then walks the walkers grouped by cluster in
-    one call; `walker` has a single factor and cannot be combined with clustering, nor can the resident live set."""
+    one call; `walker` has a single factor and cannot be combined with clustering.
+
+    With `live` as well, the clustering runs on the device (GpuRVModel.live_runs_step_clustered): the run is the
+    one-run resident ENSEMBLE, run_nested_ensemble(None, None, ndim, [seed], live=live, clustering=True, ...)[0], with the
+    ensemble's draws, results and `timing` keys; the model is left holding that ensemble (live_runs_*), not a one-run live set.
+    `clusterer` (the device clusters) and live_chol="host" (the device whitens) are refused then."""
     if clustering and walker is not None:
         raise ValueError("walker= has one whitening factor for all walkers: with clustering=True pass walker_runs= "
                          "(GpuRVModel.slice_walk_runs)")
     if clustering and live is not None:
-        raise ValueError("clustering=True does not work with the resident live set (live=)")
+        _check_resident_clustering(live, clusterer, live_chol, nboot)
+        return _ensemble_resident(live, ndim, [int(seed)], nlive, kbatch, nsteps, dlogz, max_iter, max_calls, wrapped,
+                                  clustering=True, nboot=nboot)[0]
     if walker is not None and walker_runs is not None:
         raise ValueError("pass walker= or walker_runs=, not both")
     if clustering:
@@ -511,16 +531,20 @@ def run_nested_ensemble(prior: Callable, loglike: Callable, ndim: int, seeds, nl
     and `walker_runs` are unused and may be None.  result[r] is then run_nested_slice(None, None, ndim, seed=seeds[r],
     live=<a model of that run alone>, same settings) bit for bit, and its timing holds its share of the host seconds of each
     turn (sort, draws, evidence sums), the seconds of the shared step calls it took part in, and their number.  Not with
-    clustering=True nor walker_runs."""
+    walker_runs.  With clustering=True every step clusters the survivors of every running run on the device
+    (GpuRVModel.live_runs_step_clustered): the runs' draws are those of the unclustered ensemble, the bootstrap seed
+    of a run's iteration is the host clustered path's, and result[r] is run_nested_slice(None, None, ndim, seed=seeds[r],
+    live=..., clustering=True), with `nclusters`; `clusterer` is refused (the device clusters)."""
     seeds = [int(s) for s in seeds]
     if not seeds:
         raise ValueError("need at least one seed")
     if live is not None:
         if clustering:
-            raise ValueError("clustering=True does not work with the resident live sets (live=)")
+            _check_resident_clustering(live, clusterer, "device", nboot)
         if walker_runs is not None:
             raise ValueError("pass walker_runs= or live=, not both")
-        return _ensemble_resident(live, ndim, seeds, nlive, kbatch, nsteps, dlogz, max_iter, max_calls, wrapped)
+        return _ensemble_resident(live, ndim, seeds, nlive, kbatch, nsteps, dlogz, max_iter, max_calls, wrapped,
+                                  clustering=clustering, nboot=nboot)
     if walker_runs is None:
         raise ValueError("walker_runs is required (GpuRVModel.slice_walk_runs)")
     if clustering:
@@ -627,9 +651,11 @@ def _cluster_turn(turn, clusterer, wrapped, nboot):
     return out
 
 
-def _ensemble_resident(live, ndim, seeds, nlive, kbatch, nsteps, dlogz, max_iter, max_calls, wrapped):
+def _ensemble_resident(live, ndim, seeds, nlive, kbatch, nsteps, dlogz, max_iter, max_calls, wrapped, clustering=False, nboot=30):
     """run_nested_ensemble(live=model): the device_order branch of run_nested_slice for every seed, the runs' live sets resident
-    side by side (run r = rows r nlive .. r nlive + nlive - 1 of the ensemble), their bookkeeping vectorised across runs."""
+    side by side (run r = rows r nlive .. r nlive + nlive - 1 of the ensemble), their bookkeeping vectorised across runs.
+    clustering: the clustered step, with run r's bootstrap seed (seeds[r] _BOOT_MUL + deaths after this iteration) mod 2^64 —
+    what run_nested_slice's host clustered path passes."""
     defaults = ultranest_defaults(ndim)
     nlive = int(nlive or defaults["nlive"])
     kbatch = int(kbatch or max(1, nlive // 4))
@@ -645,6 +671,7 @@ def _ensemble_resident(live, ndim, seeds, nlive, kbatch, nsteps, dlogz, max_iter
     logx_run, niter = np.zeros(R), np.zeros(R, dtype=np.int64)
     done = np.zeros(R, dtype=bool)
     timing = [{"host_s": 0.0, "walk_s": 0.0, "turns": 0} for _ in range(R)]
+    ncls = [[] for _ in range(R)]
     stop_gap = np.log(np.expm1(dlogz))
     it, logx = 0, 0.0                               # every running run is at the same iteration
     turns = []                                      # (runs, dying log-L [A, kbatch], their log-weights) of every turn
@@ -660,7 +687,13 @@ def _ensemble_resident(live, ndim, seeds, nlive, kbatch, nsteps, dlogz, max_iter
             ranks[j] = rngs[r].integers(0, nlive - kbatch, kbatch)
             walk_seeds.append(int(rngs[r].integers(0, 2 ** 62)))
         t1 = time.perf_counter()
-        wl, used = live.live_runs_step(act, kbatch, ranks, lstar, wrapped, nsteps, 200, walk_seeds)
+        if clustering:
+            boot = [(seeds[r] * _BOOT_MUL + it + kbatch) & _M64 for r in act]
+            wl, used, ncl = live.live_runs_step_clustered(act, kbatch, ranks, lstar, wrapped, nsteps, 200, walk_seeds, nboot, boot)
+            for j, r in enumerate(act):
+                ncls[r].append(int(ncl[j]))
+        else:
+            wl, used = live.live_runs_step(act, kbatch, ranks, lstar, wrapped, nsteps, 200, walk_seeds)
         t2 = time.perf_counter()
         logw, logz[act], h[act], logx = _deaths_runs(logz[act], h[act], logx, dl, nlive, kbatch)
         turns.append((act, dl, logw))
@@ -692,5 +725,6 @@ def _ensemble_resident(live, ndim, seeds, nlive, kbatch, nsteps, dlogz, max_iter
         all_logl = np.concatenate(dead_logl[r] + [logl])
         all_logw = np.concatenate(dead_logw[r] + [logw_live]) - logz_final
         out.append(NestedResult(float(logz_final), float(np.sqrt(max(h[r], 0.0) / nlive)), int(niter[r]), int(ncall[r]), float(h[r]),
-                                all_theta, all_logl, all_logw, timing[r], None))
+                                all_theta, all_logl, all_logw, timing[r],
+                                np.array(ncls[r], dtype=np.int64) if clustering else None))
     return out

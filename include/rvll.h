@@ -51,10 +51,11 @@ extern "C" {
 #endif
 
 #define RVLL_VERSION_MAJOR 0
-#define RVLL_VERSION_MINOR 5   /* 0.2: rvll_slice_walk takes walker_base; RVLL_FLAG_WANDERED; resident live set
+#define RVLL_VERSION_MINOR 6   /* 0.2: rvll_slice_walk takes walker_base; RVLL_FLAG_WANDERED; resident live set
                                   0.3: rvll_slice_walk_runs
                                   0.4: rvll_cluster_runs
-                                  0.5: rvll_live_runs_* (resident ensemble) */
+                                  0.5: rvll_live_runs_* (resident ensemble)
+                                  0.6: rvll_live_runs_step_clustered, rvll_live_runs_clusters */
 
 /* ---- error codes ------------------------------------------------------ */
 #define RVLL_OK             0
@@ -363,6 +364,38 @@ int rvll_live_runs_step(rvll_handle* h, const int32_t* runs /*[A]*/, int32_t A, 
                         double* chol_out /*[A, ndim, ndim] or NULL*/);
 int rvll_live_runs_get(rvll_handle* h, int32_t run, double* cube, double* theta, double* logl);
 int rvll_live_runs_dead(rvll_handle* h, int32_t run, int64_t* n_dead, double* theta, double* logl);
+/* The clustered step of the resident ensemble (nested.run_nested_ensemble(..., live=model, clustering=True)).  It
+ * follows a rvll_live_runs_sort of the same runs and kdead, takes the arguments of rvll_live_runs_step and makes its checks, and
+ * for listed run a, with m = n - kdead survivors (the run's ranks kdead .. n - 1 of the sort):
+ *   1. the global covariance and whitening factor exactly as rvll_live_runs_step;
+ *   2. the metric scale[d] = 1 / sqrt(cov[d, d] + 1e-14), in double on the host;
+ *   3. the survivors, in rank order, clustered as rvll_cluster_runs does with that scale, `wrapped`, nboot (0 .. 32) and
+ *      boot_seeds[a] (labels and nclusters[a] bit for bit those of evidence_amd/clustering.py);
+ *   4. with nclusters[a] > 1, every cluster of at least 2 ndim rows whitened by the factor of its own rows' covariance (those rows
+ *      in rank order, summed as rvll_live_step sums them), every other cluster by the run's global factor;
+ *   5. walker i (start rank ranks[a, i]) walks in the group of its start row's cluster: the groups in label order, walkers in
+ *      their order inside a group, group c with seed seeds[a] (c = 0) or seeds[a] + c * 0xD1B54A32D192ED03 (mod 2^64), its
+ *      cluster's factor and lstar[a], walker j of a group being row j of its run in the run-mode walk — the end points are those
+ *      of rvll_slice_walk_runs on the same start rows, groups, factors and seeds;
+ *   6. walker i's end point replaces dying row i as in rvll_live_runs_step; logl_new [A, kdead] is in walker order, ncalls [A] (may
+ *      be NULL) sums the run's groups, nclusters [A] out.
+ * A failed step leaves every run as it was.  All device work: the survivors packed by one gather, the clustering on them, one
+ * segmented radix sort for every run's (label, rank) order, one segmented moments pass over all (run, cluster) segments, one walk.
+ * Host synchronisations before the walk: 3 (global covariances, labels, cluster covariances — the last only when some run has
+ * a cluster of its own factor); rvll_live_runs_step makes 1.  RVLL_E_UNSUPPORTED: ndim above 64.
+ *
+ * rvll_live_runs_clusters  what the last successful clustered step found for its listed run a (0 .. A - 1): *nsurv = m,
+ *                          *nclusters, labels [m] of the survivors in rank order, scale [ndim], factors [max(nclusters, 1),
+ *                          ndim, ndim] (the walk's factor of every cluster; the global one alone when there is one cluster),
+ *                          phase_s [3]: host seconds between the step's synchronisations — clustering and label sort, cluster
+ *                          moments, walk.  Any pointer may be NULL.  RVLL_E_INVALID: no clustered step since the live sets
+ *                          were loaded, or a out of range.                                                                     */
+int rvll_live_runs_step_clustered(rvll_handle* h, const int32_t* runs /*[A]*/, int32_t A, int64_t kdead, const int32_t* ranks /*[A, kdead]*/,
+                                  const double* lstar /*[A]*/, const int32_t* wrapped /*[ndim] or NULL*/, int32_t nsteps,
+                                  int32_t max_rounds, const uint64_t* seeds /*[A]*/, int32_t nboot, const uint64_t* boot_seeds /*[A]*/,
+                                  int64_t* ncalls /*[A] or NULL*/, double* logl_new /*[A, kdead]*/, int32_t* nclusters /*[A]*/);
+int rvll_live_runs_clusters(rvll_handle* h, int32_t a, int64_t* nsurv, int32_t* nclusters, int32_t* labels /*[m]*/,
+                            double* scale /*[ndim]*/, double* factors /*[max(nclusters, 1), ndim, ndim]*/, double* phase_s /*[3]*/);
 
 /* ---- scalar-callback latency ------------------------------------------------------------------------- */
 /* PolyChord's loglike(theta) is irreducibly scalar (evidence/polychord/__init__.py:166-171): one theta per call.
