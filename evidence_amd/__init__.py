@@ -13,8 +13,10 @@ from .layout import ModelLayout, compile_layout
 from .priors import PriorError, PriorSpec, prior_constructor
 from .engine import GpuRVModel
 from .nested import run_nested_ensemble
+from . import shrinkage
+from .shrinkage import logz_error, replicates
 
 __all__ = ["GpuRVModel", "EpochTable", "ModelLayout", "compile_layout", "PriorSpec", "PriorError",
            "prior_constructor", "RvllError", "RvllLibraryError", "FLAG_INVALID_ORBIT", "FLAG_NONCONVERGED",
-           "FLAG_WANDERED", "run_nested_ensemble"]
+           "FLAG_WANDERED", "run_nested_ensemble", "shrinkage", "replicates", "logz_error"]
 __version__ = "0.1.0"

@@ -19,7 +19,7 @@ ERROR_NAMES = {
 FLAG_INVALID_ORBIT = 1
 FLAG_NONCONVERGED = 2
 FLAG_WANDERED = 4                  # a Kepler solve took > 8 Newton steps: log-L there is conditioned to ~1e-9 (rvll.h)
-ABI_VERSION = (0, 6)               # RVLL_VERSION_MAJOR / MINOR these bindings were written against
+ABI_VERSION = (0, 7)               # RVLL_VERSION_MAJOR / MINOR these bindings were written against
 
 K_K1, K_LOGK1 = 0, 1
 P_PERIOD, P_LOGPERIOD = 0, 1
@@ -85,6 +85,12 @@ class FipTiming(C.Structure):
                 ("repeats", C.c_int32), ("reserved", C.c_int32)]
 
 
+class ShrinkTiming(C.Structure):
+    _fields_ = [("kernel_ms", C.c_double), ("total_ms", C.c_double), ("elements", C.c_int64), ("launches", C.c_int32),
+                ("threads", C.c_int32)]
+
+
+SHRINK_RANDOM, SHRINK_EXPECTED = 0, 1
 FIP_MAX_PLANETS = 8
 Handle = C.c_void_p
 _dp = C.POINTER(C.c_double)
@@ -158,6 +164,9 @@ PROTOTYPES = {
     "rvll_kep_rv_batch": (C.c_int, [Handle, _dp, C.c_int64, _dp, C.c_int32, C.c_uint32, _dp]),
     "rvll_fip_accumulate": (C.c_int, [C.c_int32, _dp, _dp, C.c_int32, _dp, _dp, C.POINTER(C.c_int64), C.c_int32,
                                       C.c_int32, _dp, C.c_int32, C.POINTER(FipTiming)]),
+    "rvll_shrinkage_replicates": (C.c_int, [C.c_int32, _dp, C.c_int64, C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_int64),
+                                            _ip, _ip, C.POINTER(C.c_uint64), C.c_int32, C.c_int32, _dp, _dp, _dp, C.c_int64,
+                                            C.POINTER(ShrinkTiming)]),
     "rvll_dev_trace_loglike": (C.c_int, [Handle, C.c_int64, C.c_int32, C.POINTER(C.c_uint64), C.c_int64, _ip, _ip]),
     "rvll_debug_eval": (C.c_int, [Handle, C.c_int32, _dp, _dp, C.c_int64, _dp]),
     "rvll_last_error": (C.c_char_p, []),

@@ -32,6 +32,8 @@ class NestedResult:
     logwt: np.ndarray            # log posterior weights (normalised)
     timing: dict = None          # resident live set: seconds in the order step, waiting for the live step, and the loop turns
     nclusters: np.ndarray = None  # clustering=True: the clusters of the survivors, one entry per iteration (None when off)
+    nlive: int = None            # the schedule the run died by (shrinkage.replicates reads it): nlive live points,
+    kbatch: int = None           # kbatch deaths per iteration (run_nested: 1)
 
 
 def _logaddexp_many(x):
@@ -128,7 +130,7 @@ def run_nested(prior: Callable, loglike: Callable, ndim: int, nlive: Optional[in
     all_logl = np.concatenate([dead_logl, logl])
     all_logw = np.concatenate([dead_logw, logw_live]) - logz_final
     return NestedResult(float(logz_final), float(np.sqrt(max(h, 0.0) / nlive)), it, ncall, float(h),
-                        all_theta, all_logl, all_logw)
+                        all_theta, all_logl, all_logw, nlive=nlive, kbatch=1)
 
 
 # --------------------------------------------------------------------------------------------------
@@ -480,7 +482,8 @@ def run_nested_slice(prior: Callable, loglike: Callable, ndim: int, nlive: Optio
     all_logl = np.concatenate(dead_logl + [logl])
     all_logw = np.concatenate(dead_logw + [logw_live]) - logz_final
     return NestedResult(float(logz_final), float(np.sqrt(max(h, 0.0) / nlive)), it, ncall, float(h),
-                        all_theta, all_logl, all_logw, timing, None if nclusters is None else np.array(nclusters, dtype=np.int64))
+                        all_theta, all_logl, all_logw, timing, None if nclusters is None else np.array(nclusters, dtype=np.int64),
+                        nlive=nlive, kbatch=kbatch)
 
 
 class _EnsembleRun:
@@ -624,7 +627,7 @@ def run_nested_ensemble(prior: Callable, loglike: Callable, ndim: int, seeds, nl
         all_logw = np.concatenate(r.dead_logw + [logw_live]) - logz_final
         out.append(NestedResult(float(logz_final), float(np.sqrt(max(r.h, 0.0) / nlive)), r.it, r.ncall, float(r.h),
                                 all_theta, all_logl, all_logw, r.timing,
-                                np.array(r.nclusters, dtype=np.int64) if clustering else None))
+                                np.array(r.nclusters, dtype=np.int64) if clustering else None, nlive=nlive, kbatch=kbatch))
     return out
 
 
@@ -726,5 +729,5 @@ def _ensemble_resident(live, ndim, seeds, nlive, kbatch, nsteps, dlogz, max_iter
         all_logw = np.concatenate(dead_logw[r] + [logw_live]) - logz_final
         out.append(NestedResult(float(logz_final), float(np.sqrt(max(h[r], 0.0) / nlive)), int(niter[r]), int(ncall[r]), float(h[r]),
                                 all_theta, all_logl, all_logw, timing[r],
-                                np.array(ncls[r], dtype=np.int64) if clustering else None))
+                                np.array(ncls[r], dtype=np.int64) if clustering else None, nlive=nlive, kbatch=kbatch))
     return out

@@ -51,11 +51,12 @@ extern "C" {
 #endif
 
 #define RVLL_VERSION_MAJOR 0
-#define RVLL_VERSION_MINOR 6   /* 0.2: rvll_slice_walk takes walker_base; RVLL_FLAG_WANDERED; resident live set
+#define RVLL_VERSION_MINOR 7   /* 0.2: rvll_slice_walk takes walker_base; RVLL_FLAG_WANDERED; resident live set
                                   0.3: rvll_slice_walk_runs
                                   0.4: rvll_cluster_runs
                                   0.5: rvll_live_runs_* (resident ensemble)
-                                  0.6: rvll_live_runs_step_clustered, rvll_live_runs_clusters */
+                                  0.6: rvll_live_runs_step_clustered, rvll_live_runs_clusters
+                                  0.7: rvll_shrinkage_replicates */
 
 /* ---- error codes ------------------------------------------------------ */
 #define RVLL_OK             0
@@ -525,6 +526,36 @@ int rvll_fip_accumulate(int32_t device, const double* nua, const double* nub, in
                         const double* periods /*[rows, np_max]*/, const double* contrib /*[rows]*/,
                         const int64_t* run_start /*[n_runs + 1]*/, int32_t n_runs, int32_t np_max,
                         double* fapnu /*[n_runs, nfreq] in/out*/, int32_t repeats, rvll_fip_timing* timing);
+
+/* ---- simulated shrinkage of finished runs (post-processing; independent of any model handle) ---------- */
+/* Replicates of ln Z, the information H and the posterior weights of R finished nested-sampling runs, each death's prior
+ * shrinkage redrawn (Skilling 2006; Higson et al. 2018).  evidence_amd/shrinkage.py is the definition.
+ * Rows run_start[r] .. run_start[r+1] of logl (n_rows in all) are run r: n_dead[r] dead points in death order, then its
+ * m = rows - n_dead[r] >= 1 final live points.  Death j of run r dies with n_j = nlive[r] - (j mod kbatch[r]) live points and
+ * shrinks the prior volume by log t_j = log(1 - uniform01(seed, j)) / n_j, seed = seeds[r] + s * 0xD1B54A32D192ED03 for
+ * replicate s (RVLL_SHRINK_EXPECTED: log t_j = -1 / n_j).  logX_j = logX_{j-1} + log t_j from 0; a dead row weighs
+ * logl_j + logX_{j-1} + log(-expm1(log t_j)), a live row logX_last - log(m) + logl_i.  Out: logz[r * nsamples + s] =
+ * logsumexp of every row, info[r * nsamples + s] = the dead rows' information (sum w logl / Zd - ln Zd; 0 without weight),
+ * and, if logwt is not NULL, logwt[nsamples * run_start[r] + s * rows + i] = weight - ln Z (the caller's buffer of
+ * nsamples * n_rows doubles).  The weights go through a device block of at most block_bytes (0: 512 MiB), some replicates of
+ * every run at a time; RVLL_E_NOMEM, before any work, when one replicate of all runs does not fit.  RVLL_E_INVALID for a
+ * run_start that does not rise from 0 to n_rows, n_dead < 0, kbatch < 1, kbatch >= nlive, n_dead % kbatch != 0, m < 1,
+ * nsamples < 1 and negative sizes.  A (run, replicate)'s results do not depend on the other runs of the call.  timing may be
+ * NULL.  device < 0 uses the current device.                                                                         */
+#define RVLL_SHRINK_RANDOM 0
+#define RVLL_SHRINK_EXPECTED 1
+typedef struct rvll_shrink_timing {
+    double  kernel_ms;       /* HIP-event time of the replicate kernels, summed over the launches */
+    double  total_ms;        /* the whole call: allocation, uploads, kernels, downloads           */
+    int64_t elements;        /* (row, replicate) pairs: n_rows * nsamples                          */
+    int32_t launches;
+    int32_t threads;         /* per workgroup; one workgroup per (run, replicate)                  */
+} rvll_shrink_timing;
+int rvll_shrinkage_replicates(int32_t device, const double* logl, int64_t n_rows, const int64_t* run_start /*[n_runs + 1]*/,
+                              int32_t n_runs, const int64_t* n_dead, const int32_t* nlive, const int32_t* kbatch,
+                              const uint64_t* seeds, int32_t nsamples, int32_t mode, double* logz /*[n_runs, nsamples]*/,
+                              double* info /*[n_runs, nsamples]*/, double* logwt /*NULL or [nsamples * n_rows]*/,
+                              int64_t block_bytes, rvll_shrink_timing* timing);
 
 /* ---- diagnostics -------------------------------------------------------------- */
 /* Evaluate one device math routine elementwise (tests only; no reference counterpart):
