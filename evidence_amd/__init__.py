@@ -14,9 +14,10 @@ from .priors import PriorError, PriorSpec, prior_constructor
 from .engine import GpuRVModel
 from .nested import run_nested_ensemble
 from . import shrinkage
+from . import insertion
 from .shrinkage import logz_error, replicates
 
 __all__ = ["GpuRVModel", "EpochTable", "ModelLayout", "compile_layout", "PriorSpec", "PriorError",
            "prior_constructor", "RvllError", "RvllLibraryError", "FLAG_INVALID_ORBIT", "FLAG_NONCONVERGED",
-           "FLAG_WANDERED", "run_nested_ensemble", "shrinkage", "replicates", "logz_error"]
+           "FLAG_WANDERED", "run_nested_ensemble", "shrinkage", "replicates", "logz_error", "insertion"]
 __version__ = "0.1.0"

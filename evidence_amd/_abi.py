@@ -19,7 +19,7 @@ ERROR_NAMES = {
 FLAG_INVALID_ORBIT = 1
 FLAG_NONCONVERGED = 2
 FLAG_WANDERED = 4                  # a Kepler solve took > 8 Newton steps: log-L there is conditioned to ~1e-9 (rvll.h)
-ABI_VERSION = (0, 7)               # RVLL_VERSION_MAJOR / MINOR these bindings were written against
+ABI_VERSION = (0, 8)               # RVLL_VERSION_MAJOR / MINOR these bindings were written against
 
 K_K1, K_LOGK1 = 0, 1
 P_PERIOD, P_LOGPERIOD = 0, 1
@@ -90,6 +90,11 @@ class ShrinkTiming(C.Structure):
                 ("threads", C.c_int32)]
 
 
+class InsertionTiming(C.Structure):
+    _fields_ = [("kernel_ms", C.c_double), ("total_ms", C.c_double), ("rows", C.c_int64), ("launches", C.c_int32),
+                ("threads", C.c_int32)]
+
+
 SHRINK_RANDOM, SHRINK_EXPECTED = 0, 1
 FIP_MAX_PLANETS = 8
 Handle = C.c_void_p
@@ -125,6 +130,8 @@ PROTOTYPES = {
                                                 C.POINTER(C.c_uint64), C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_int64),
                                                 _dp, _ip]),
     "rvll_live_runs_clusters": (C.c_int, [Handle, C.c_int32, C.POINTER(C.c_int64), _ip, _ip, _dp, _dp, _dp]),
+    "rvll_live_births": (C.c_int, [Handle, C.POINTER(C.c_int64), _dp, _dp]),
+    "rvll_live_runs_births": (C.c_int, [Handle, C.c_int32, C.POINTER(C.c_int64), _dp, _dp]),
     "rvll_scalar_server": (C.c_int, [Handle, C.c_int32]),
     "rvll_loglike_batch": (C.c_int, [Handle, _dp, C.c_int64, _dp, _ip]),
     "rvll_prior_batch": (C.c_int, [Handle, _dp, C.c_int64, _dp]),
@@ -167,6 +174,8 @@ PROTOTYPES = {
     "rvll_shrinkage_replicates": (C.c_int, [C.c_int32, _dp, C.c_int64, C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_int64),
                                             _ip, _ip, C.POINTER(C.c_uint64), C.c_int32, C.c_int32, _dp, _dp, _dp, C.c_int64,
                                             C.POINTER(ShrinkTiming)]),
+    "rvll_insertion_indexes": (C.c_int, [C.c_int32, _dp, _dp, C.c_int64, C.POINTER(C.c_int64), C.c_int32, _ip, _ip,
+                                         C.POINTER(InsertionTiming)]),
     "rvll_dev_trace_loglike": (C.c_int, [Handle, C.c_int64, C.c_int32, C.POINTER(C.c_uint64), C.c_int64, _ip, _ip]),
     "rvll_debug_eval": (C.c_int, [Handle, C.c_int32, _dp, _dp, C.c_int64, _dp]),
     "rvll_last_error": (C.c_char_p, []),

@@ -170,6 +170,7 @@ struct rvll_handle {
     // device-resident live set (rvll_live_*): nested sampling's live points, and the points that died, stay in HBM
     long long live_n = 0, live_cap = 0;
     double *d_live_u = nullptr, *d_live_theta = nullptr, *d_live_logl = nullptr;
+    double* d_live_birth = nullptr;             // [live_cap] every live row's birth contour: -inf from the load, else the lstar it was drawn above
     int32_t* d_live_idx = nullptr;              // [2 * live_cap] order, then start rows, of the current step
     double *d_live_mom = nullptr;               // scratch, mean, covariance of the whitening
     // the order on the device (rvll_live_sort): keys in / out, rows in (the order itself lands in d_live_idx), rocPRIM's scratch
@@ -180,7 +181,7 @@ struct rvll_handle {
     long long sorted_kdead = -1;                // kdead of the rvll_live_sort whose order d_live_idx holds (-1: none, or used up)
     double sorted_lstar = 0.;
     long long dead_n = 0, dead_cap = 0;
-    double *d_dead_theta = nullptr, *d_dead_logl = nullptr;
+    double *d_dead_theta = nullptr, *d_dead_logl = nullptr, *d_dead_birth = nullptr;   // [dead_cap, ndim], [dead_cap] x 2
     // the resident ensemble (rvll_live_runs_*): R live sets of n rows in d_live_u / _theta / _logl (run r = rows r n .. r n + n - 1;
     // live_n is 0 meanwhile, so the one-run calls refuse them, and rvll_live_init sets runs_R to 0); the dead store holds the dying
     // rows of every step in one block of A kdead rows, run a's kdead at a kdead, and runs_dead[r] lists run r's pieces in death order

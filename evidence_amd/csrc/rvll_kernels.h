@@ -269,6 +269,12 @@ hipError_t launch_label_sort(const int32_t* labels, int32_t* labels_out, const i
                              const int32_t* seg, void* temp, size_t temp_bytes, hipStream_t st);
 hipError_t launch_moments_segs(const double* u, const int32_t* idx, const long long* seg, const double* sc, int S, int D, double* scratch,
                                int chunk, double* mean, double* cov, hipStream_t st);
+// birth contours of the resident rows: p[0 .. n) = v (the births of a freshly loaded live set: -inf); and a step's births in one
+// launch — dying row dying[e] (e < K, distinct rows) hands its birth to dead_birth[e] and is born again at lstar_at[(e / kdead)
+// kdead] (lstar_at != null: its run's highest dying log-L, where the dead store holds it) or at lstar
+hipError_t launch_fill(double* p, long long n, double v, hipStream_t st);
+hipError_t launch_births_step(const int32_t* dying, long long K, long long kdead, const double* lstar_at, double lstar, double* live_birth,
+                              double* dead_birth, hipStream_t st);
 
 // ---- scalar-call server: a one-workgroup persistent kernel that answers single-point log-L requests through a
 // block of host-coherent pinned memory, so a scalar callback costs a PCIe round trip instead of a kernel launch

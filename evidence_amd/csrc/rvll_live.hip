@@ -252,6 +252,25 @@ void runs_survivors_kernel(const double* u, const int32_t* order, int A, long lo
     }
 }
 
+__global__ __launch_bounds__(kThreads)
+void fill_kernel(double* p, long long n, double v)
+{
+    for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < n; i += (long long)gridDim.x * kThreads) p[i] = v;
+}
+
+// a step's births: walker e's dying row hands its birth to the dead store (slot e, where its theta and log-L went) and takes its
+// run's lstar.  One thread reads and then writes its own row: the rows are distinct, so nothing races.
+__global__ __launch_bounds__(kThreads)
+void births_step_kernel(const int32_t* dying, long long K, long long kdead, const double* lstar_at, double lstar, double* live_birth,
+                        double* dead_birth)
+{
+    for (long long e = (long long)blockIdx.x * kThreads + threadIdx.x; e < K; e += (long long)gridDim.x * kThreads) {
+        const int32_t r = dying[e];
+        dead_birth[e] = live_birth[r];
+        live_birth[r] = lstar_at ? lstar_at[(e / kdead) * kdead] : lstar;
+    }
+}
+
 int blocks_for(long long total)
 {
     long long b = (total + kThreads - 1) / kThreads;
@@ -439,6 +458,23 @@ hipError_t launch_moments_segs(const double* u, const int32_t* idx, const long l
         hipLaunchKernelGGL(moments_fold_kernel<true>, dim3((D * D + kFoldCols - 1) / kFoldCols, ns), dim3(kThreads), 0, st, scratch,
                            D * D, 0.0, c, ps, (long long)D * D, sc + 1, (long long)s0);
     }
+    return hipGetLastError();
+}
+
+// ---- birth contours (rvll_live_births, rvll_live_runs_births) -----------------------------------------------------------------
+hipError_t launch_fill(double* p, long long n, double v, hipStream_t st)
+{
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(fill_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, st, p, n, v);
+    return hipGetLastError();
+}
+
+hipError_t launch_births_step(const int32_t* dying, long long K, long long kdead, const double* lstar_at, double lstar, double* live_birth,
+                              double* dead_birth, hipStream_t st)
+{
+    if (K <= 0 || kdead <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(births_step_kernel, dim3(blocks_for(K)), dim3(kThreads), 0, st, dying, K, kdead, lstar_at, lstar, live_birth,
+                       dead_birth);
     return hipGetLastError();
 }
 

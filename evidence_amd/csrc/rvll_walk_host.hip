@@ -120,26 +120,28 @@ int dead_reserve(rvll_handle* h, long long add, long long grow, const char* who)
     const size_t D = (size_t)h->L.ndim;
     hipStream_t st = h->compute;
     const long long cap = std::max<long long>(2 * h->dead_cap, h->dead_n + 4 * grow);
-    double *nt = nullptr, *nl = nullptr;
+    double *nt = nullptr, *nl = nullptr, *nb = nullptr;
     HIP_TRY(hipMalloc(&nt, sizeof(double) * D * (size_t)cap));
     {
-        const hipError_t e = hipMalloc(&nl, sizeof(double) * (size_t)cap);
+        hipError_t e = hipMalloc(&nl, sizeof(double) * (size_t)cap);
+        if (e == hipSuccess) e = hipMalloc(&nb, sizeof(double) * (size_t)cap);
         if (e != hipSuccess) {
-            (void)hipFree(nt);
+            (void)hipFree(nt); if (nl) (void)hipFree(nl);
             return report_error(e == hipErrorOutOfMemory ? RVLL_E_NOMEM : RVLL_E_HIP, "%s: dead store: %s", who, hipGetErrorString(e));
         }
     }
     if (h->dead_n) {
         hipError_t e = hipMemcpyAsync(nt, h->d_dead_theta, sizeof(double) * D * (size_t)h->dead_n, hipMemcpyDeviceToDevice, st);
         if (e == hipSuccess) e = hipMemcpyAsync(nl, h->d_dead_logl, sizeof(double) * (size_t)h->dead_n, hipMemcpyDeviceToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(nb, h->d_dead_birth, sizeof(double) * (size_t)h->dead_n, hipMemcpyDeviceToDevice, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
         if (e != hipSuccess) {
-            (void)hipFree(nt); (void)hipFree(nl);
+            (void)hipFree(nt); (void)hipFree(nl); (void)hipFree(nb);
             return report_error(RVLL_E_HIP, "%s: dead store: %s", who, hipGetErrorString(e));
         }
     }
-    dev_free(h->d_dead_theta); dev_free(h->d_dead_logl);
-    h->d_dead_theta = nt; h->d_dead_logl = nl; h->dead_cap = cap;
+    dev_free(h->d_dead_theta); dev_free(h->d_dead_logl); dev_free(h->d_dead_birth);
+    h->d_dead_theta = nt; h->d_dead_logl = nl; h->d_dead_birth = nb; h->dead_cap = cap;
     return RVLL_OK;
 }
 
@@ -858,7 +860,8 @@ int walk_upload_frame(rvll_handle* h, const double* chol, const int32_t* wrapped
     return RVLL_OK;
 }
 
-// N unit-cube rows -> prior transform -> log-L into the resident live buffers d_live_u / _theta / _logl (grown on demand);
+// N unit-cube rows -> prior transform -> log-L into the resident live buffers d_live_u / _theta / _logl (grown on demand), births
+// -inf;
 // logl_out [N] may be NULL.  Shared by the one-run live set and the ensemble; the caller keeps the state.
 int live_load(rvll_handle* h, const double* cube, int64_t N, double* logl_out)
 {
@@ -872,12 +875,13 @@ int live_load(rvll_handle* h, const double* cube, int64_t N, double* logl_out)
     rc = use_device(h);                                  // (elements the table-only prior stage handed over are redone here)
     if (rc) return rc;
     if (N > h->live_cap) {
-        dev_free(h->d_live_u); dev_free(h->d_live_theta); dev_free(h->d_live_logl); dev_free(h->d_live_idx);
+        dev_free(h->d_live_u); dev_free(h->d_live_theta); dev_free(h->d_live_logl); dev_free(h->d_live_birth); dev_free(h->d_live_idx);
         dev_free(h->d_sort_keys); dev_free(h->d_sort_rows);
         h->live_cap = 0;
         HIP_TRY(hipMalloc(&h->d_live_u, sizeof(double) * D * (size_t)N));
         HIP_TRY(hipMalloc(&h->d_live_theta, sizeof(double) * D * (size_t)N));
         HIP_TRY(hipMalloc(&h->d_live_logl, sizeof(double) * (size_t)N));
+        HIP_TRY(hipMalloc(&h->d_live_birth, sizeof(double) * (size_t)N));
         HIP_TRY(hipMalloc(&h->d_live_idx, sizeof(int32_t) * 2 * (size_t)N));
         HIP_TRY(hipMalloc(&h->d_sort_keys, sizeof(unsigned long long) * 2 * (size_t)N));
         HIP_TRY(hipMalloc(&h->d_sort_rows, sizeof(int32_t) * (size_t)N));
@@ -888,6 +892,7 @@ int live_load(rvll_handle* h, const double* cube, int64_t N, double* logl_out)
     HIP_TRY(hipMemcpyAsync(h->d_live_u, h->d_cube, sizeof(double) * D * (size_t)N, hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipMemcpyAsync(h->d_live_theta, h->d_theta, sizeof(double) * D * (size_t)N, hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipMemcpyAsync(h->d_live_logl, h->d_logL2[h->logl_last], sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(rvll::launch_fill(h->d_live_birth, N, -INFINITY, st));       // drawn from the whole prior: born at -inf
     if (logl_out) HIP_TRY(hipMemcpyAsync(logl_out, h->d_live_logl, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return RVLL_OK;
@@ -1079,7 +1084,8 @@ int rvll_live_step(rvll_handle* h, const int32_t* order, int64_t kdead, const in
     if (rc) return rc;
     rc = walk_core(h, kdead, lstar, nsteps, max_rounds, seed, walker_base, ncalls);
     if (rc) return rc;
-    // ... and their end points replace the dead rows
+    // ... and their end points replace the dead rows, born at lstar (the dying rows' births go to the dead store first)
+    HIP_TRY(rvll::launch_births_step(d_order, kdead, kdead, nullptr, lstar, h->d_live_birth, h->d_dead_birth + h->dead_n, st));
     HIP_TRY(rvll::launch_scatter_rows(h->d_walk_u, d_order, kdead, Di, h->d_live_u, st));
     HIP_TRY(rvll::launch_scatter_rows(h->d_walk_theta, d_order, kdead, Di, h->d_live_theta, st));
     HIP_TRY(rvll::launch_scatter_rows(h->d_walk_logl, d_order, kdead, 1, h->d_live_logl, st));
@@ -1329,7 +1335,10 @@ int rvll_live_runs_step(rvll_handle* h, const int32_t* runs, int32_t A, int64_t 
     RunWalk rw{run.data(), rid.data(), std::vector<long long>((size_t)K, 0)};
     rc = walk_core(h, K, 0., nsteps, max_rounds, 0, 0, nullptr, &rw);
     if (rc) return rc;
-    // ... and their end points replace the dying rows
+    // ... and their end points replace the dying rows, born at their run's lstar: the highest dying log-L, slot a kdead + kdead - 1
+    // of the step's block in the dead store (the dying rows' births go to the dead store first)
+    double* dead_birth = h->d_dead_birth + h->dead_n;
+    HIP_TRY(rvll::launch_births_step(d_dying, K, kdead, h->d_dead_logl + h->dead_n + (kdead - 1), 0., h->d_live_birth, dead_birth, st));
     HIP_TRY(rvll::launch_scatter_rows(h->d_walk_u, d_dying, K, Di, h->d_live_u, st));
     HIP_TRY(rvll::launch_scatter_rows(h->d_walk_theta, d_dying, K, Di, h->d_live_theta, st));
     HIP_TRY(rvll::launch_scatter_rows(h->d_walk_logl, d_dying, K, 1, h->d_live_logl, st));
@@ -1569,6 +1578,9 @@ int rvll_live_runs_step_clustered(rvll_handle* h, const int32_t* runs, int32_t A
     RunWalk rw{grun.data(), grid.data(), std::vector<long long>((size_t)K, 0)};
     rc = walk_core(h, K, 0., nsteps, max_rounds, 0, 0, nullptr, &rw);
     if (rc) return rc;
+    // births as rvll_live_runs_step: in the dead store's order (d_dying), each run's rows at its lstar
+    HIP_TRY(rvll::launch_births_step(d_dying, K, kdead, h->d_dead_logl + h->dead_n + (kdead - 1), 0., h->d_live_birth,
+                                     h->d_dead_birth + h->dead_n, st));
     HIP_TRY(rvll::launch_scatter_rows(h->d_walk_u, d_gdying, K, Di, h->d_live_u, st));
     HIP_TRY(rvll::launch_scatter_rows(h->d_walk_theta, d_gdying, K, Di, h->d_live_theta, st));
     HIP_TRY(rvll::launch_scatter_rows(h->d_walk_logl, d_gdying, K, 1, h->d_live_logl, st));
@@ -1660,6 +1672,59 @@ int rvll_live_runs_dead(rvll_handle* h, int32_t run, int64_t* n_dead, double* th
             HIP_TRY(rvll::launch_gather_rows(h->d_dead_logl, h->d_walk_order, m, 1, h->d_walk_logl, st));
             HIP_TRY(hipMemcpyAsync(logl + lo, h->d_walk_logl, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, st));
         }
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    return RVLL_OK;
+}
+
+// ---- birth contours of the resident rows ----------------------------------------------------------------------------------------
+int rvll_live_births(rvll_handle* h, int64_t* n_dead, double* dead_birth, double* live_birth)
+{
+    int rc = use_device(h);
+    if (rc) return rc;
+    if (!n_dead) return report_error(RVLL_E_INVALID, "n_dead is null");
+    if (h->runs_R > 0) return report_error(RVLL_E_INVALID, "rvll_live_births: the resident rows are an ensemble's (rvll_live_runs_births)");
+    if (live_birth && h->live_n < 1) return report_error(RVLL_E_INVALID, "rvll_live_init has not been called");
+    const int64_t have = h->dead_n, want = dead_birth ? std::min<int64_t>(*n_dead, have) : 0;
+    *n_dead = have;
+    hipStream_t st = h->compute;
+    if (want > 0) HIP_TRY(hipMemcpyAsync(dead_birth, h->d_dead_birth, sizeof(double) * (size_t)want, hipMemcpyDeviceToHost, st));
+    if (live_birth) HIP_TRY(hipMemcpyAsync(live_birth, h->d_live_birth, sizeof(double) * (size_t)h->live_n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return RVLL_OK;
+}
+
+int rvll_live_runs_births(rvll_handle* h, int32_t run, int64_t* n_dead, double* dead_birth, double* live_birth)
+{
+    int rc = use_device(h);
+    if (rc) return rc;
+    if (!n_dead) return report_error(RVLL_E_INVALID, "n_dead is null");
+    if (h->runs_R < 1) return report_error(RVLL_E_INVALID, "rvll_live_runs_init has not been called");
+    if (run < 0 || run >= h->runs_R) return report_error(RVLL_E_INVALID, "rvll_live_runs_births: run %d out of range", (int)run);
+    const auto& pieces = h->runs_dead[(size_t)run];
+    int64_t have = 0;
+    for (const auto& p : pieces) have += p.second;
+    const int64_t want = dead_birth ? std::min<int64_t>(*n_dead, have) : 0;
+    *n_dead = have;
+    hipStream_t st = h->compute;
+    if (live_birth) {
+        const size_t n = (size_t)h->runs_n, r0 = (size_t)run * n;
+        HIP_TRY(hipMemcpyAsync(live_birth, h->d_live_birth + r0, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    if (want <= 0) return RVLL_OK;
+    // the run's rows of the store in death order, as rvll_live_runs_dead gathers them
+    std::vector<int32_t> rows;
+    rows.reserve((size_t)want);
+    for (const auto& p : pieces)
+        for (long long i = 0; i < p.second && (int64_t)rows.size() < want; ++i) rows.push_back((int32_t)(p.first + i));
+    rc = walk_reserve(h, 1);
+    if (rc) return rc;
+    for (int64_t lo = 0; lo < want; lo += h->walk_cap) {
+        const int64_t m = std::min<int64_t>(h->walk_cap, want - lo);
+        HIP_TRY(hipMemcpyAsync(h->d_walk_order, rows.data() + lo, sizeof(int32_t) * (size_t)m, hipMemcpyHostToDevice, st));
+        HIP_TRY(rvll::launch_gather_rows(h->d_dead_birth, h->d_walk_order, m, 1, h->d_walk_logl, st));
+        HIP_TRY(hipMemcpyAsync(dead_birth + lo, h->d_walk_logl, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
     }
     return RVLL_OK;

@@ -464,6 +464,15 @@ class GpuRVModel:
             _abi.check(self._lib.rvll_live_dead(self._h, C.byref(cnt), _abi.as_dp(th), _abi.as_dp(ll)))
         return th, ll
 
+    def live_births(self):
+        """(dead, live): the birth contours (rvll_live_births) of every point that died so far, in the order they died, and of
+        the live points as live_get orders them — -inf for a point of live_init, else the lstar of the step that drew it."""
+        n = self.live_dead_count()
+        dead, live = np.empty(n), np.empty(self._live_n)
+        cnt = C.c_int64(n)
+        _abi.check(self._lib.rvll_live_births(self._h, C.byref(cnt), _abi.as_dp(dead), _abi.as_dp(live)))
+        return dead, live
+
     # ---- the resident ensemble: R live sets in one handle (nested.run_nested_ensemble(..., live=model)) -----------------
     def live_runs_init(self, cube, nruns):
         """R = nruns independent live sets of n rows each (cube [R n, ndim]; run r = rows r n .. r n + n - 1) -> prior
@@ -600,6 +609,15 @@ class GpuRVModel:
             cnt = C.c_int64(n)
             _abi.check(self._lib.rvll_live_runs_dead(self._h, int(run), C.byref(cnt), _abi.as_dp(th), _abi.as_dp(ll)))
         return th, ll
+
+    def live_runs_births(self, run):
+        """live_births for run `run` of the resident ensemble (rvll_live_runs_births): (dead in the order live_runs_dead gives,
+        live [n])."""
+        n = self.live_runs_dead_count(run)
+        dead, live = np.empty(n), np.empty(self._runs[1])
+        cnt = C.c_int64(n)
+        _abi.check(self._lib.rvll_live_runs_births(self._h, int(run), C.byref(cnt), _abi.as_dp(dead), _abi.as_dp(live)))
+        return dead, live
 
     def scalar_server(self, enable=True):
         """Answer scalar log_likelihood(x) calls through a persistent kernel polling pinned host memory (a PCIe

@@ -34,6 +34,8 @@ class NestedResult:
     nclusters: np.ndarray = None  # clustering=True: the clusters of the survivors, one entry per iteration (None when off)
     nlive: int = None            # the schedule the run died by (shrinkage.replicates reads it): nlive live points,
     kbatch: int = None           # kbatch deaths per iteration (run_nested: 1)
+    logl_birth: np.ndarray = None  # per row (the order of logl): the contour it was drawn above — -inf for an initial point, else the
+                                   # lstar of the iteration that drew it (the insertion-index test reads it; insertion.py)
 
 
 def _logaddexp_many(x):
@@ -74,6 +76,7 @@ def run_nested(prior: Callable, loglike: Callable, ndim: int, nlive: Optional[in
     ncall = nlive
     update_every = update_every or max(1, nlive // 5)
     dead_theta, dead_logl, dead_logw = [], [], []
+    birth, dead_birth = np.full(nlive, -np.inf), []
     logz, h, logx = -np.inf, 0.0, 0.0
     pool_u = pool_t = pool_l = None
     pos = 0
@@ -89,6 +92,7 @@ def run_nested(prior: Callable, loglike: Callable, ndim: int, nlive: Optional[in
         h = np.exp(logw - logz_new) * lmin + h_old_term - logz_new
         logz, logx = logz_new, logx_new
         dead_theta.append(theta[worst].copy()); dead_logl.append(lmin); dead_logw.append(logw)
+        dead_birth.append(birth[worst])
         # replacement: the first pooled candidate above the threshold.  A pool drawn from an older
         # (larger) ellipsoid stays valid — it is uniform on a superset of the constrained region.
         found = False
@@ -110,12 +114,13 @@ def run_nested(prior: Callable, loglike: Callable, ndim: int, nlive: Optional[in
                 pos += 1
                 if pool_l[k] > lmin:
                     u[worst], theta[worst], logl[worst] = pool_u[k], pool_t[k], pool_l[k]
+                    birth[worst] = lmin
                     found = True
                     break
         if not found:                      # budget exhausted: the point removed above stays dead, stop here
             logl[worst] = -np.inf
             keep = np.isfinite(logl)
-            u, theta, logl = u[keep], theta[keep], logl[keep]
+            u, theta, logl, birth = u[keep], theta[keep], logl[keep], birth[keep]
             it += 1
             break
         it += 1
@@ -130,7 +135,8 @@ def run_nested(prior: Callable, loglike: Callable, ndim: int, nlive: Optional[in
     all_logl = np.concatenate([dead_logl, logl])
     all_logw = np.concatenate([dead_logw, logw_live]) - logz_final
     return NestedResult(float(logz_final), float(np.sqrt(max(h, 0.0) / nlive)), it, ncall, float(h),
-                        all_theta, all_logl, all_logw, nlive=nlive, kbatch=1)
+                        all_theta, all_logl, all_logw, nlive=nlive, kbatch=1,
+                        logl_birth=np.concatenate([np.array(dead_birth, dtype=np.float64), birth]))
 
 
 # --------------------------------------------------------------------------------------------------
@@ -344,6 +350,7 @@ def run_nested_slice(prior: Callable, loglike: Callable, ndim: int, nlive: Optio
         logl = np.asarray(loglike(theta), dtype=np.float64)
     ncall = nlive
     dead_theta, dead_logl, dead_logw = [], [], []
+    birth, dead_birth = np.full(nlive, -np.inf), []      # (host order: every path but device_order, which reads them at the end)
     logz, h, logx = -np.inf, 0.0, 0.0
     it = 0
     # the resident live set with the ORDER on the device as well (GpuRVModel.live_sort, round 4): no per-point state on the host
@@ -366,6 +373,8 @@ def run_nested_slice(prior: Callable, loglike: Callable, ndim: int, nlive: Optio
             dead = order[:kbatch]
             lstar = logl[dead[-1]]
             dl = logl[dead]
+            dead_birth.append(birth[dead])
+            birth[dead] = lstar                                   # (the replacements of this iteration are drawn above lstar)
             timing["order_s"] += time.perf_counter() - t_turn
         if device_order:
             pass
@@ -481,9 +490,15 @@ def run_nested_slice(prior: Callable, loglike: Callable, ndim: int, nlive: Optio
         all_theta = np.vstack([a.reshape(-1, ndim) for a in dead_theta] + [theta])
     all_logl = np.concatenate(dead_logl + [logl])
     all_logw = np.concatenate(dead_logw + [logw_live]) - logz_final
+    if live is not None and hasattr(live, "live_births"):
+        all_birth = np.concatenate(live.live_births())        # the device's own record (it chose the dying rows)
+    elif device_order:
+        all_birth = None                                      # (a live set without births: the host never saw which rows died)
+    else:
+        all_birth = np.concatenate(dead_birth + [birth])
     return NestedResult(float(logz_final), float(np.sqrt(max(h, 0.0) / nlive)), it, ncall, float(h),
                         all_theta, all_logl, all_logw, timing, None if nclusters is None else np.array(nclusters, dtype=np.int64),
-                        nlive=nlive, kbatch=kbatch)
+                        nlive=nlive, kbatch=kbatch, logl_birth=all_birth)
 
 
 class _EnsembleRun:
@@ -496,6 +511,7 @@ class _EnsembleRun:
         self.theta = self.logl = None
         self.ncall = nlive
         self.dead_theta, self.dead_logl, self.dead_logw = [], [], []
+        self.birth, self.dead_birth = np.full(nlive, -np.inf), []
         self.logz, self.h, self.logx = -np.inf, 0.0, 0.0
         self.it = 0
         self.done = False
@@ -581,6 +597,8 @@ def run_nested_ensemble(prior: Callable, loglike: Callable, ndim: int, seeds, nl
             logw, r.logz, r.h, r.logx = _deaths(r.logz, r.h, r.logx, dl, nlive, kbatch)
             r.dead_theta.append(r.theta[dead])
             r.dead_logl.append(dl); r.dead_logw.append(logw)
+            r.dead_birth.append(r.birth[dead])
+            r.birth[dead] = lstar
             r.it += kbatch
             alive = order[kbatch:]
             chol = _whitening(r.u[alive])
@@ -627,7 +645,8 @@ def run_nested_ensemble(prior: Callable, loglike: Callable, ndim: int, seeds, nl
         all_logw = np.concatenate(r.dead_logw + [logw_live]) - logz_final
         out.append(NestedResult(float(logz_final), float(np.sqrt(max(r.h, 0.0) / nlive)), r.it, r.ncall, float(r.h),
                                 all_theta, all_logl, all_logw, r.timing,
-                                np.array(r.nclusters, dtype=np.int64) if clustering else None, nlive=nlive, kbatch=kbatch))
+                                np.array(r.nclusters, dtype=np.int64) if clustering else None, nlive=nlive, kbatch=kbatch,
+                                logl_birth=np.concatenate(r.dead_birth + [r.birth])))
     return out
 
 
@@ -727,7 +746,9 @@ def _ensemble_resident(live, ndim, seeds, nlive, kbatch, nsteps, dlogz, max_iter
         live.live_runs_get(r, cube=False, logl=False, theta_out=all_theta[ndead:])
         all_logl = np.concatenate(dead_logl[r] + [logl])
         all_logw = np.concatenate(dead_logw[r] + [logw_live]) - logz_final
+        all_birth = np.concatenate(live.live_runs_births(r)) if hasattr(live, "live_runs_births") else None
         out.append(NestedResult(float(logz_final), float(np.sqrt(max(h[r], 0.0) / nlive)), int(niter[r]), int(ncall[r]), float(h[r]),
                                 all_theta, all_logl, all_logw, timing[r],
-                                np.array(ncls[r], dtype=np.int64) if clustering else None, nlive=nlive, kbatch=kbatch))
+                                np.array(ncls[r], dtype=np.int64) if clustering else None, nlive=nlive, kbatch=kbatch,
+                                logl_birth=all_birth))
     return out

@@ -51,12 +51,13 @@ extern "C" {
 #endif
 
 #define RVLL_VERSION_MAJOR 0
-#define RVLL_VERSION_MINOR 7   /* 0.2: rvll_slice_walk takes walker_base; RVLL_FLAG_WANDERED; resident live set
+#define RVLL_VERSION_MINOR 8   /* 0.2: rvll_slice_walk takes walker_base; RVLL_FLAG_WANDERED; resident live set
                                   0.3: rvll_slice_walk_runs
                                   0.4: rvll_cluster_runs
                                   0.5: rvll_live_runs_* (resident ensemble)
                                   0.6: rvll_live_runs_step_clustered, rvll_live_runs_clusters
-                                  0.7: rvll_shrinkage_replicates */
+                                  0.7: rvll_shrinkage_replicates
+                                  0.8: rvll_live_births, rvll_live_runs_births, rvll_insertion_indexes */
 
 /* ---- error codes ------------------------------------------------------ */
 #define RVLL_OK             0
@@ -397,6 +398,17 @@ int rvll_live_runs_step_clustered(rvll_handle* h, const int32_t* runs /*[A]*/, i
                                   int64_t* ncalls /*[A] or NULL*/, double* logl_new /*[A, kdead]*/, int32_t* nclusters /*[A]*/);
 int rvll_live_runs_clusters(rvll_handle* h, int32_t a, int64_t* nsurv, int32_t* nclusters, int32_t* labels /*[m]*/,
                             double* scale /*[ndim]*/, double* factors /*[max(nclusters, 1), ndim, ndim]*/, double* phase_s /*[3]*/);
+/* Birth contours of the resident rows (the insertion-index test; evidence_amd/insertion.py).  A row loaded by
+ * rvll_live_init / rvll_live_runs_init is born at -inf; a row a step draws is born at that step's lstar (its run's, for the
+ * ensemble steps) — the highest log-L of the batch that died.  The dying rows' births go to the dead store with their theta and
+ * log-L, and a step that fails leaves every birth as it was.
+ * rvll_live_births       as rvll_live_dead: *n_dead in: capacity of dead_birth [*] (ignored when it is NULL), out: rows in the dead
+ *                        store; dead_birth in death order, live_birth [N] (may be NULL) the live rows' as rvll_live_get orders them.
+ *                        RVLL_E_INVALID while an ensemble is loaded, or live_birth without a live set.
+ * rvll_live_runs_births  the same for run r of the ensemble: dead_birth in the order rvll_live_runs_dead gives, live_birth [n]. */
+int rvll_live_births(rvll_handle* h, int64_t* n_dead, double* dead_birth /*[*n_dead] or NULL*/, double* live_birth /*[N] or NULL*/);
+int rvll_live_runs_births(rvll_handle* h, int32_t run, int64_t* n_dead, double* dead_birth /*[*n_dead] or NULL*/,
+                          double* live_birth /*[n] or NULL*/);
 
 /* ---- scalar-callback latency ------------------------------------------------------------------------- */
 /* PolyChord's loglike(theta) is irreducibly scalar (evidence/polychord/__init__.py:166-171): one theta per call.
@@ -556,6 +568,25 @@ int rvll_shrinkage_replicates(int32_t device, const double* logl, int64_t n_rows
                               const uint64_t* seeds, int32_t nsamples, int32_t mode, double* logz /*[n_runs, nsamples]*/,
                               double* info /*[n_runs, nsamples]*/, double* logwt /*NULL or [nsamples * n_rows]*/,
                               int64_t block_bytes, rvll_shrink_timing* timing);
+
+/* ---- insertion indexes of finished runs (post-processing; independent of any model handle) ---------------- */
+/* The insertion-index test (Fowlie, Handley & Su 2020): evidence_amd/insertion.py is the definition.  Rows
+ * run_start[r] .. run_start[r+1] of logl / birth (n_rows in all, any order inside a run) are run r.  For a row j with
+ * birth b = birth[j] > -inf: live(j) = {k in its run : birth[k] <= b < logl[k]}, n_at_out[j] = |live(j)|, index_out[j] =
+ * #{k in live(j) : logl[k] < logl[j]}; rows with birth -inf get -1 in both.  Doubles are compared as doubles (-0.0 == +0.0).
+ * The outputs are integers: the same for a run alone or inside any batch.  RVLL_E_INVALID for NaN values, a run_start that
+ * does not rise from 0 to n_rows, n_runs < 1, runs of 2^31 rows or more, and null buffers.  timing may be NULL.  device < 0
+ * uses the current device.                                                                                               */
+typedef struct rvll_insertion_timing {
+    double  kernel_ms;       /* HIP-event time of the device work (key map, two segmented sorts, counts), summed over chunks */
+    double  total_ms;        /* the whole call: checks, allocation, uploads, kernels, downloads                            */
+    int64_t rows;            /* n_rows                                                                                      */
+    int32_t launches;        /* kernel launches issued (a rocPRIM sort counted as one)                                      */
+    int32_t threads;         /* per workgroup; one wave64 per row                                                           */
+} rvll_insertion_timing;
+int rvll_insertion_indexes(int32_t device, const double* logl /*[n_rows]*/, const double* birth /*[n_rows]*/, int64_t n_rows,
+                           const int64_t* run_start /*[n_runs + 1]*/, int32_t n_runs, int32_t* index_out /*[n_rows]*/,
+                           int32_t* n_at_out /*[n_rows]*/, rvll_insertion_timing* timing);
 
 /* ---- diagnostics -------------------------------------------------------------- */
 /* Evaluate one device math routine elementwise (tests only; no reference counterpart):
