@@ -112,6 +112,10 @@ PROTOTYPES = {
                                   C.c_uint64, C.c_int64, C.POINTER(C.c_int64)]),
     "rvll_slice_walk_runs": (C.c_int, [Handle, _dp, _dp, _dp, C.POINTER(C.c_int64), C.c_int32, _dp, _dp,
                                        C.POINTER(C.c_uint64), _ip, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    "rvll_slice_walk_runs_steps": (C.c_int, [Handle, _dp, _dp, _dp, C.POINTER(C.c_int64), C.c_int32, _dp, _dp,
+                                             C.POINTER(C.c_uint64), _ip, _ip, C.c_int32, C.POINTER(C.c_int64)]),
+    "rvll_walk_distances_runs": (C.c_int, [Handle, _dp, C.POINTER(C.c_int64), C.c_int32, _dp, _ip, _dp, _dp, _ip, C.c_int64,
+                                           _dp, _dp]),
     "rvll_cluster_runs": (C.c_int, [Handle, _dp, C.POINTER(C.c_int64), C.c_int64, _dp, _ip, C.c_int,
                                     C.POINTER(C.c_uint64), _ip, _ip, _dp]),
     "rvll_live_init": (C.c_int, [Handle, _dp, C.c_int64, _dp]),
@@ -129,6 +133,9 @@ PROTOTYPES = {
     "rvll_live_runs_step_clustered": (C.c_int, [Handle, _ip, C.c_int32, C.c_int64, _ip, _dp, _ip, C.c_int32, C.c_int32,
                                                 C.POINTER(C.c_uint64), C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_int64),
                                                 _dp, _ip]),
+    "rvll_live_runs_step_steps": (C.c_int, [Handle, _ip, C.c_int32, C.c_int64, _ip, _dp, _ip, _ip, C.c_int32,
+                                            C.POINTER(C.c_uint64), C.c_int32, C.c_int32, C.POINTER(C.c_uint64),
+                                            C.POINTER(C.c_int64), _dp, _ip, _dp, _dp]),
     "rvll_live_runs_clusters": (C.c_int, [Handle, C.c_int32, C.POINTER(C.c_int64), _ip, _ip, _dp, _dp, _dp]),
     "rvll_live_births": (C.c_int, [Handle, C.POINTER(C.c_int64), _dp, _dp]),
     "rvll_live_runs_births": (C.c_int, [Handle, C.c_int32, C.POINTER(C.c_int64), _dp, _dp]),

@@ -149,6 +149,7 @@ struct rvll_handle {
     double* d_run_lstar = nullptr;              // [runs_cap]
     unsigned long long* d_run_seed = nullptr;   // [runs_cap]
     double* d_run_chol = nullptr;               // [runs_cap, ndim, ndim]
+    int32_t* d_run_nsteps = nullptr;            // [runs_cap] per-run step counts (rvll_slice_walk_runs_steps)
     int wander_exact = 1;                       // wandering solves are redone with correctly rounded sin / cos (rvll_set_wander_exact; RVLL_WANDER_EXACT)
     int walk_spec = 4;                          // candidates a walker may evaluate ahead per iteration (rvll_set_walk_speculation)
     // the walk as rounds of launches (rvll_rounds.hip; walk_rounds in rvll_walk_host.hip): one arena with every group's walker
@@ -200,6 +201,11 @@ struct rvll_handle {
     void* d_cl_work = nullptr;
     void* d_cl_out = nullptr;
     size_t cl_in_cap = 0, cl_work_cap = 0, cl_out_cap = 0;   // bytes
+    // the step-count adaptation's distances (rvll_walk_distances_runs): one grow-only block of inputs, tiles, partials, outputs
+    void* d_adapt = nullptr;
+    size_t adapt_cap = 0;                                     // bytes
+    void* d_adapt_in = nullptr;                               // rvll_walk_distances_runs' inputs; the resident step's walker start rows
+    size_t adapt_in_cap = 0;                                  // bytes
     // the clustered step of the resident ensemble (rvll_live_runs_step_clustered): grow-only block of the per-(run, cluster) segments
     // — (offset, rows) [S][2], fold scales [S][2], mean [S][D], covariance [S][D, D] — and what the last clustered step found, for
     // rvll_live_runs_clusters: per listed run the survivors' labels in rank order [A m], the metric scale [A D], the cluster count,
@@ -259,6 +265,21 @@ ClusterLayout cluster_layout(int64_t N, int64_t R, int D, size_t block_ints);
 int cluster_reserve(rvll_handle* h, const ClusterLayout& L, const char* who);
 rvll::ClusterArgs cluster_args(rvll_handle* h, const ClusterLayout& L, int D, int nboot, const int32_t* wrapped);
 int cluster_core(rvll_handle* h, const rvll::ClusterArgs& a);
+// rvll_adapt.hip: the step-count adaptation's distances on device pointers.  Group g's members are rows (d_idx ? d_idx[gofs[g] + i]
+// : gofs[g] + i) of d_rows, i < gcnt[g]; its factor is d_factors[g]; walker k went from d_starts[k] to d_ends[k] in group
+// d_walker_group[k].  Leaves pair [G] and move [K] in *d_pair / *d_move (h->d_adapt) behind the launches on the compute stream;
+// `tables` (and gofs, gcnt) must live until the stream has passed them.  adapt_in_reserve: the grow-only block d_adapt_in.
+int walk_distances_core(rvll_handle* h, const double* d_rows, const int32_t* d_idx, const std::vector<int64_t>& gofs,
+                        const std::vector<int64_t>& gcnt, const double* d_factors, unsigned long long wmask, const double* d_starts,
+                        const double* d_ends, const int32_t* d_walker_group, int64_t K, double** d_pair, double** d_move,
+                        std::vector<int32_t>& tables);
+int adapt_in_reserve(rvll_handle* h, size_t bytes);
+inline unsigned long long wrapped_mask(const int32_t* wrapped, int D)
+{
+    unsigned long long m = 0;
+    if (wrapped) for (int d = 0; d < D && d < 64; ++d) if (wrapped[d]) m |= 1ull << d;
+    return m;
+}
 constexpr size_t kDownloadStagedMin = 32u << 20, kDeadStagedMin = 8u << 20;
 
 }  // namespace host

@@ -119,6 +119,8 @@ struct WalkArgs {
     const double* run_lstar;             // [R]
     const unsigned long long* run_seed;  // [R]
     const double* run_chol;              // [R, D, D] row-major lower-triangular factors
+    const int32_t* run_nsteps;           // [R] or null (run mode): row g makes min(nsteps, run_nsteps[run[g]]) moves
+                                         // (rvll_slice_walk_runs_steps: nsteps is then the largest of them, or a first part's)
 };
 constexpr int kWalkCholLds = 48;   // the walk stages a whitening factor of up to 48 x 48 (18 KB) in LDS
 size_t walk_lds_bytes(const LoglikeArgs& a);

@@ -52,6 +52,7 @@ namespace {
 // RUNS (run mode, rvll_slice_walk_runs; w.run != null): the rows belong to independent runs, each with its own lstar, seed
 // and whitening factor (WalkArgs).  The factor is read from global memory, per walker that starts a move (the walkers of a
 // workgroup may belong to different runs); the instantiation without it is the one-run walk, instruction for instruction.
+// With w.run_nsteps a row stops after its run's own number of moves (w.nsteps is then the largest, which bounds the loop).
 template <int PREC, bool FAT, int NP = 0, bool RUNS = false>   // NP: the planet count at compile time (rvll_tile.h, eval_item), 0 = a.Np
 __global__ __launch_bounds__(kThreads, FAT ? 2 : RVLL_WALK_WAVES) __attribute__((flatten))
 void slice_walk_kernel(const LoglikeArgs a, const WalkArgs w)
@@ -103,6 +104,11 @@ void slice_walk_kernel(const LoglikeArgs a, const WalkArgs w)
 
     // the k-th row to be handed out (k: position in the host's order, or the row itself)
     auto row_at = [&](long long k) -> int { return w.order ? w.order[k] : (int)k; };
+    // the moves row g makes in this launch: nsteps, or (run mode with a per-run table) its run's count if that is fewer
+    auto moves_of = [&](int g) -> int {
+        if constexpr (RUNS) { if (w.run_nsteps) return min(w.nsteps, w.run_nsteps[w.run[g]]); }
+        return w.nsteps;
+    };
     for (int i = tid; i < nw * D; i += kThreads) wu[i] = w.u[(long long)row_at(w0 + i / D) * D + i % D];
     if (chol_in_lds) for (int i = tid; i < D * D; i += kThreads) chol_s[i] = w.chol[i];
     for (int i = tid; i < D; i += kThreads) wrapped_s[i] = w.wrapped[i];
@@ -135,7 +141,7 @@ void slice_walk_kernel(const LoglikeArgs a, const WalkArgs w)
         int st = active ? state[pl] : 1, stp = active ? step_of[pl] : 0;
         if (active && !first) { const int u = used_of[pl]; calls += u; cost_of[pl] += u; }
         if (active && st == 2) { st = 0; stp += 1; }
-        const bool done = active && !(stp < w.nsteps && st != 3);
+        const bool done = active && !(stp < moves_of(gid[pl]) && st != 3);
         int g = active ? gid[pl] : -1, rf = 0;
         if (done) {
             gold[pl] = g;
@@ -147,7 +153,7 @@ void slice_walk_kernel(const LoglikeArgs a, const WalkArgs w)
                 if (k >= w.K) { queue_empty = true; break; }
                 const int q = w.order ? w.order[k] : (int)k;
                 const int ss = w.step_start ? w.step_start[q] : 0;
-                if (ss < w.nsteps) { g = q; break; }
+                if (ss < moves_of(q)) { g = q; break; }
                 if (w.steps_done) w.steps_done[q] = ss;
                 if (w.cost) w.cost[q] = 0;
             }

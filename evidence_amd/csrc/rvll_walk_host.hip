@@ -49,10 +49,14 @@ int walk_reserve(rvll_handle* h, int64_t K)
 // it); per run lstar, seed and whitening factor are in d_run_lstar / d_run_seed / d_run_chol.  Every launch of the walk counts
 // the calls of each row in d_walk_cost (the single-kernel forms' per-row cost, the rounds step's per-walker count), and the
 // host adds them up per row: the calls of a run are then those its own walk would report, whichever forms the rows took.
+// With a per-run step-count table (rvll_slice_walk_runs_steps; nsteps != null, d_run_nsteps uploaded) the nsteps of the walk
+// is the largest count and a row stops after its run's own: the single-kernel forms read the table (WalkArgs::run_nsteps),
+// the rounds form, whose direction table has nsteps rows per walker, is not taken.
 struct RunWalk {
     const int32_t* run;                // [K] host copy of d_walk_run
     const int32_t* rid;                // [K] host copy of d_walk_wid
     std::vector<long long> row_calls;  // [K] out: likelihood calls every row consumed
+    const int32_t* nsteps = nullptr;   // [R] or null: host copy of d_run_nsteps
 };
 
 // run mode: d_walk_cost [n] down and added to rw->row_calls (at rows[j], or at j when rows is null); synchronises the stream
@@ -81,9 +85,10 @@ int runs_reserve(rvll_handle* h, int64_t K, int64_t R)
     }
     if (R > h->runs_cap) {
         HIP_TRY(hipStreamSynchronize(st));
-        dev_free(h->d_run_lstar); dev_free(h->d_run_seed); dev_free(h->d_run_chol);
+        dev_free(h->d_run_lstar); dev_free(h->d_run_seed); dev_free(h->d_run_chol); dev_free(h->d_run_nsteps);
         h->runs_cap = 0;
         const size_t cap = (size_t)std::max<int64_t>(R, 64);
+        HIP_TRY(hipMalloc(&h->d_run_nsteps, sizeof(int32_t) * cap));
         HIP_TRY(hipMalloc(&h->d_run_lstar, sizeof(double) * cap));
         HIP_TRY(hipMalloc(&h->d_run_seed, sizeof(unsigned long long) * cap));
         HIP_TRY(hipMalloc(&h->d_run_chol, sizeof(double) * D * D * cap));
@@ -580,7 +585,7 @@ int walk_core(rvll_handle* h, int64_t K, double lstar, int32_t nsteps, int32_t m
     long long rounds_calls = 0, rounds_slots = 0;
     bool by_rounds = false;
     h->walk_rounds_used = 0;
-    if (slim && rounds_wanted(K)) {
+    if (slim && rounds_wanted(K) && !(rw && rw->nsteps)) {
         rc = walk_rounds(h, K, lstar, nsteps, max_rounds, seed, walker_base, &rounds_calls, &rounds_slots, rw);
         if (rc == RVLL_OK) by_rounds = true;
         else if (rc != RVLL_E_UNSUPPORTED) return rc;
@@ -596,6 +601,7 @@ int walk_core(rvll_handle* h, int64_t K, double lstar, int32_t nsteps, int32_t m
         w.run = h->d_walk_run;  w.run_lstar = h->d_run_lstar;  w.run_seed = h->d_run_seed;  w.run_chol = h->d_run_chol;
         w.walker_id = h->d_walk_wid;                   // the row's index inside its run
         w.cost = h->d_walk_cost;                       // every launch counts every row's calls
+        if (rw->nsteps) w.run_nsteps = h->d_run_nsteps;
     }
     // no more workgroups than the chip holds at once; freed walker slots draw the remaining rows from a queue
     // (RVLL_WALK_QUEUE, a measurement / test switch: 0 = one workgroup per PB rows, as many residency rounds as that
@@ -746,8 +752,10 @@ int walk_core(rvll_handle* h, int64_t K, double lstar, int32_t nsteps, int32_t m
                 evaluated[6], evaluated[8], evaluated[9], evaluated[10], evaluated[11]);
     if (slim) {
         std::vector<int32_t> ids, start;
-        for (int64_t i = 0; i < K; ++i)
-            if (steps[(size_t)i] < nsteps) { ids.push_back((int32_t)i); start.push_back(steps[(size_t)i]); }
+        for (int64_t i = 0; i < K; ++i) {
+            const int32_t ni = rw && rw->nsteps ? std::min(nsteps, rw->nsteps[rw->run[i]]) : nsteps;
+            if (steps[(size_t)i] < ni) { ids.push_back((int32_t)i); start.push_back(steps[(size_t)i]); }
+        }
         if (!ids.empty()) {
             // finish the interrupted walkers with the full solvers inline: same seed, same walker index in the
             // random-number counters, resumed at the start of the move that was interrupted.  Rare: the rows travel
@@ -931,9 +939,15 @@ int rvll_slice_walk(rvll_handle* h, double* cube, double* theta, double* logl, i
     return RVLL_OK;
 }
 
-int rvll_slice_walk_runs(rvll_handle* h, double* cube, double* theta, double* logl, const int64_t* run_start, int32_t R,
+}  // extern "C"
+
+namespace {
+
+// rvll_slice_walk_runs (steps = null: every run makes nsteps moves) and rvll_slice_walk_runs_steps (steps [R]: run r makes
+// steps[r]; nsteps is their largest)
+int slice_walk_runs_impl(rvll_handle* h, double* cube, double* theta, double* logl, const int64_t* run_start, int32_t R,
                          const double* lstar, const double* chol, const uint64_t* seed, const int32_t* wrapped,
-                         int32_t nsteps, int32_t max_rounds, int64_t* ncalls)
+                         const int32_t* steps, int32_t nsteps, int32_t max_rounds, int64_t* ncalls)
 {
     int rc = use_device(h);
     if (rc) return rc;
@@ -966,9 +980,10 @@ int rvll_slice_walk_runs(rvll_handle* h, double* cube, double* theta, double* lo
     HIP_TRY(hipMemcpyAsync(h->d_run_lstar, lstar, sizeof(double) * (size_t)R, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(h->d_run_seed, seed, sizeof(uint64_t) * (size_t)R, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(h->d_run_chol, chol, sizeof(double) * D * D * (size_t)R, hipMemcpyHostToDevice, st));
+    if (steps) HIP_TRY(hipMemcpyAsync(h->d_run_nsteps, steps, sizeof(int32_t) * (size_t)R, hipMemcpyHostToDevice, st));
     rc = walk_upload_frame(h, nullptr, wrapped);       // (synchronises: the host tables above may go out of scope after it)
     if (rc) return rc;
-    RunWalk rw{run.data(), rid.data(), std::vector<long long>((size_t)K, 0)};
+    RunWalk rw{run.data(), rid.data(), std::vector<long long>((size_t)K, 0), steps};
     rc = walk_core(h, K, 0., nsteps, max_rounds, 0, 0, nullptr, &rw);
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(cube, h->d_walk_u, sizeof(double) * D * (size_t)K, hipMemcpyDeviceToHost, st));
@@ -979,6 +994,34 @@ int rvll_slice_walk_runs(rvll_handle* h, double* cube, double* theta, double* lo
         for (int32_t r = 0; r < R; ++r)
             for (int64_t i = run_start[r]; i < run_start[r + 1]; ++i) ncalls[r] += rw.row_calls[(size_t)i];
     return RVLL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rvll_slice_walk_runs(rvll_handle* h, double* cube, double* theta, double* logl, const int64_t* run_start, int32_t R,
+                         const double* lstar, const double* chol, const uint64_t* seed, const int32_t* wrapped,
+                         int32_t nsteps, int32_t max_rounds, int64_t* ncalls)
+{
+    return slice_walk_runs_impl(h, cube, theta, logl, run_start, R, lstar, chol, seed, wrapped, nullptr, nsteps, max_rounds, ncalls);
+}
+
+int rvll_slice_walk_runs_steps(rvll_handle* h, double* cube, double* theta, double* logl, const int64_t* run_start, int32_t R,
+                               const double* lstar, const double* chol, const uint64_t* seed, const int32_t* wrapped,
+                               const int32_t* nsteps, int32_t max_rounds, int64_t* ncalls)
+{
+    if (R > 0 && !nsteps) return report_error(RVLL_E_INVALID, "rvll_slice_walk_runs_steps: null step table");
+    int32_t most = 0, least = R > 0 ? nsteps[0] : 0;
+    for (int32_t r = 0; r < R; ++r) {
+        if (nsteps[r] < 0 || nsteps[r] >= (1 << 18))
+            return report_error(RVLL_E_INVALID, "rvll_slice_walk_runs_steps: nsteps[%d] = %d out of range", (int)r, (int)nsteps[r]);
+        most = std::max(most, nsteps[r]);
+        least = std::min(least, nsteps[r]);
+    }
+    // a uniform table is the scalar walk (every form open to it); otherwise the rows stop at their run's count
+    return slice_walk_runs_impl(h, cube, theta, logl, run_start, R, lstar, chol, seed, wrapped, least == most ? nullptr : nsteps,
+                                most, max_rounds, ncalls);
 }
 
 // ---- nested sampling with the live points resident on the device -------------------------------------------
@@ -1267,9 +1310,11 @@ int rvll_live_runs_sort(rvll_handle* h, const int32_t* runs, int32_t A, int64_t 
     return RVLL_OK;
 }
 
-int rvll_live_runs_step(rvll_handle* h, const int32_t* runs, int32_t A, int64_t kdead, const int32_t* ranks, const double* lstar,
-                        const int32_t* wrapped, int32_t nsteps, int32_t max_rounds, const uint64_t* seeds, int64_t* ncalls,
-                        double* logl_new, double* chol_out)
+// rvll_live_runs_step, and rvll_live_runs_step_steps unclustered: steps [A] or null (every run nsteps; else nsteps is their
+// largest), move_out / pair_out [A kdead] or null (the step-count adaptation's distances)
+static int live_runs_step_impl(rvll_handle* h, const int32_t* runs, int32_t A, int64_t kdead, const int32_t* ranks, const double* lstar,
+                               const int32_t* wrapped, int32_t nsteps, const int32_t* steps, int32_t max_rounds, const uint64_t* seeds,
+                               int64_t* ncalls, double* logl_new, double* chol_out, double* move_out, double* pair_out)
 {
     int rc = use_device(h);
     if (rc) return rc;
@@ -1332,9 +1377,36 @@ int rvll_live_runs_step(rvll_handle* h, const int32_t* runs, int32_t A, int64_t 
     if (rc) return rc;
     std::vector<int32_t> run((size_t)K), rid((size_t)K);
     for (int64_t e = 0; e < K; ++e) { run[(size_t)e] = (int32_t)(e / kdead); rid[(size_t)e] = (int32_t)(e % kdead); }
-    RunWalk rw{run.data(), rid.data(), std::vector<long long>((size_t)K, 0)};
+    const bool dist = move_out || pair_out;
+    double* d_wstart = nullptr;
+    int32_t* d_wgroup = nullptr;
+    if (dist) {                                          // the walkers' start rows and groups (walk_core may reuse d_walk_run)
+        rc = adapt_in_reserve(h, 8 * (size_t)K * D + 4 * (size_t)K + 16);
+        if (rc) return rc;
+        d_wstart = static_cast<double*>(h->d_adapt_in);
+        d_wgroup = reinterpret_cast<int32_t*>(d_wstart + (size_t)K * D);
+        HIP_TRY(hipMemcpyAsync(d_wstart, h->d_walk_u, 8 * (size_t)K * D, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_wgroup, run.data(), 4 * (size_t)K, hipMemcpyHostToDevice, st));
+    }
+    if (steps) HIP_TRY(hipMemcpyAsync(h->d_run_nsteps, steps, sizeof(int32_t) * (size_t)A, hipMemcpyHostToDevice, st));
+    RunWalk rw{run.data(), rid.data(), std::vector<long long>((size_t)K, 0), steps};
     rc = walk_core(h, K, 0., nsteps, max_rounds, 0, 0, nullptr, &rw);
     if (rc) return rc;
+    // the distances (group = the run: its survivors, ranks kdead .. n of its sort order, and its factor), behind the walk
+    std::vector<int64_t> gofs, gcnt;
+    std::vector<int32_t> tables;
+    std::vector<double> hmove, hpair;
+    if (dist) {
+        gofs.resize((size_t)A); gcnt.assign((size_t)A, n - kdead);
+        for (int32_t a = 0; a < A; ++a) gofs[(size_t)a] = (int64_t)a * n + kdead;
+        double *d_pair = nullptr, *d_move = nullptr;
+        rc = walk_distances_core(h, h->d_live_u, d_order, gofs, gcnt, h->d_run_chol, wrapped_mask(wrapped, Di), d_wstart, h->d_walk_u,
+                                 d_wgroup, K, &d_pair, &d_move, tables);
+        if (rc) return rc;
+        hmove.resize((size_t)K); hpair.resize((size_t)A);
+        HIP_TRY(hipMemcpyAsync(hmove.data(), d_move, 8 * (size_t)K, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(hpair.data(), d_pair, 8 * (size_t)A, hipMemcpyDeviceToHost, st));
+    }
     // ... and their end points replace the dying rows, born at their run's lstar: the highest dying log-L, slot a kdead + kdead - 1
     // of the step's block in the dead store (the dying rows' births go to the dead store first)
     double* dead_birth = h->d_dead_birth + h->dead_n;
@@ -1346,18 +1418,33 @@ int rvll_live_runs_step(rvll_handle* h, const int32_t* runs, int32_t A, int64_t 
     HIP_TRY(hipStreamSynchronize(st));
     if (ncalls)
         for (int64_t e = 0; e < K; ++e) ncalls[e / kdead] += rw.row_calls[(size_t)e];
+    if (dist)
+        for (int64_t e = 0; e < K; ++e) {
+            if (move_out) move_out[e] = hmove[(size_t)e];
+            if (pair_out) pair_out[e] = hpair[(size_t)(e / kdead)];
+        }
     for (int32_t a = 0; a < A; ++a) h->runs_dead[(size_t)runs[a]].emplace_back(h->dead_n + (long long)a * kdead, (long long)kdead);
     h->dead_n += K;
     return RVLL_OK;
 }
 
+int rvll_live_runs_step(rvll_handle* h, const int32_t* runs, int32_t A, int64_t kdead, const int32_t* ranks, const double* lstar,
+                        const int32_t* wrapped, int32_t nsteps, int32_t max_rounds, const uint64_t* seeds, int64_t* ncalls,
+                        double* logl_new, double* chol_out)
+{
+    return live_runs_step_impl(h, runs, A, kdead, ranks, lstar, wrapped, nsteps, nullptr, max_rounds, seeds, ncalls, logl_new, chol_out,
+                               nullptr, nullptr);
+}
+
 // The clustered step ("Clustering inside the resident ensemble").  Host synchronisations before the walk: the global
 // covariances (as rvll_live_runs_step), the labels and cluster counts, and — only when some run has more than one cluster with at
 // least 2 ndim rows — the per-cluster covariances; then those of the walk and the final download, as rvll_live_runs_step.
-int rvll_live_runs_step_clustered(rvll_handle* h, const int32_t* runs, int32_t A, int64_t kdead, const int32_t* ranks,
-                                  const double* lstar, const int32_t* wrapped, int32_t nsteps, int32_t max_rounds,
-                                  const uint64_t* seeds, int32_t nboot, const uint64_t* boot_seeds, int64_t* ncalls,
-                                  double* logl_new, int32_t* nclusters)
+// rvll_live_runs_step_clustered, and rvll_live_runs_step_steps clustered (steps, move_out, pair_out as live_runs_step_impl; the
+// distances' groups are the walk's (run, cluster) groups)
+static int live_runs_step_clustered_impl(rvll_handle* h, const int32_t* runs, int32_t A, int64_t kdead, const int32_t* ranks,
+                                         const double* lstar, const int32_t* wrapped, int32_t nsteps, const int32_t* steps,
+                                         int32_t max_rounds, const uint64_t* seeds, int32_t nboot, const uint64_t* boot_seeds,
+                                         int64_t* ncalls, double* logl_new, int32_t* nclusters, double* move_out, double* pair_out)
 {
     const char* who = "rvll_live_runs_step_clustered";
     int rc = use_device(h);
@@ -1526,9 +1613,10 @@ int rvll_live_runs_step_clustered(rvll_handle* h, const int32_t* runs, int32_t A
     }
     // 5. the walker groups (nested.py's _walk_groups): per run, the non-empty clusters of the start rows in label order, walkers in
     // their order inside a group; walk row e is walker perm[e] = a kdead + i
-    std::vector<int32_t> perm((size_t)K), grun((size_t)K), grid((size_t)K);
+    std::vector<int32_t> perm((size_t)K), grun((size_t)K), grid((size_t)K), gsteps;
     std::vector<double> glstar, gchol;
     std::vector<uint64_t> gseed;
+    std::vector<int64_t> gofs, gcnt;                     // every group's survivors: slots gofs .. + gcnt of the (label, rank) order
     {
         int64_t e = 0;
         std::vector<int32_t> wc((size_t)kdead);
@@ -1542,8 +1630,13 @@ int rvll_live_runs_step_clustered(rvll_handle* h, const int32_t* runs, int32_t A
             }
             for (size_t c = 0; c < k; ++c) first[c + 1] += first[c];
             std::vector<int32_t> gof(k, -1);             // group number of cluster c (-1: no walker starts in it)
+            long long offc = (long long)a * m;
             for (size_t c = 0; c < k; ++c) {
+                offc += c > 0 ? cnt[(size_t)a][c - 1] : 0;
                 if (first[c + 1] == first[c]) continue;
+                gofs.push_back(offc);
+                gcnt.push_back(cnt[(size_t)a][c]);
+                gsteps.push_back(steps ? steps[a] : nsteps);
                 gof[c] = (int32_t)glstar.size();
                 glstar.push_back(lstar[a]);
                 gseed.push_back(c == 0 ? seeds[a] : seeds[a] + (uint64_t)c * 0xD1B54A32D192ED03ull);
@@ -1573,11 +1666,36 @@ int rvll_live_runs_step_clustered(rvll_handle* h, const int32_t* runs, int32_t A
     HIP_TRY(rvll::launch_gather_rows(h->d_live_u, d_gstart, K, Di, h->d_walk_u, st));
     HIP_TRY(rvll::launch_gather_rows(h->d_live_theta, d_gstart, K, Di, h->d_walk_theta, st));
     HIP_TRY(rvll::launch_gather_rows(h->d_live_logl, d_gstart, K, 1, h->d_walk_logl, st));
+    const bool dist = move_out || pair_out;
+    double* d_wstart = nullptr;
+    int32_t* d_wgroup = nullptr;
+    if (dist) {                                          // the walkers' start rows and groups (walk_core may reuse d_walk_run)
+        rc = adapt_in_reserve(h, 8 * (size_t)K * D + 4 * (size_t)K + 16);
+        if (rc) return rc;
+        d_wstart = static_cast<double*>(h->d_adapt_in);
+        d_wgroup = reinterpret_cast<int32_t*>(d_wstart + (size_t)K * D);
+        HIP_TRY(hipMemcpyAsync(d_wstart, h->d_walk_u, 8 * (size_t)K * D, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_wgroup, grun.data(), 4 * (size_t)K, hipMemcpyHostToDevice, st));
+    }
+    if (steps) HIP_TRY(hipMemcpyAsync(h->d_run_nsteps, gsteps.data(), sizeof(int32_t) * gsteps.size(), hipMemcpyHostToDevice, st));
     rc = walk_upload_frame(h, nullptr, wrapped);         // (synchronises: the host tables above may go out of scope after it)
     if (rc) return rc;
-    RunWalk rw{grun.data(), grid.data(), std::vector<long long>((size_t)K, 0)};
+    RunWalk rw{grun.data(), grid.data(), std::vector<long long>((size_t)K, 0), steps ? gsteps.data() : nullptr};
     rc = walk_core(h, K, 0., nsteps, max_rounds, 0, 0, nullptr, &rw);
     if (rc) return rc;
+    // the distances: group g's survivors are the packed rows of its cluster (d_surv through the label sort's slots), its factor the
+    // walk's
+    std::vector<int32_t> tables;
+    std::vector<double> hmove, hpair;
+    if (dist) {
+        double *d_pair = nullptr, *d_move = nullptr;
+        rc = walk_distances_core(h, d_surv, d_slot_sorted, gofs, gcnt, h->d_run_chol, wrapped_mask(wrapped, Di), d_wstart, h->d_walk_u,
+                                 d_wgroup, K, &d_pair, &d_move, tables);
+        if (rc) return rc;
+        hmove.resize((size_t)K); hpair.resize(gofs.size());
+        HIP_TRY(hipMemcpyAsync(hmove.data(), d_move, 8 * (size_t)K, hipMemcpyDeviceToHost, st));
+        if (!gofs.empty()) HIP_TRY(hipMemcpyAsync(hpair.data(), d_pair, 8 * gofs.size(), hipMemcpyDeviceToHost, st));
+    }
     // births as rvll_live_runs_step: in the dead store's order (d_dying), each run's rows at its lstar
     HIP_TRY(rvll::launch_births_step(d_dying, K, kdead, h->d_dead_logl + h->dead_n + (kdead - 1), 0., h->d_live_birth,
                                      h->d_dead_birth + h->dead_n, st));
@@ -1591,6 +1709,8 @@ int rvll_live_runs_step_clustered(rvll_handle* h, const int32_t* runs, int32_t A
     for (int64_t e = 0; e < K; ++e) {
         logl_new[perm[(size_t)e]] = wl[(size_t)e];
         if (ncalls) ncalls[perm[(size_t)e] / kdead] += rw.row_calls[(size_t)e];
+        if (move_out) move_out[perm[(size_t)e]] = hmove[(size_t)e];
+        if (pair_out) pair_out[perm[(size_t)e]] = hpair[(size_t)grun[(size_t)e]];
     }
     for (int32_t a = 0; a < A; ++a) nclusters[a] = ncl[a];
     h->cl_A = A;
@@ -1605,6 +1725,36 @@ int rvll_live_runs_step_clustered(rvll_handle* h, const int32_t* runs, int32_t A
     for (int32_t a = 0; a < A; ++a) h->runs_dead[(size_t)runs[a]].emplace_back(h->dead_n + (long long)a * kdead, (long long)kdead);
     h->dead_n += K;
     return RVLL_OK;
+}
+
+int rvll_live_runs_step_clustered(rvll_handle* h, const int32_t* runs, int32_t A, int64_t kdead, const int32_t* ranks,
+                                  const double* lstar, const int32_t* wrapped, int32_t nsteps, int32_t max_rounds,
+                                  const uint64_t* seeds, int32_t nboot, const uint64_t* boot_seeds, int64_t* ncalls,
+                                  double* logl_new, int32_t* nclusters)
+{
+    return live_runs_step_clustered_impl(h, runs, A, kdead, ranks, lstar, wrapped, nsteps, nullptr, max_rounds, seeds, nboot, boot_seeds,
+                                         ncalls, logl_new, nclusters, nullptr, nullptr);
+}
+
+int rvll_live_runs_step_steps(rvll_handle* h, const int32_t* runs, int32_t A, int64_t kdead, const int32_t* ranks, const double* lstar,
+                              const int32_t* wrapped, const int32_t* nsteps, int32_t max_rounds, const uint64_t* seeds, int32_t clustered,
+                              int32_t nboot, const uint64_t* boot_seeds, int64_t* ncalls, double* logl_new, int32_t* nclusters,
+                              double* move, double* pair)
+{
+    if (A > 0 && !nsteps) return report_error(RVLL_E_INVALID, "rvll_live_runs_step_steps: null step table");
+    int32_t most = 0, least = A > 0 ? nsteps[0] : 0;
+    for (int32_t a = 0; a < A; ++a) {
+        if (nsteps[a] < 0 || nsteps[a] >= (1 << 18))
+            return report_error(RVLL_E_INVALID, "rvll_live_runs_step_steps: nsteps[%d] = %d out of range", (int)a, (int)nsteps[a]);
+        most = std::max(most, nsteps[a]);
+        least = std::min(least, nsteps[a]);
+    }
+    const int32_t* steps = least == most ? nullptr : nsteps;         // a uniform table is the scalar step
+    if (clustered)
+        return live_runs_step_clustered_impl(h, runs, A, kdead, ranks, lstar, wrapped, most, steps, max_rounds, seeds, nboot, boot_seeds,
+                                             ncalls, logl_new, nclusters, move, pair);
+    return live_runs_step_impl(h, runs, A, kdead, ranks, lstar, wrapped, most, steps, max_rounds, seeds, ncalls, logl_new, nullptr,
+                               move, pair);
 }
 
 int rvll_live_runs_clusters(rvll_handle* h, int32_t a, int64_t* nsurv, int32_t* nclusters, int32_t* labels, double* scale, double* factors,

@@ -323,7 +323,8 @@ class GpuRVModel:
         """The walks of R independent runs in ONE device walk (rvll_slice_walk_runs).  Rows run_start[r] .. run_start[r + 1]
         of cube / theta / logl are the walkers of run r, which walks inside logL > lstar[r] with the whitening factor
         chol[r] ([R, ndim, ndim]) and seed seeds[r].  Returns (cube, theta, logl, ncalls[R]); run r's rows and ncalls[r] are
-        bit for bit those of slice_walk(its rows, lstar[r], chol[r], wrapped, nsteps, max_rounds, seeds[r])."""
+        bit for bit those of slice_walk(its rows, lstar[r], chol[r], wrapped, nsteps, max_rounds, seeds[r]).  nsteps is an int
+        (every run) or one count per run ([R]: rvll_slice_walk_runs_steps, run r then walks as slice_walk(..., nsteps[r], ...))."""
         cube = np.array(self._theta2d(cube), dtype=np.float64, order="C")
         theta = np.array(self._theta2d(theta), dtype=np.float64, order="C")
         logl = np.array(logl, dtype=np.float64).reshape(-1)
@@ -343,12 +344,42 @@ class GpuRVModel:
             raise ValueError("chol must be [runs, ndim, ndim]")
         wr = None if wrapped is None else np.ascontiguousarray(np.asarray(wrapped, dtype=bool).astype(np.int32))
         ncalls = np.zeros(nrun, dtype=np.int64)
+        if np.ndim(nsteps) != 0:
+            steps = np.ascontiguousarray(nsteps, dtype=np.int32).reshape(-1)
+            if steps.shape[0] != nrun:
+                raise ValueError("nsteps needs one entry per run (or one int for all)")
+            _abi.check(self._lib.rvll_slice_walk_runs_steps(
+                self._h, _abi.as_dp(cube), _abi.as_dp(theta), _abi.as_dp(logl),
+                run_start.ctypes.data_as(C.POINTER(C.c_int64)), nrun, _abi.as_dp(lstar), _abi.as_dp(chol),
+                seeds.ctypes.data_as(C.POINTER(C.c_uint64)), _abi.as_ip(wr) if wr is not None else None,
+                _abi.as_ip(steps), int(max_rounds), ncalls.ctypes.data_as(C.POINTER(C.c_int64))))
+            return cube, theta, logl, ncalls
         _abi.check(self._lib.rvll_slice_walk_runs(
             self._h, _abi.as_dp(cube), _abi.as_dp(theta), _abi.as_dp(logl),
             run_start.ctypes.data_as(C.POINTER(C.c_int64)), nrun, _abi.as_dp(lstar), _abi.as_dp(chol),
             seeds.ctypes.data_as(C.POINTER(C.c_uint64)), _abi.as_ip(wr) if wr is not None else None,
             int(nsteps), int(max_rounds), ncalls.ctypes.data_as(C.POINTER(C.c_int64))))
         return cube, theta, logl, ncalls
+
+    def walk_distances_runs(self, survivors, group_start, factors, wrapped, starts, ends, walker_group):
+        """The distances of the step-count adaptation on the device (rvll_walk_distances_runs): rows
+        group_start[g] .. group_start[g + 1] of survivors ([N, ndim] unit-cube rows) are group g, whitened by factors[g]
+        ([G, ndim, ndim]); walker k went from starts[k] to ends[k] in group walker_group[k].  Returns (pair [G], move [K]) —
+        adapt.walk_distances_runs's: move bit for bit, pair to round-off (its summation order)."""
+        from .adapt import check_args
+        survivors, group_start, factors, wrapped, starts, ends, walker_group = check_args(
+            self._theta2d(survivors), group_start, factors, wrapped, starts, ends, walker_group)
+        if survivors.shape[1] != self.ndim:
+            raise ValueError("rows must have ndim columns")
+        G, K = group_start.shape[0] - 1, starts.shape[0]
+        wr = None if wrapped is None else np.ascontiguousarray(wrapped.astype(np.int32))
+        pair = np.empty(G, dtype=np.float64)
+        move = np.empty(K, dtype=np.float64)
+        _abi.check(self._lib.rvll_walk_distances_runs(
+            self._h, _abi.as_dp(survivors), group_start.ctypes.data_as(C.POINTER(C.c_int64)), G, _abi.as_dp(factors),
+            _abi.as_ip(wr) if wr is not None else None, _abi.as_dp(starts), _abi.as_dp(ends), _abi.as_ip(walker_group), K,
+            _abi.as_dp(pair), _abi.as_dp(move)))
+        return pair, move
 
     def cluster_runs(self, cube, run_start, scale, wrapped=None, nboot=30, seeds=()):
         """MLFriends clustering of R independent row sets in one device call (rvll_cluster_runs).  Rows
@@ -507,11 +538,32 @@ class GpuRVModel:
                                                  _abi.as_dp(top)))
         return dead, lstar, top
 
-    def live_runs_step(self, runs, kdead, ranks, lstar, wrapped=None, nsteps=10, max_rounds=200, seeds=(), return_chol=False):
+    def _live_runs_step_steps(self, runs, kdead, ranks, lstar, wr, nsteps, max_rounds, seeds, clustered, nboot, boot_seeds,
+                              return_distances):
+        """rvll_live_runs_step_steps (the arguments checked by the caller): (logl_new, ncalls, nclusters or None, move, pair)."""
+        A = runs.size
+        steps = np.ascontiguousarray(np.broadcast_to(np.asarray(nsteps, dtype=np.int32), (A,)))
+        logl_new = np.empty((A, kdead), dtype=np.float64)
+        ncalls = np.zeros(A, dtype=np.int64)
+        nclusters = np.zeros(A, dtype=np.int32) if clustered else None
+        move = np.empty((A, kdead), dtype=np.float64) if return_distances else None
+        pair = np.empty((A, kdead), dtype=np.float64) if return_distances else None
+        _abi.check(self._lib.rvll_live_runs_step_steps(
+            self._h, _abi.as_ip(runs), A, kdead, _abi.as_ip(ranks), _abi.as_dp(lstar), _abi.as_ip(wr) if wr is not None else None,
+            _abi.as_ip(steps), int(max_rounds), seeds.ctypes.data_as(C.POINTER(C.c_uint64)), 1 if clustered else 0, int(nboot),
+            boot_seeds.ctypes.data_as(C.POINTER(C.c_uint64)) if clustered else None, ncalls.ctypes.data_as(C.POINTER(C.c_int64)),
+            _abi.as_dp(logl_new), _abi.as_ip(nclusters) if clustered else None, _abi.as_dp(move) if return_distances else None,
+            _abi.as_dp(pair) if return_distances else None))
+        return logl_new, ncalls, nclusters, move, pair
+
+    def live_runs_step(self, runs, kdead, ranks, lstar, wrapped=None, nsteps=10, max_rounds=200, seeds=(), return_chol=False,
+                       return_distances=False):
         """One iteration of every listed run on the resident ensemble (rvll_live_runs_step), after live_runs_sort of the same
         runs: ranks [A, kdead] among each run's survivors, lstar [A] as live_runs_sort returned them, seeds [A].  Returns
         (logl_new [A, kdead], ncalls [A]) (+ the whitening factors [A, ndim, ndim] with return_chol); run a's part is bit for
-        bit what live_step(None, kdead, ranks[a], lstar[a], ..., seeds[a]) gives a model that holds only that run."""
+        bit what live_step(None, kdead, ranks[a], lstar[a], ..., seeds[a]) gives a model that holds only that run.
+        nsteps may be one count per run ([A]), and return_distances=True appends (move, pair) [A, kdead], the step-count
+        adaptation's distances (rvll_live_runs_step_steps); neither goes with return_chol."""
         runs = self._runs_list(runs)
         kdead = int(kdead)
         A = runs.size
@@ -523,6 +575,14 @@ class GpuRVModel:
         if lstar.shape != (A,) or seeds.shape != (A,):
             raise ValueError("lstar and seeds need one entry per run")
         wr = None if wrapped is None else np.ascontiguousarray(np.asarray(wrapped, dtype=bool).astype(np.int32))
+        if np.ndim(nsteps) != 0 or return_distances:
+            if return_chol:
+                raise ValueError("return_chol does not go with a step table or return_distances")
+            if np.ndim(nsteps) != 0 and np.shape(nsteps) != (A,):
+                raise ValueError("nsteps needs one entry per run (or one int for all)")
+            logl_new, ncalls, _, move, pair = self._live_runs_step_steps(runs, kdead, ranks, lstar, wr, nsteps, max_rounds, seeds,
+                                                                         False, 0, None, return_distances)
+            return (logl_new, ncalls, move, pair) if return_distances else (logl_new, ncalls)
         logl_new = np.empty((A, kdead), dtype=np.float64)
         ncalls = np.zeros(A, dtype=np.int64)
         used = np.empty((A, self.ndim, self.ndim)) if return_chol else None
@@ -533,10 +593,11 @@ class GpuRVModel:
         return (logl_new, ncalls, used) if return_chol else (logl_new, ncalls)
 
     def live_runs_step_clustered(self, runs, kdead, ranks, lstar, wrapped=None, nsteps=10, max_rounds=200, seeds=(), nboot=30,
-                                 boot_seeds=()):
+                                 boot_seeds=(), return_distances=False):
         """live_runs_step with the survivors of every listed run clustered on the device (rvll_live_runs_step_clustered; DESIGN
         §4e): run a's walkers are grouped by the cluster of their start row and whitened by that cluster's covariance, the
-        clustering bootstrapped with boot_seeds[a].  Returns (logl_new [A, kdead] in walker order, ncalls [A], nclusters [A])."""
+        clustering bootstrapped with boot_seeds[a].  Returns (logl_new [A, kdead] in walker order, ncalls [A], nclusters [A]).
+        nsteps may be one count per run ([A]); return_distances=True appends (move, pair) [A, kdead] (rvll_live_runs_step_steps)."""
         runs = self._runs_list(runs)
         kdead = int(kdead)
         A = runs.size
@@ -549,6 +610,12 @@ class GpuRVModel:
         if lstar.shape != (A,) or seeds.shape != (A,) or boot_seeds.shape != (A,):
             raise ValueError("lstar, seeds and boot_seeds need one entry per run")
         wr = None if wrapped is None else np.ascontiguousarray(np.asarray(wrapped, dtype=bool).astype(np.int32))
+        if np.ndim(nsteps) != 0 or return_distances:
+            if np.ndim(nsteps) != 0 and np.shape(nsteps) != (A,):
+                raise ValueError("nsteps needs one entry per run (or one int for all)")
+            logl_new, ncalls, nclusters, move, pair = self._live_runs_step_steps(runs, kdead, ranks, lstar, wr, nsteps, max_rounds,
+                                                                                 seeds, True, nboot, boot_seeds, return_distances)
+            return (logl_new, ncalls, nclusters, move, pair) if return_distances else (logl_new, ncalls, nclusters)
         logl_new = np.empty((A, kdead), dtype=np.float64)
         ncalls = np.zeros(A, dtype=np.int64)
         nclusters = np.zeros(A, dtype=np.int32)

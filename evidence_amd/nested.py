@@ -36,6 +36,8 @@ class NestedResult:
     kbatch: int = None           # kbatch deaths per iteration (run_nested: 1)
     logl_birth: np.ndarray = None  # per row (the order of logl): the contour it was drawn above — -inf for an initial point, else the
                                    # lstar of the iteration that drew it (the insertion-index test reads it; insertion.py)
+    nsteps_trace: np.ndarray = None  # adaptive_nsteps: the step count every iteration walked with (None when off; adapt.py)
+    far_fraction: np.ndarray = None  # adaptive_nsteps: the far walkers' share of the counted ones per iteration, NaN where none counted
 
 
 def _logaddexp_many(x):
@@ -268,6 +270,17 @@ def _check_resident_clustering(live, clusterer, live_chol, nboot):
         raise ValueError(f"nboot must be in [0, {MAX_BOOT}]")
 
 
+def _check_resident_adaptive(live, distances, live_chol):
+    """The arguments that adaptive_nsteps with the resident live sets (live=) refuses."""
+    if not hasattr(live, "_live_runs_step_steps"):
+        raise ValueError("adaptive_nsteps with live= needs the resident ensemble's step with per-run step counts "
+                         "(GpuRVModel.live_runs_step(nsteps=[...], return_distances=True))")
+    if distances is not None:
+        raise ValueError("distances= does not apply with live=: the resident step measures the walkers on the device")
+    if live_chol != "device":
+        raise ValueError('live_chol="host" does not work with adaptive_nsteps: the resident step whitens on the device')
+
+
 def _default_clusterer(clusterer):
     if clusterer is not None:
         return clusterer
@@ -275,12 +288,48 @@ def _default_clusterer(clusterer):
     return cluster_runs
 
 
+# ---- step-count adaptation (adaptive_nsteps="move-distance"; DESIGN §4h, adapt.py) -----------------------------------------
+def _adapt_setup(adaptive_nsteps, nsteps, min_nsteps, max_nsteps, distances):
+    """(min_nsteps, max_nsteps, distances) of an adaptive run, or None when adaptation is off."""
+    if adaptive_nsteps is None:
+        return None
+    from . import adapt
+    lo, hi = adapt.check_settings(adaptive_nsteps, nsteps, min_nsteps, max_nsteps)
+    return lo, hi, (distances if distances is not None else adapt.walk_distances_runs)
+
+
+def _adapt_counts(entries, distances, wrapped):
+    """The counted and far walkers of every entry (one run's iteration each) from ONE `distances` call: an entry is (survivors
+    [n, ndim], their cluster labels or None, the factors by label, every walker's label, its start rows, its end rows).  A
+    group is a label that has walkers, in label order; its members are the survivors with that label.  Returns (counted [E],
+    far [E])."""
+    from .adapt import far_counts
+    surv, gstart, facs, wg, st, en, wr = [], [0], [], [], [], [], []
+    for e, (ua, lab, factors, cw, starts, ends) in enumerate(entries):
+        cw = np.asarray(cw, dtype=np.intp)
+        groups = np.unique(cw)
+        base = len(facs)
+        for g in groups:
+            rows = ua if lab is None else ua[lab == g]
+            surv.append(rows)
+            gstart.append(gstart[-1] + len(rows))
+            facs.append(factors[g])
+        wg.append(base + np.searchsorted(groups, cw))
+        st.append(starts); en.append(ends); wr.append(np.full(len(cw), e))
+    wg = np.concatenate(wg).astype(np.int32)
+    pair, move = distances(np.concatenate(surv), np.array(gstart, dtype=np.int64), np.stack(facs), wrapped,
+                           np.concatenate(st), np.concatenate(en), wg)
+    return far_counts(pair, move, wg, np.concatenate(wr), len(entries))
+
+
 def run_nested_slice(prior: Callable, loglike: Callable, ndim: int, nlive: Optional[int] = None, kbatch: Optional[int] = None,
                      nsteps: Optional[int] = None, dlogz: float = 0.5, max_iter: int = 10_000_000,
                      max_calls: int = 50_000_000, wrapped=None, seed: int = 0,
                      prior_loglike: Optional[Callable] = None, walker: Optional[Callable] = None,
                      live=None, live_chol: str = "device", clustering: bool = False, nboot: int = 30,
-                     clusterer: Optional[Callable] = None, walker_runs: Optional[Callable] = None) -> NestedResult:
+                     clusterer: Optional[Callable] = None, walker_runs: Optional[Callable] = None,
+                     adaptive_nsteps: Optional[str] = None, min_nsteps: Optional[int] = None, max_nsteps: Optional[int] = None,
+                     distances: Optional[Callable] = None) -> NestedResult:
     """Nested sampling with `kbatch` deaths per iteration and batched hit-and-run slice sampling.
 
     `prior_loglike(cubes) -> (theta, logl)`, if given, replaces the prior + loglike pair inside the loop
@@ -316,10 +365,25 @@ def run_nested_slice(prior: Callable, loglike: Callable, ndim: int, nlive: Optio
     With `live` as well, the clustering runs on the device (GpuRVModel.live_runs_step_clustered): the run is the
     one-run resident ENSEMBLE, run_nested_ensemble(None, None, ndim, [seed], live=live, clustering=True, ...)[0], with the
     ensemble's draws, results and `timing` keys; the model is left holding that ensemble (live_runs_*), not a one-run live set.
-    `clusterer` (the device clusters) and live_chol="host" (the device whitens) are refused then."""
+    `clusterer` (the device clusters) and live_chol="host" (the device whitens) are refused then.
+
+    adaptive_nsteps="move-distance" (UltraNest's adaptive_nsteps='move-distance'; DESIGN §4h, adapt.py) changes every run's
+    step count from one iteration to the next by how far its walkers got from their start rows, measured against the mean
+    distance between the survivors of their group, within [min_nsteps (default: nsteps), max_nsteps (default 1000)].
+    `distances` (adapt.walk_distances_runs by default, or GpuRVModel.walk_distances_runs) gives those distances, one call per
+    iteration.  With `live` the run is the one-run resident ensemble, whose step measures the walkers on the device
+    (`distances` is refused).  The rule draws nothing, so every draw is that of the same run without adaptation;
+    the results gain `nsteps_trace` and `far_fraction`."""
     if clustering and walker is not None:
         raise ValueError("walker= has one whitening factor for all walkers: with clustering=True pass walker_runs= "
                          "(GpuRVModel.slice_walk_runs)")
+    if adaptive_nsteps is not None and live is not None:
+        _check_resident_adaptive(live, distances, live_chol)
+        if clustering:
+            _check_resident_clustering(live, clusterer, live_chol, nboot)
+        return _ensemble_resident(live, ndim, [int(seed)], nlive, kbatch, nsteps, dlogz, max_iter, max_calls, wrapped,
+                                  clustering=clustering, nboot=nboot, adaptive_nsteps=adaptive_nsteps, min_nsteps=min_nsteps,
+                                  max_nsteps=max_nsteps)[0]
     if clustering and live is not None:
         _check_resident_clustering(live, clusterer, live_chol, nboot)
         return _ensemble_resident(live, ndim, [int(seed)], nlive, kbatch, nsteps, dlogz, max_iter, max_calls, wrapped,
@@ -336,6 +400,8 @@ def run_nested_slice(prior: Callable, loglike: Callable, ndim: int, nlive: Optio
     if not 1 <= kbatch < nlive:
         raise ValueError("need 1 <= kbatch < nlive")
     nsteps = int(nsteps or defaults["nsteps"])
+    adapting = _adapt_setup(adaptive_nsteps, nsteps, min_nsteps, max_nsteps, distances)
+    trace, fars = [], []
     wrapped = None if wrapped is None else np.asarray(wrapped, dtype=bool)
     u = rng.random((nlive, ndim))
     if live is not None:
@@ -421,8 +487,10 @@ def run_nested_slice(prior: Callable, loglike: Callable, ndim: int, nlive: Optio
                 break
             continue
         wu, wt, wl = u[start], theta[start], logl[start]
+        starts = wu.copy() if adapting else None
         factors = [chol]
         cw = np.zeros(kbatch, dtype=np.intp)
+        labels = None
         if clustering:
             ua = u[alive]
             labels, ncl, _ = clusterer(ua, [0, len(ua)], _cluster_scale(ua)[None, :], wrapped, nboot,
@@ -471,6 +539,13 @@ def run_nested_slice(prior: Callable, loglike: Callable, ndim: int, nlive: Optio
                 todo = rej
                 rounds += 1
         u[dead], theta[dead], logl[dead] = wu, wt, wl
+        if adapting:
+            from .adapt import far_fraction, next_nsteps
+            c, f = _adapt_counts([(u[alive], None if labels is None else np.asarray(labels, dtype=np.intp), factors, cw, starts,
+                                   wu)], adapting[2], wrapped)
+            trace.append(nsteps)
+            fars.append(float(far_fraction(f[0], c[0])))
+            nsteps = next_nsteps(nsteps, int(f[0]), int(c[0]), adapting[0], adapting[1])
         if np.max(logl) + logx < logz + np.log(np.expm1(dlogz)):
             break
     if device_order:
@@ -498,7 +573,9 @@ def run_nested_slice(prior: Callable, loglike: Callable, ndim: int, nlive: Optio
         all_birth = np.concatenate(dead_birth + [birth])
     return NestedResult(float(logz_final), float(np.sqrt(max(h, 0.0) / nlive)), it, ncall, float(h),
                         all_theta, all_logl, all_logw, timing, None if nclusters is None else np.array(nclusters, dtype=np.int64),
-                        nlive=nlive, kbatch=kbatch, logl_birth=all_birth)
+                        nlive=nlive, kbatch=kbatch, logl_birth=all_birth,
+                        nsteps_trace=np.array(trace, dtype=np.int64) if adapting else None,
+                        far_fraction=np.array(fars, dtype=np.float64) if adapting else None)
 
 
 class _EnsembleRun:
@@ -517,13 +594,18 @@ class _EnsembleRun:
         self.done = False
         self.timing = {"host_s": 0.0, "walk_s": 0.0, "turns": 0}
         self.nclusters = []
+        self.nsteps = None                          # adaptive_nsteps: this run's step count, its trace and far fractions
+        self.trace, self.fars = [], []
+        self.groups = None                          # adaptive_nsteps: (survivors, labels, factors, walker labels) of the turn
 
 
 def run_nested_ensemble(prior: Callable, loglike: Callable, ndim: int, seeds, nlive: Optional[int] = None,
                         kbatch: Optional[int] = None, nsteps: Optional[int] = None, dlogz: float = 0.5,
                         max_iter: int = 10_000_000, max_calls: int = 50_000_000, wrapped=None,
                         walker_runs: Optional[Callable] = None, clustering: bool = False, nboot: int = 30,
-                        clusterer: Optional[Callable] = None, live=None) -> list:
+                        clusterer: Optional[Callable] = None, live=None, adaptive_nsteps: Optional[str] = None,
+                        min_nsteps: Optional[int] = None, max_nsteps: Optional[int] = None,
+                        distances: Optional[Callable] = None) -> list:
     """len(seeds) independent runs of run_nested_slice in lockstep, their walks in ONE call per iteration.
 
     The reference's FIP workflow repeats independent runs of every model and takes the median and spread of ln Z over them
@@ -553,17 +635,26 @@ def run_nested_ensemble(prior: Callable, loglike: Callable, ndim: int, seeds, nl
     walker_runs.  With clustering=True every step clusters the survivors of every running run on the device
     (GpuRVModel.live_runs_step_clustered): the runs' draws are those of the unclustered ensemble, the bootstrap seed
     of a run's iteration is the host clustered path's, and result[r] is run_nested_slice(None, None, ndim, seed=seeds[r],
-    live=..., clustering=True), with `nclusters`; `clusterer` is refused (the device clusters)."""
+    live=..., clustering=True), with `nclusters`; `clusterer` is refused (the device clusters).
+
+    adaptive_nsteps="move-distance" (with min_nsteps, max_nsteps, distances as run_nested_slice takes them): every run keeps
+    its own step count, the walk call gets them per group (an int when they are all equal), and one `distances` call per
+    iteration measures the walkers of every run; result[r] is run_nested_slice(..., adaptive_nsteps=...) for seed r, bit for
+    bit.  With live= the resident step takes the per-run counts and returns the distances from the device rows
+    (GpuRVModel.live_runs_step(nsteps=[...], return_distances=True)); result[r] is then the standalone resident adaptive run."""
     seeds = [int(s) for s in seeds]
     if not seeds:
         raise ValueError("need at least one seed")
+    if adaptive_nsteps is not None and live is not None:
+        _check_resident_adaptive(live, distances, "device")
     if live is not None:
         if clustering:
             _check_resident_clustering(live, clusterer, "device", nboot)
         if walker_runs is not None:
             raise ValueError("pass walker_runs= or live=, not both")
         return _ensemble_resident(live, ndim, seeds, nlive, kbatch, nsteps, dlogz, max_iter, max_calls, wrapped,
-                                  clustering=clustering, nboot=nboot)
+                                  clustering=clustering, nboot=nboot, adaptive_nsteps=adaptive_nsteps, min_nsteps=min_nsteps,
+                                  max_nsteps=max_nsteps)
     if walker_runs is None:
         raise ValueError("walker_runs is required (GpuRVModel.slice_walk_runs)")
     if clustering:
@@ -574,8 +665,11 @@ def run_nested_ensemble(prior: Callable, loglike: Callable, ndim: int, seeds, nl
     if not 1 <= kbatch < nlive:
         raise ValueError("need 1 <= kbatch < nlive")
     nsteps = int(nsteps or defaults["nsteps"])
+    adapting = _adapt_setup(adaptive_nsteps, nsteps, min_nsteps, max_nsteps, distances)
     wrapped = None if wrapped is None else np.asarray(wrapped, dtype=bool)
     runs = [_EnsembleRun(s, nlive, ndim) for s in seeds]
+    for r in runs:
+        r.nsteps = nsteps
     theta = np.asarray(prior(np.concatenate([r.u for r in runs])), dtype=np.float64)
     logl = np.asarray(loglike(theta), dtype=np.float64)
     for i, r in enumerate(runs):
@@ -608,20 +702,29 @@ def run_nested_ensemble(prior: Callable, loglike: Callable, ndim: int, seeds, nl
             r.timing["host_s"] += time.perf_counter() - t0
         if not turn:
             break
+        if adapting:
+            starts = [r.u[st] for r, _d, st, *_x in turn]
         if clustering:
-            turn = _cluster_turn(turn, clusterer, wrapped, nboot)
+            turn = _cluster_turn(turn, clusterer, wrapped, nboot, keep_groups=bool(adapting))
         else:
+            if adapting:
+                for r, _d, _st, _ls, chol, _sd, alive, _pick in turn:
+                    r.groups = (r.u[alive], None, [chol], np.zeros(kbatch, dtype=np.intp))
             turn = [t[:6] + (np.arange(kbatch), [kbatch], [t[4]], [t[5]]) for t in turn]
         # (run, dead rows, start rows, lstar, chol, walk seed, walker order, group sizes, group factors, group seeds)
         sizes = np.concatenate([t[7] for t in turn])
         run_start = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        steps = nsteps
+        if adapting:
+            steps = np.repeat([t[0].nsteps for t in turn], [len(t[7]) for t in turn]).astype(np.int32)
+            steps = int(steps[0]) if np.all(steps == steps[0]) else steps
         t0 = time.perf_counter()
         wu, wt, wl, used = walker_runs(np.concatenate([r.u[st[wo]] for r, _, st, _, _, _, wo, *_ in turn]),
                                        np.concatenate([r.theta[st[wo]] for r, _, st, _, _, _, wo, *_ in turn]),
                                        np.concatenate([r.logl[st[wo]] for r, _, st, _, _, _, wo, *_ in turn]),
                                        run_start, np.repeat([t[3] for t in turn], [len(t[7]) for t in turn]),
                                        np.stack([f for t in turn for f in t[8]]),
-                                       wrapped, nsteps, 200, [s for t in turn for s in t[9]])
+                                       wrapped, steps, 200, [s for t in turn for s in t[9]])
         t_walk = time.perf_counter() - t0
         g = 0
         for j, (r, dead, _st, _ls, _ch, _sd, wo, gsizes, *_rest) in enumerate(turn):
@@ -636,6 +739,18 @@ def run_nested_ensemble(prior: Callable, loglike: Callable, ndim: int, seeds, nl
             r.timing["walk_s"] += t_walk
             r.timing["turns"] += 1
             r.timing["host_s"] += time.perf_counter() - t0
+        if adapting:
+            from .adapt import far_fraction, next_nsteps
+            t0 = time.perf_counter()
+            c, f = _adapt_counts([t[0].groups + (starts[j], t[0].u[t[1]]) for j, t in enumerate(turn)], adapting[2], wrapped)
+            dt = (time.perf_counter() - t0) / len(turn)
+            for j, t in enumerate(turn):
+                r = t[0]
+                r.trace.append(r.nsteps)
+                r.fars.append(float(far_fraction(f[j], c[j])))
+                r.nsteps = next_nsteps(r.nsteps, int(f[j]), int(c[j]), adapting[0], adapting[1])
+                r.groups = None
+                r.timing["host_s"] += dt
     out = []
     for r in runs:
         logw_live = r.logx - np.log(nlive) + r.logl
@@ -646,14 +761,16 @@ def run_nested_ensemble(prior: Callable, loglike: Callable, ndim: int, seeds, nl
         out.append(NestedResult(float(logz_final), float(np.sqrt(max(r.h, 0.0) / nlive)), r.it, r.ncall, float(r.h),
                                 all_theta, all_logl, all_logw, r.timing,
                                 np.array(r.nclusters, dtype=np.int64) if clustering else None, nlive=nlive, kbatch=kbatch,
-                                logl_birth=np.concatenate(r.dead_birth + [r.birth])))
+                                logl_birth=np.concatenate(r.dead_birth + [r.birth]),
+                                nsteps_trace=np.array(r.trace, dtype=np.int64) if adapting else None,
+                                far_fraction=np.array(r.fars, dtype=np.float64) if adapting else None))
     return out
 
 
-def _cluster_turn(turn, clusterer, wrapped, nboot):
+def _cluster_turn(turn, clusterer, wrapped, nboot, keep_groups=False):
     """run_nested_ensemble(clustering=True): the survivors of every run of the turn clustered in ONE clusterer call, then per
     run its walkers grouped by cluster as run_nested_slice groups them.  Appends the group order, sizes, factors and seeds
-    to every turn entry."""
+    to every turn entry; keep_groups: leaves (survivors, labels, factors, walker labels) in every run's `groups`."""
     t0 = time.perf_counter()
     uas = [r.u[alive] for r, *_x, alive, _pick in turn]
     run_start = np.concatenate([[0], np.cumsum([len(ua) for ua in uas])]).astype(np.int64)
@@ -668,24 +785,31 @@ def _cluster_turn(turn, clusterer, wrapped, nboot):
         r.nclusters.append(int(ncl[j]))
         factors = _cluster_factors(uas[j], lab, int(ncl[j]), chol)
         wo, sizes, gf, gseeds = _walk_groups(lab[pick], factors, wseed)
+        if keep_groups:
+            r.groups = (uas[j], lab, factors, lab[pick])
         out.append((r, dead, start, lstar, chol, wseed, wo, sizes, gf, gseeds))
         r.timing["host_s"] += dt + time.perf_counter() - t0
     return out
 
 
-def _ensemble_resident(live, ndim, seeds, nlive, kbatch, nsteps, dlogz, max_iter, max_calls, wrapped, clustering=False, nboot=30):
+def _ensemble_resident(live, ndim, seeds, nlive, kbatch, nsteps, dlogz, max_iter, max_calls, wrapped, clustering=False, nboot=30,
+                       adaptive_nsteps=None, min_nsteps=None, max_nsteps=None):
     """run_nested_ensemble(live=model): the device_order branch of run_nested_slice for every seed, the runs' live sets resident
     side by side (run r = rows r nlive .. r nlive + nlive - 1 of the ensemble), their bookkeeping vectorised across runs.
     clustering: the clustered step, with run r's bootstrap seed (seeds[r] _BOOT_MUL + deaths after this iteration) mod 2^64 —
-    what run_nested_slice's host clustered path passes."""
+    what run_nested_slice's host clustered path passes.  adaptive_nsteps: every run walks with its own step count, and the step
+    returns the walkers' distances from the device rows (GpuRVModel.live_runs_step(nsteps=[...], return_distances=True))."""
     defaults = ultranest_defaults(ndim)
     nlive = int(nlive or defaults["nlive"])
     kbatch = int(kbatch or max(1, nlive // 4))
     if not 1 <= kbatch < nlive:
         raise ValueError("need 1 <= kbatch < nlive")
     nsteps = int(nsteps or defaults["nsteps"])
+    adapting = _adapt_setup(adaptive_nsteps, nsteps, min_nsteps, max_nsteps, None)
     wrapped = None if wrapped is None else np.asarray(wrapped, dtype=bool)
     R = len(seeds)
+    steps = np.full(R, nsteps, dtype=np.int64)
+    trace, fars = [[] for _ in range(R)], [[] for _ in range(R)]
     rngs = [np.random.default_rng(s) for s in seeds]
     live.live_runs_init(np.concatenate([g.random((nlive, ndim)) for g in rngs]), R)
     ncall = np.full(R, nlive, dtype=np.int64)
@@ -709,14 +833,27 @@ def _ensemble_resident(live, ndim, seeds, nlive, kbatch, nsteps, dlogz, max_iter
             ranks[j] = rngs[r].integers(0, nlive - kbatch, kbatch)
             walk_seeds.append(int(rngs[r].integers(0, 2 ** 62)))
         t1 = time.perf_counter()
+        st = steps[act] if adapting else nsteps
+        dist = {"return_distances": True} if adapting else {}
         if clustering:
             boot = [(seeds[r] * _BOOT_MUL + it + kbatch) & _M64 for r in act]
-            wl, used, ncl = live.live_runs_step_clustered(act, kbatch, ranks, lstar, wrapped, nsteps, 200, walk_seeds, nboot, boot)
+            wl, used, ncl, *md = live.live_runs_step_clustered(act, kbatch, ranks, lstar, wrapped, st, 200, walk_seeds, nboot, boot, **dist)
             for j, r in enumerate(act):
                 ncls[r].append(int(ncl[j]))
         else:
-            wl, used = live.live_runs_step(act, kbatch, ranks, lstar, wrapped, nsteps, 200, walk_seeds)
+            wl, used, *md = live.live_runs_step(act, kbatch, ranks, lstar, wrapped, st, 200, walk_seeds, **dist)
         t2 = time.perf_counter()
+        if adapting:
+            from .adapt import far_fraction, next_nsteps
+            move, pair = md
+            counted = ~np.isnan(pair)
+            c = np.count_nonzero(counted, axis=1)
+            f = np.count_nonzero(counted & (move > pair), axis=1)
+            ff = far_fraction(f, c)
+            for j, r in enumerate(act):
+                trace[r].append(int(steps[r]))
+                fars[r].append(float(ff[j]))
+            steps[act] = next_nsteps(steps[act], f, c, adapting[0], adapting[1])
         logw, logz[act], h[act], logx = _deaths_runs(logz[act], h[act], logx, dl, nlive, kbatch)
         turns.append((act, dl, logw))
         it += kbatch
@@ -750,5 +887,7 @@ def _ensemble_resident(live, ndim, seeds, nlive, kbatch, nsteps, dlogz, max_iter
         out.append(NestedResult(float(logz_final), float(np.sqrt(max(h[r], 0.0) / nlive)), int(niter[r]), int(ncall[r]), float(h[r]),
                                 all_theta, all_logl, all_logw, timing[r],
                                 np.array(ncls[r], dtype=np.int64) if clustering else None, nlive=nlive, kbatch=kbatch,
-                                logl_birth=all_birth))
+                                logl_birth=all_birth,
+                                nsteps_trace=np.array(trace[r], dtype=np.int64) if adapting else None,
+                                far_fraction=np.array(fars[r], dtype=np.float64) if adapting else None))
     return out

@@ -57,7 +57,9 @@ extern "C" {
                                   0.5: rvll_live_runs_* (resident ensemble)
                                   0.6: rvll_live_runs_step_clustered, rvll_live_runs_clusters
                                   0.7: rvll_shrinkage_replicates
-                                  0.8: rvll_live_births, rvll_live_runs_births, rvll_insertion_indexes */
+                                  0.8: rvll_live_births, rvll_live_runs_births, rvll_insertion_indexes;
+                                       additions within 0.8 (new symbols only, no signature changed):
+                                       rvll_slice_walk_runs_steps, rvll_walk_distances_runs, rvll_live_runs_step_steps */
 
 /* ---- error codes ------------------------------------------------------ */
 #define RVLL_OK             0
@@ -269,6 +271,29 @@ int rvll_slice_walk_runs(rvll_handle* h, double* cube, double* theta, double* lo
                          const double* lstar /*[R]*/, const double* chol /*[R, ndim, ndim]*/, const uint64_t* seed /*[R]*/,
                          const int32_t* wrapped /*[ndim] or NULL*/, int32_t nsteps, int32_t max_rounds,
                          int64_t* ncalls /*[R] out*/);
+/* rvll_slice_walk_runs with a step count per run: run r makes nsteps[r] moves (0 <= nsteps[r] < 2^18), and its rows, theta,
+ * log-L and ncalls[r] are bit for bit those of rvll_slice_walk(rows of run r, ..., nsteps[r], ...).  A uniform table is
+ * rvll_slice_walk_runs itself; otherwise every row stops after its run's count in the single-kernel forms (the rounds form,
+ * whose direction table holds the same number of moves for every walker, is not taken).  For the step-count adaptation
+ * of evidence_amd/adapt.py.                                                                                  */
+int rvll_slice_walk_runs_steps(rvll_handle* h, double* cube, double* theta, double* logl /*[K, ndim], [K, ndim], [K]*/,
+                               const int64_t* run_start /*[R + 1]*/, int32_t R,
+                               const double* lstar /*[R]*/, const double* chol /*[R, ndim, ndim]*/, const uint64_t* seed /*[R]*/,
+                               const int32_t* wrapped /*[ndim] or NULL*/, const int32_t* nsteps /*[R]*/, int32_t max_rounds,
+                               int64_t* ncalls /*[R] out*/);
+/* The distances of the step-count adaptation (definition: DESIGN §4h, evidence_amd/adapt.py).  Rows group_start[g] ..
+ * group_start[g + 1] of survivors [N, ndim] (unit-cube rows) are the members of group g, whose lower-triangular factor is
+ * factors[g] ([G, ndim, ndim] row-major); walker k went from starts[k] to ends[k] ([K, ndim]) in group walker_group[k].
+ * Out: pair_out[g], the mean over the unordered pairs of group g of dist_g (NaN below two members), and move_out[k] =
+ * dist_g(starts[k], ends[k]) — with dist_g the length of the solution of L_g z = delta by forward substitution, delta the
+ * row difference (minimum image on wrapped dimensions), every operation IEEE-rounded on its own.  move_out and every pair
+ * distance are the definition's bits; a group's pair sum has a fixed order of its own (pair_out does not depend on the other
+ * groups of the call).  RVLL_E_INVALID: group_start not rising from 0 to N, walker_group out of range, a required pointer
+ * NULL; RVLL_E_UNSUPPORTED: ndim above 64.  Needs no priors.                                                            */
+int rvll_walk_distances_runs(rvll_handle* h, const double* survivors /*[N, ndim]*/, const int64_t* group_start /*[G + 1]*/,
+                             int32_t G, const double* factors /*[G, ndim, ndim]*/, const int32_t* wrapped /*[ndim] or NULL*/,
+                             const double* starts /*[K, ndim]*/, const double* ends /*[K, ndim]*/,
+                             const int32_t* walker_group /*[K]*/, int64_t K, double* pair_out /*[G]*/, double* move_out /*[K]*/);
 /* MLFriends clustering of R independent row sets in one call (definition: DESIGN §4e).  Rows run_start[r] .. run_start[r+1]
  * of cube belong to run r; scale [R, ndim] is each run's metric (1 / per-dimension spread); wrapped [ndim] may be NULL;
  * 0 <= nboot <= 32; seeds [R].  Out: labels [run_start[R]] (cluster of each row inside its run, 0-based, by smallest row),
@@ -276,6 +301,17 @@ int rvll_slice_walk_runs(rvll_handle* h, double* cube, double* theta, double* lo
  * (evidence_amd/clustering.py).  An empty run gets nclusters 0 and radius2 0.  RVLL_E_INVALID: nboot outside [0, 32],
  * run_start not rising from 0, a scale that is not finite and positive, a required pointer NULL; RVLL_E_UNSUPPORTED: ndim
  * above 64.  Needs no priors.                                                                                               */
+/* The resident ensemble's step with one step count per listed run (rvll_live_runs_step, or with clustered != 0
+ * rvll_live_runs_step_clustered with nboot / boot_seeds / nclusters, otherwise the same arguments): run a walks nsteps[a] moves.
+ * move / pair [A kdead] (either may be NULL) receive, per walker in the order of ranks, the step-count adaptation's distances
+ * (DESIGN §4h): move = dist_g(start, end) and pair = pair_g of the walker's group g (the run, or the run's cluster its start row
+ * is in), computed on the device from the live rows after the walk, with no host synchronisation of their own.  A uniform
+ * table with move and pair NULL is rvll_live_runs_step / _clustered bit for bit.  nclusters is only written when clustered. */
+int rvll_live_runs_step_steps(rvll_handle* h, const int32_t* runs /*[A]*/, int32_t A, int64_t kdead, const int32_t* ranks /*[A kdead]*/,
+                              const double* lstar /*[A]*/, const int32_t* wrapped, const int32_t* nsteps /*[A]*/, int32_t max_rounds,
+                              const uint64_t* seeds /*[A]*/, int32_t clustered, int32_t nboot, const uint64_t* boot_seeds /*[A] or NULL*/,
+                              int64_t* ncalls /*[A]*/, double* logl_new /*[A kdead]*/, int32_t* nclusters /*[A] or NULL*/,
+                              double* move /*[A kdead] or NULL*/, double* pair /*[A kdead] or NULL*/);
 int rvll_cluster_runs(rvll_handle* h, const double* cube /*[N, ndim]*/, const int64_t* run_start /*[R + 1]*/, int64_t R,
                       const double* scale, const int32_t* wrapped, int nboot, const uint64_t* seeds,
                       int32_t* labels, int32_t* nclusters, double* radius2);
