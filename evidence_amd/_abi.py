@@ -160,6 +160,7 @@ PROTOTYPES = {
     "rvll_set_kernel_form": (C.c_int, [Handle, C.c_int32]),
     "rvll_set_slim_table_range": (C.c_int, [Handle, C.c_double]),
     "rvll_set_walk_speculation": (C.c_int, [Handle, C.c_int32]),
+    "rvll_set_walk_proposal": (C.c_int, [Handle, C.c_int32, C.c_double]),
     "rvll_slice_walk_evaluated": (C.c_int, [Handle, C.POINTER(C.c_int64)]),
     "rvll_slice_walk_phases": (C.c_int, [Handle, C.POINTER(C.c_uint64)]),
     "rvll_slice_walk_rounds": (C.c_int, [Handle, C.POINTER(C.c_int32)]),

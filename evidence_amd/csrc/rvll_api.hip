@@ -529,6 +529,7 @@ int rvll_destroy(rvll_handle* h)
     if (h->pin_defer) (void)hipHostFree(h->pin_defer);
     stream_free(h);
     dev_free(h->d_walk_steps); dev_free(h->d_walk_wid); dev_free(h->d_walk_start); dev_free(h->d_walk_cost); dev_free(h->d_walk_order); dev_free(h->d_walk_wflag);
+    dev_free(h->d_walk_basis);
     dev_free(h->d_rounds); dev_free(h->d_walk_dirs);
     dev_free(h->d_walk_run); dev_free(h->d_run_lstar); dev_free(h->d_run_seed); dev_free(h->d_run_chol); dev_free(h->d_run_nsteps);
     if (h->pin_rounds) (void)hipHostFree(h->pin_rounds);

@@ -152,6 +152,10 @@ struct rvll_handle {
     int32_t* d_run_nsteps = nullptr;            // [runs_cap] per-run step counts (rvll_slice_walk_runs_steps)
     int wander_exact = 1;                       // wandering solves are redone with correctly rounded sin / cos (rvll_set_wander_exact; RVLL_WANDER_EXACT)
     int walk_spec = 4;                          // candidates a walker may evaluate ahead per iteration (rvll_set_walk_speculation)
+    int walk_prop = 0;                          // the walk's proposal (rvll_set_walk_proposal): RVLL_PROPOSAL_CHORD / _STEPOUT ...
+    double walk_width = 1.;                     // ... and the stepout bracket's width
+    double* d_walk_basis = nullptr;             // stepout: [slots, ndim, ndim] the basis of every walker slot (walk_core)
+    size_t walk_basis_cap = 0;                  // ... in doubles
     // the walk as rounds of launches (rvll_rounds.hip; walk_rounds in rvll_walk_host.hip): one arena with every group's walker
     // state, candidate slots and counters; a progress word per group in mapped pinned memory
     int walk_spec_rounds = 8;                   // ... and per round of the rounds form, while a round is below the latency floor

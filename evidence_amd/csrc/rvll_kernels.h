@@ -122,15 +122,33 @@ struct WalkArgs {
     const int32_t* run_nsteps;           // [R] or null (run mode): row g makes min(nsteps, run_nsteps[run[g]]) moves
                                          // (rvll_slice_walk_runs_steps: nsteps is then the largest of them, or a first part's)
 };
+// PROPOSAL (rvll_set_walk_proposal): kPropChord, the hit-and-run chord walk of WalkArgs, or kPropStepout,
+// PolyChord-style stepping out along a cycled random orthonormal basis (launch_slice_walk only), with the arguments below.
+// The stepout kernels take them in a kernel-argument struct of their own, so the chord kernels' arguments stay as they were.
+constexpr int kPropChord = 0, kPropStepout = 1;   // = RVLL_PROPOSAL_CHORD / _STEPOUT
+struct StepoutArgs {
+    double step_width;                   // the bracket's width w, in whitened units
+    double* basis;                       // [basis_slots, D, D] per walker SLOT: the basis its walker moves along
+    long long basis_slots;               // slots it has room for (>= the launch's workgroups * a.PB)
+};
+struct WalkArgsStepout : WalkArgs { StepoutArgs so; };
+constexpr int kStepoutMaxD = 64;   // a basis of D normals takes 2 D^2 counters of the 8192 below a move's shrink draws
 constexpr int kWalkCholLds = 48;   // the walk stages a whitening factor of up to 48 x 48 (18 KB) in LDS
-size_t walk_lds_bytes(const LoglikeArgs& a);
+size_t walk_lds_bytes(const LoglikeArgs& a, int proposal = kPropChord);
 // a: fused (cube -> theta -> log-L) arguments whose cube / theta_out / logL / flags rows [0, K) are scratch
 // fat = false: slim prior stage (4 waves per SIMD; deferring walkers report steps_done < nsteps);
 // fat = true : full solvers inline (every walker finishes)
 // max_cus > 0: launch at most as many workgroups as max_cus compute units hold at once (the rest of the rows are drawn
 // from w.queue by slots whose walker has finished); 0: one workgroup per PB rows
-hipError_t launch_slice_walk(const LoglikeArgs& a, const WalkArgs& w, bool fat, int max_cus, hipStream_t stream);
+// so != null: the stepout proposal
+hipError_t launch_slice_walk(const LoglikeArgs& a, const WalkArgs& w, bool fat, int max_cus, hipStream_t stream,
+                             const StepoutArgs* so = nullptr);
 long long slice_walk_resident_blocks(const LoglikeArgs& a, bool fat, int cus);
+// the workgroups launch_slice_walk starts for a stepout walk of K rows (-1: the occupancy query failed); each has a.PB slots
+long long slice_walk_stepout_blocks(const LoglikeArgs& a, long long K, bool fat, bool runs, int max_cus);
+// (launch_slice_walk with a StepoutArgs: the arguments checked, lds = walk_lds_bytes(a, kPropStepout); rvll_walk_stepout.hip)
+hipError_t launch_slice_walk_stepout(const LoglikeArgs& a, const WalkArgs& w, const StepoutArgs& so, bool fat, bool runs, int max_cus,
+                                     size_t lds, hipStream_t stream);
 // The same walk with the rows dealt to the workgroups in advance (rvll_walk.hip, slice_walk_rows_kernel): nblocks
 // workgroups own w.rows_per_wg rows each (position k of w.order — the host sorts by expected cost — goes to workgroup
 // k mod nblocks, every other tier reversed), park them in LDS and interleave them over their a.PB walker slots at move

@@ -10,6 +10,9 @@ using namespace rvll::host;
 
 namespace {
 
+// the bound of the stepout walk's basis scratch (walk_core), in doubles: 512 MiB
+constexpr size_t kStepoutBasisMax = (size_t)1 << 26;
+
 // device buffers of the walk for K rows (grown on demand)
 int walk_reserve(rvll_handle* h, int64_t K)
 {
@@ -531,6 +534,14 @@ int walk_core(rvll_handle* h, int64_t K, double lstar, int32_t nsteps, int32_t m
     const size_t D = (size_t)h->L.ndim;
     hipStream_t st = h->compute;
     int rc;
+    // the stepout proposal (rvll_set_walk_proposal) runs in the single-kernel forms only: not in the rounds form
+    // (its direction table holds one unit direction per move), not in the rows form
+    const bool so = h->walk_prop == RVLL_PROPOSAL_STEPOUT;
+    if (so) {
+        const char* e = getenv("RVLL_WALK_ROWS");
+        if (e && atoi(e) >= 1) return report_error(RVLL_E_UNSUPPORTED, "the rows form (RVLL_WALK_ROWS) has no stepout proposal");
+        if (D > (size_t)rvll::kStepoutMaxD) return report_error(RVLL_E_UNSUPPORTED, "stepout walks take at most %d parameters", rvll::kStepoutMaxD);
+    }
     if (rw) {
         const char* e = getenv("RVLL_WALK_ROWS");
         if (e && atoi(e) >= 1) return report_error(RVLL_E_UNSUPPORTED, "rvll_slice_walk_runs: the rows form (RVLL_WALK_ROWS) has no run mode");
@@ -562,14 +573,14 @@ int walk_core(rvll_handle* h, int64_t K, double lstar, int32_t nsteps, int32_t m
         if (h->pb_override <= 0 && n >= 4096) {
             a->PB = std::min(10, rvll::kMaxPointsPerBlock);
             a->CH = window(a->PB);
-            while (a->PB > 1 && 4 * rvll::walk_lds_bytes(*a) > rvll::kCuLdsBudget) { a->PB -= 1; a->CH = window(a->PB); }
+            while (a->PB > 1 && 4 * rvll::walk_lds_bytes(*a, h->walk_prop) > rvll::kCuLdsBudget) { a->PB -= 1; a->CH = window(a->PB); }
         }
         a->CH = window(a->PB);
-        while (a->PB > 1 && (rvll::walk_lds_bytes(*a) > 60 * 1024 || (long long)a->PB * a->D > 4 * rvll::kThreads)) {
+        while (a->PB > 1 && (rvll::walk_lds_bytes(*a, h->walk_prop) > 60 * 1024 || (long long)a->PB * a->D > 4 * rvll::kThreads)) {
             a->PB -= 1;
             a->CH = window(a->PB);
         }
-        if (rvll::walk_lds_bytes(*a) > 64 * 1024 || (long long)a->PB * a->D > 4 * rvll::kThreads)
+        if (rvll::walk_lds_bytes(*a, h->walk_prop) > 64 * 1024 || (long long)a->PB * a->D > 4 * rvll::kThreads)
             return report_error(RVLL_E_UNSUPPORTED, "%d parameters exceed the walk kernel's LDS budget", a->D);
         return RVLL_OK;
     };
@@ -585,7 +596,7 @@ int walk_core(rvll_handle* h, int64_t K, double lstar, int32_t nsteps, int32_t m
     long long rounds_calls = 0, rounds_slots = 0;
     bool by_rounds = false;
     h->walk_rounds_used = 0;
-    if (slim && rounds_wanted(K) && !(rw && rw->nsteps)) {
+    if (slim && !so && rounds_wanted(K) && !(rw && rw->nsteps)) {
         rc = walk_rounds(h, K, lstar, nsteps, max_rounds, seed, walker_base, &rounds_calls, &rounds_slots, rw);
         if (rc == RVLL_OK) by_rounds = true;
         else if (rc != RVLL_E_UNSUPPORTED) return rc;
@@ -603,11 +614,33 @@ int walk_core(rvll_handle* h, int64_t K, double lstar, int32_t nsteps, int32_t m
         w.cost = h->d_walk_cost;                       // every launch counts every row's calls
         if (rw->nsteps) w.run_nsteps = h->d_run_nsteps;
     }
+    rvll::StepoutArgs so_args{h->walk_width, nullptr, 0};
+    rvll::StepoutArgs* sop = so ? &so_args : nullptr;   // (null: the chord walk)
     // no more workgroups than the chip holds at once; freed walker slots draw the remaining rows from a queue
     // (RVLL_WALK_QUEUE, a measurement / test switch: 0 = one workgroup per PB rows, as many residency rounds as that
     // takes; n > 0 = as many workgroups as n compute units hold, so that a small walk goes through the queue too)
     const char* qenv = getenv("RVLL_WALK_QUEUE");
     const int max_cus = qenv ? std::max(0, std::min(atoi(qenv), h->n_cu)) : h->n_cu;
+    // stepout: scratch for the basis of every walker slot of a launch of n rows — grid x PB x D^2 doubles, not K x D^2; grown on
+    // demand, bounded (a walk that would need more is refused before anything is launched)
+    auto basis_for = [&](const rvll::LoglikeArgs& aa, long long n, bool fat) -> int {
+        if (!so) return RVLL_OK;
+        const long long nb = rvll::slice_walk_stepout_blocks(aa, n, fat, rw != nullptr, max_cus);
+        if (nb < 1) return report_error(RVLL_E_HIP, "stepout walk: the occupancy query failed");
+        const size_t need = (size_t)nb * (size_t)aa.PB * D * D;
+        if (need > kStepoutBasisMax)
+            return report_error(RVLL_E_UNSUPPORTED, "stepout walk: %lld walker slots x %zu^2 exceed the basis scratch's bound", nb * aa.PB, D);
+        if (need > h->walk_basis_cap) {
+            HIP_TRY(hipStreamSynchronize(st));
+            dev_free(h->d_walk_basis);
+            h->walk_basis_cap = 0;
+            HIP_TRY(hipMalloc(&h->d_walk_basis, sizeof(double) * need));
+            h->walk_basis_cap = need;
+        }
+        so_args.basis = h->d_walk_basis;
+        so_args.basis_slots = (long long)(h->walk_basis_cap / (D * D));
+        return RVLL_OK;
+    };
     // With more rows than walker slots a row handed out late still takes a whole walk — nsteps sequential moves — and the
     // kernel ends in a drain (phase clock: mean workgroup life 7.2 ms of a 9.5 ms kernel at 16384 rows).  What a row costs
     // per move is a property of where it walks, so the walk is launched in two parts: the first moves of every row through
@@ -632,7 +665,11 @@ int walk_core(rvll_handle* h, int64_t K, double lstar, int32_t nsteps, int32_t m
         if (const char* e = getenv("RVLL_WALK_FIRST")) w.nsteps = std::max(1, std::min(nsteps - 1, atoi(e)));   // measurement switch
         w.cost = h->d_walk_cost;
     }
-    if (!by_rounds) HIP_TRY(rvll::launch_slice_walk(a, w, !slim, max_cus, st));
+    if (!by_rounds) {
+        rc = basis_for(a, w.K, !slim);
+        if (rc) return rc;
+        HIP_TRY(rvll::launch_slice_walk(a, w, !slim, max_cus, st, sop));
+    }
     if (two_parts && !by_rounds) {
         const int first = w.nsteps;
         std::vector<int32_t> cost((size_t)K), done((size_t)K), order((size_t)K);
@@ -726,7 +763,9 @@ int walk_core(rvll_handle* h, int64_t K, double lstar, int32_t nsteps, int32_t m
             HIP_TRY(hipMemsetAsync(h->d_walk_ncalls + kWalkWords - 1, 0, sizeof(unsigned long long), st));   // the queue; the counts go on
             w.K = K2;
             w.order = h->d_walk_order;
-            HIP_TRY(rvll::launch_slice_walk(a, w, !slim, max_cus, st));
+            rc = basis_for(a, w.K, !slim);
+            if (rc) return rc;
+            HIP_TRY(rvll::launch_slice_walk(a, w, !slim, max_cus, st, sop));
             HIP_TRY(hipStreamSynchronize(st)); // `order` goes out of scope
         }
         w.K = K;
@@ -796,7 +835,9 @@ int walk_core(rvll_handle* h, int64_t K, double lstar, int32_t nsteps, int32_t m
             w2.walker_id = h->d_walk_wid;
             w2.step_start = h->d_walk_start;
             if (rw) w2.cost = h->d_walk_cost;
-            HIP_TRY(rvll::launch_slice_walk(a2, w2, true, max_cus, st));
+            rc = basis_for(a2, w2.K, true);
+            if (rc) return rc;
+            HIP_TRY(rvll::launch_slice_walk(a2, w2, true, max_cus, st, sop));
             HIP_TRY(hipMemcpyAsync(su.data(), h->d_walk_u, sizeof(double) * D * M, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipMemcpyAsync(sth.data(), h->d_walk_theta, sizeof(double) * D * M, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipMemcpyAsync(sl.data(), h->d_walk_logl, sizeof(double) * M, hipMemcpyDeviceToHost, st));
@@ -845,7 +886,7 @@ int walk_core(rvll_handle* h, int64_t K, double lstar, int32_t nsteps, int32_t m
     return RVLL_OK;
 }
 
-int walk_check_args(rvll_handle* h, int64_t K, int32_t nsteps, int32_t max_rounds, int64_t walker_base)
+int walk_check_args(rvll_handle* h, int64_t K, int32_t nsteps, int32_t max_rounds, int64_t walker_base, const int32_t* wrapped)
 {
     if (!h->have_priors) return report_error(RVLL_E_NOPRIORS, "rvll_set_priors has not been called");
     if (K < 0 || nsteps < 0) return report_error(RVLL_E_INVALID, "negative size");
@@ -853,6 +894,11 @@ int walk_check_args(rvll_handle* h, int64_t K, int32_t nsteps, int32_t max_round
         walker_base + K >= (1LL << 32))
         return report_error(RVLL_E_INVALID, "nsteps / max_rounds / K / walker_base out of range");
     if (h->L.ndim < 1) return report_error(RVLL_E_INVALID, "no free parameter to walk in");
+    if (h->walk_prop == RVLL_PROPOSAL_STEPOUT) {       // nothing would bound the bracket's stepping out
+        bool all = wrapped != nullptr;
+        for (int k = 0; all && k < h->L.ndim; ++k) all = wrapped[k] != 0;
+        if (all) return report_error(RVLL_E_INVALID, "a stepout walk needs at least one parameter that is not wrapped");
+    }
     return RVLL_OK;
 }
 
@@ -917,7 +963,7 @@ int rvll_slice_walk(rvll_handle* h, double* cube, double* theta, double* logl, i
     int rc = use_device(h);
     if (rc) return rc;
     if (ncalls) *ncalls = 0;
-    rc = walk_check_args(h, K, nsteps, max_rounds, walker_base);
+    rc = walk_check_args(h, K, nsteps, max_rounds, walker_base, wrapped);
     if (rc) return rc;
     if (K == 0 || nsteps == 0) return RVLL_OK;
     if (!cube || !theta || !logl || !chol) return report_error(RVLL_E_INVALID, "null buffer");
@@ -957,7 +1003,7 @@ int slice_walk_runs_impl(rvll_handle* h, double* cube, double* theta, double* lo
     for (int32_t r = 0; r < R; ++r)
         if (run_start[r + 1] < run_start[r]) return report_error(RVLL_E_INVALID, "rvll_slice_walk_runs: run_start decreases at run %d", (int)r);
     const int64_t K = R > 0 ? run_start[R] : 0;
-    rc = walk_check_args(h, K, nsteps, max_rounds, 0);
+    rc = walk_check_args(h, K, nsteps, max_rounds, 0, wrapped);
     if (rc) return rc;
     if (K == 0 || nsteps == 0) return RVLL_OK;
     if (!cube || !theta || !logl || !lstar || !chol || !seed) return report_error(RVLL_E_INVALID, "null buffer");
@@ -1055,7 +1101,7 @@ int rvll_live_step(rvll_handle* h, const int32_t* order, int64_t kdead, const in
     const int64_t N = h->live_n;
     if (N < 1) return report_error(RVLL_E_INVALID, "rvll_live_init has not been called");
     if (!start || !logl_new || kdead < 1 || kdead >= N) return report_error(RVLL_E_INVALID, "rvll_live_step: bad arguments");
-    rc = walk_check_args(h, kdead, nsteps, max_rounds, walker_base);
+    rc = walk_check_args(h, kdead, nsteps, max_rounds, walker_base, wrapped);
     if (rc) return rc;
     const bool dev_order = order == nullptr;             // the order rvll_live_sort left on the device; start[] are ranks among the survivors
     if (dev_order) {
@@ -1324,7 +1370,7 @@ static int live_runs_step_impl(rvll_handle* h, const int32_t* runs, int32_t A, i
     if (!ranks || !lstar || !seeds || !logl_new) return report_error(RVLL_E_INVALID, "rvll_live_runs_step: bad arguments");
     const long long n = h->runs_n, R = h->runs_R;
     const int64_t K = (int64_t)A * kdead;
-    rc = walk_check_args(h, K, nsteps, max_rounds, 0);
+    rc = walk_check_args(h, K, nsteps, max_rounds, 0, wrapped);
     if (rc) return rc;
     if (h->runs_sorted_kdead != kdead || h->runs_sorted.size() != (size_t)A || !std::equal(runs, runs + A, h->runs_sorted.begin()))
         return report_error(RVLL_E_INVALID, "rvll_live_runs_step: no rvll_live_runs_sort of these runs with kdead = %lld precedes", (long long)kdead);
@@ -1460,7 +1506,7 @@ static int live_runs_step_clustered_impl(rvll_handle* h, const int32_t* runs, in
         return report_error(RVLL_E_UNSUPPORTED, "%s: %d parameters (the clustering takes 1 .. %d)", who, Di, rvll::kClusterMaxDims);
     const long long n = h->runs_n, R = h->runs_R, m = n - kdead;
     const int64_t K = (int64_t)A * kdead, M = (int64_t)A * m;
-    rc = walk_check_args(h, K, nsteps, max_rounds, 0);
+    rc = walk_check_args(h, K, nsteps, max_rounds, 0, wrapped);
     if (rc) return rc;
     if (h->runs_sorted_kdead != kdead || h->runs_sorted.size() != (size_t)A || !std::equal(runs, runs + A, h->runs_sorted.begin()))
         return report_error(RVLL_E_INVALID, "%s: no rvll_live_runs_sort of these runs with kdead = %lld precedes", who, (long long)kdead);
@@ -1877,6 +1923,16 @@ int rvll_live_runs_births(rvll_handle* h, int32_t run, int64_t* n_dead, double* 
         HIP_TRY(hipMemcpyAsync(dead_birth + lo, h->d_walk_logl, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
     }
+    return RVLL_OK;
+}
+
+int rvll_set_walk_proposal(rvll_handle* h, int32_t kind, double width)
+{
+    if (!h) return report_error(RVLL_E_INVALID, "null handle");
+    if (kind != RVLL_PROPOSAL_CHORD && kind != RVLL_PROPOSAL_STEPOUT) return report_error(RVLL_E_INVALID, "unknown proposal %d", kind);
+    if (!(width > 0.) || !std::isfinite(width)) return report_error(RVLL_E_INVALID, "the step width must be positive and finite");
+    h->walk_prop = kind;
+    h->walk_width = width;
     return RVLL_OK;
 }
 

@@ -9,6 +9,7 @@ plus the batched forms the GPU exists for.  Every evaluation goes through the C-
 import ctypes as C
 import threading
 import weakref
+from contextlib import contextmanager
 from typing import Dict, Optional, Sequence
 
 import numpy as np
@@ -17,6 +18,7 @@ from . import _abi
 from .data import EpochTable
 from .layout import compile_layout
 from .priors import PriorSpec
+from .stepout import PROPOSALS, check_proposal
 
 
 # ---- large result arrays ---------------------------------------------------------------------------------
@@ -296,7 +298,7 @@ class GpuRVModel:
         _abi.check(self._lib.rvll_dev_loglike(self._h, int(n)))
 
     def slice_walk(self, cube, theta, logl, lstar, chol, wrapped=None, nsteps=10, max_rounds=200, seed=0,
-                   walker_base=0):
+                   walker_base=0, proposal=None, step_width=None):
         """nsteps slice-sampling moves of every walker inside logL > lstar, entirely on the GPU
         (rvll_slice_walk).  cube/theta/logl are the walkers' start points; returns (cube, theta, logl, ncalls)
         of the end points.  chol: lower-triangular factor of the live points' covariance in the unit cube.
@@ -313,13 +315,15 @@ class GpuRVModel:
             raise ValueError("chol must be [ndim, ndim]")
         wr = None if wrapped is None else np.ascontiguousarray(np.asarray(wrapped, dtype=bool).astype(np.int32))
         ncalls = C.c_int64(0)
-        _abi.check(self._lib.rvll_slice_walk(
-            self._h, _abi.as_dp(cube), _abi.as_dp(theta), _abi.as_dp(logl), k, float(lstar), _abi.as_dp(chol),
-            _abi.as_ip(wr) if wr is not None else None, int(nsteps), int(max_rounds), int(seed) & (2 ** 64 - 1),
-            int(walker_base), C.byref(ncalls)))
+        with self._proposal_for(proposal, step_width):
+            _abi.check(self._lib.rvll_slice_walk(
+                self._h, _abi.as_dp(cube), _abi.as_dp(theta), _abi.as_dp(logl), k, float(lstar), _abi.as_dp(chol),
+                _abi.as_ip(wr) if wr is not None else None, int(nsteps), int(max_rounds), int(seed) & (2 ** 64 - 1),
+                int(walker_base), C.byref(ncalls)))
         return cube, theta, logl, int(ncalls.value)
 
-    def slice_walk_runs(self, cube, theta, logl, run_start, lstar, chol, wrapped=None, nsteps=10, max_rounds=200, seeds=()):
+    def slice_walk_runs(self, cube, theta, logl, run_start, lstar, chol, wrapped=None, nsteps=10, max_rounds=200, seeds=(),
+                        proposal=None, step_width=None):
         """The walks of R independent runs in ONE device walk (rvll_slice_walk_runs).  Rows run_start[r] .. run_start[r + 1]
         of cube / theta / logl are the walkers of run r, which walks inside logL > lstar[r] with the whitening factor
         chol[r] ([R, ndim, ndim]) and seed seeds[r].  Returns (cube, theta, logl, ncalls[R]); run r's rows and ncalls[r] are
@@ -348,17 +352,19 @@ class GpuRVModel:
             steps = np.ascontiguousarray(nsteps, dtype=np.int32).reshape(-1)
             if steps.shape[0] != nrun:
                 raise ValueError("nsteps needs one entry per run (or one int for all)")
-            _abi.check(self._lib.rvll_slice_walk_runs_steps(
+            with self._proposal_for(proposal, step_width):
+                _abi.check(self._lib.rvll_slice_walk_runs_steps(
+                    self._h, _abi.as_dp(cube), _abi.as_dp(theta), _abi.as_dp(logl),
+                    run_start.ctypes.data_as(C.POINTER(C.c_int64)), nrun, _abi.as_dp(lstar), _abi.as_dp(chol),
+                    seeds.ctypes.data_as(C.POINTER(C.c_uint64)), _abi.as_ip(wr) if wr is not None else None,
+                    _abi.as_ip(steps), int(max_rounds), ncalls.ctypes.data_as(C.POINTER(C.c_int64))))
+            return cube, theta, logl, ncalls
+        with self._proposal_for(proposal, step_width):
+            _abi.check(self._lib.rvll_slice_walk_runs(
                 self._h, _abi.as_dp(cube), _abi.as_dp(theta), _abi.as_dp(logl),
                 run_start.ctypes.data_as(C.POINTER(C.c_int64)), nrun, _abi.as_dp(lstar), _abi.as_dp(chol),
                 seeds.ctypes.data_as(C.POINTER(C.c_uint64)), _abi.as_ip(wr) if wr is not None else None,
-                _abi.as_ip(steps), int(max_rounds), ncalls.ctypes.data_as(C.POINTER(C.c_int64))))
-            return cube, theta, logl, ncalls
-        _abi.check(self._lib.rvll_slice_walk_runs(
-            self._h, _abi.as_dp(cube), _abi.as_dp(theta), _abi.as_dp(logl),
-            run_start.ctypes.data_as(C.POINTER(C.c_int64)), nrun, _abi.as_dp(lstar), _abi.as_dp(chol),
-            seeds.ctypes.data_as(C.POINTER(C.c_uint64)), _abi.as_ip(wr) if wr is not None else None,
-            int(nsteps), int(max_rounds), ncalls.ctypes.data_as(C.POINTER(C.c_int64))))
+                int(nsteps), int(max_rounds), ncalls.ctypes.data_as(C.POINTER(C.c_int64))))
         return cube, theta, logl, ncalls
 
     def walk_distances_runs(self, survivors, group_start, factors, wrapped, starts, ends, walker_group):
@@ -427,7 +433,7 @@ class GpuRVModel:
         return logl
 
     def live_step(self, order, kdead, start, lstar, wrapped=None, nsteps=10, max_rounds=200, seed=0, walker_base=0,
-                  chol=None, return_chol=False):
+                  chol=None, return_chol=False, proposal=None, step_width=None):
         """One iteration of nested sampling on the resident live set (include/rvll.h, rvll_live_step): rows order[:kdead]
         die (kept in the device's dead store), kdead walkers start from rows `start`, walk, and replace them.  chol=None:
         the whitening comes from the surviving rows' covariance, computed on the device.  Returns (logl_new[kdead], ncalls)
@@ -446,10 +452,11 @@ class GpuRVModel:
         logl_new = np.empty(kdead, dtype=np.float64)
         used = np.empty((self.ndim, self.ndim)) if return_chol else None
         ncalls = C.c_int64(0)
-        _abi.check(self._lib.rvll_live_step(
-            self._h, _abi.as_ip(order) if order is not None else None, kdead, _abi.as_ip(start), float(lstar), _abi.as_dp(ch) if ch is not None else None,
-            _abi.as_ip(wr) if wr is not None else None, int(nsteps), int(max_rounds), int(seed) & (2 ** 64 - 1),
-            int(walker_base), C.byref(ncalls), _abi.as_dp(logl_new), _abi.as_dp(used) if used is not None else None))
+        with self._proposal_for(proposal, step_width):
+            _abi.check(self._lib.rvll_live_step(
+                self._h, _abi.as_ip(order) if order is not None else None, kdead, _abi.as_ip(start), float(lstar), _abi.as_dp(ch) if ch is not None else None,
+                _abi.as_ip(wr) if wr is not None else None, int(nsteps), int(max_rounds), int(seed) & (2 ** 64 - 1),
+                int(walker_base), C.byref(ncalls), _abi.as_dp(logl_new), _abi.as_dp(used) if used is not None else None))
         return (logl_new, int(ncalls.value), used) if return_chol else (logl_new, int(ncalls.value))
 
     def live_sort(self, kdead):
@@ -539,7 +546,7 @@ class GpuRVModel:
         return dead, lstar, top
 
     def _live_runs_step_steps(self, runs, kdead, ranks, lstar, wr, nsteps, max_rounds, seeds, clustered, nboot, boot_seeds,
-                              return_distances):
+                              return_distances, proposal=None, step_width=None):
         """rvll_live_runs_step_steps (the arguments checked by the caller): (logl_new, ncalls, nclusters or None, move, pair)."""
         A = runs.size
         steps = np.ascontiguousarray(np.broadcast_to(np.asarray(nsteps, dtype=np.int32), (A,)))
@@ -548,16 +555,17 @@ class GpuRVModel:
         nclusters = np.zeros(A, dtype=np.int32) if clustered else None
         move = np.empty((A, kdead), dtype=np.float64) if return_distances else None
         pair = np.empty((A, kdead), dtype=np.float64) if return_distances else None
-        _abi.check(self._lib.rvll_live_runs_step_steps(
-            self._h, _abi.as_ip(runs), A, kdead, _abi.as_ip(ranks), _abi.as_dp(lstar), _abi.as_ip(wr) if wr is not None else None,
-            _abi.as_ip(steps), int(max_rounds), seeds.ctypes.data_as(C.POINTER(C.c_uint64)), 1 if clustered else 0, int(nboot),
-            boot_seeds.ctypes.data_as(C.POINTER(C.c_uint64)) if clustered else None, ncalls.ctypes.data_as(C.POINTER(C.c_int64)),
-            _abi.as_dp(logl_new), _abi.as_ip(nclusters) if clustered else None, _abi.as_dp(move) if return_distances else None,
-            _abi.as_dp(pair) if return_distances else None))
+        with self._proposal_for(proposal, step_width):
+            _abi.check(self._lib.rvll_live_runs_step_steps(
+                self._h, _abi.as_ip(runs), A, kdead, _abi.as_ip(ranks), _abi.as_dp(lstar), _abi.as_ip(wr) if wr is not None else None,
+                _abi.as_ip(steps), int(max_rounds), seeds.ctypes.data_as(C.POINTER(C.c_uint64)), 1 if clustered else 0, int(nboot),
+                boot_seeds.ctypes.data_as(C.POINTER(C.c_uint64)) if clustered else None, ncalls.ctypes.data_as(C.POINTER(C.c_int64)),
+                _abi.as_dp(logl_new), _abi.as_ip(nclusters) if clustered else None, _abi.as_dp(move) if return_distances else None,
+                _abi.as_dp(pair) if return_distances else None))
         return logl_new, ncalls, nclusters, move, pair
 
     def live_runs_step(self, runs, kdead, ranks, lstar, wrapped=None, nsteps=10, max_rounds=200, seeds=(), return_chol=False,
-                       return_distances=False):
+                       return_distances=False, proposal=None, step_width=None):
         """One iteration of every listed run on the resident ensemble (rvll_live_runs_step), after live_runs_sort of the same
         runs: ranks [A, kdead] among each run's survivors, lstar [A] as live_runs_sort returned them, seeds [A].  Returns
         (logl_new [A, kdead], ncalls [A]) (+ the whitening factors [A, ndim, ndim] with return_chol); run a's part is bit for
@@ -581,19 +589,20 @@ class GpuRVModel:
             if np.ndim(nsteps) != 0 and np.shape(nsteps) != (A,):
                 raise ValueError("nsteps needs one entry per run (or one int for all)")
             logl_new, ncalls, _, move, pair = self._live_runs_step_steps(runs, kdead, ranks, lstar, wr, nsteps, max_rounds, seeds,
-                                                                         False, 0, None, return_distances)
+                                                                         False, 0, None, return_distances, proposal, step_width)
             return (logl_new, ncalls, move, pair) if return_distances else (logl_new, ncalls)
         logl_new = np.empty((A, kdead), dtype=np.float64)
         ncalls = np.zeros(A, dtype=np.int64)
         used = np.empty((A, self.ndim, self.ndim)) if return_chol else None
-        _abi.check(self._lib.rvll_live_runs_step(
-            self._h, _abi.as_ip(runs), A, kdead, _abi.as_ip(ranks), _abi.as_dp(lstar), _abi.as_ip(wr) if wr is not None else None,
-            int(nsteps), int(max_rounds), seeds.ctypes.data_as(C.POINTER(C.c_uint64)), ncalls.ctypes.data_as(C.POINTER(C.c_int64)),
-            _abi.as_dp(logl_new), _abi.as_dp(used) if used is not None else None))
+        with self._proposal_for(proposal, step_width):
+            _abi.check(self._lib.rvll_live_runs_step(
+                self._h, _abi.as_ip(runs), A, kdead, _abi.as_ip(ranks), _abi.as_dp(lstar), _abi.as_ip(wr) if wr is not None else None,
+                int(nsteps), int(max_rounds), seeds.ctypes.data_as(C.POINTER(C.c_uint64)), ncalls.ctypes.data_as(C.POINTER(C.c_int64)),
+                _abi.as_dp(logl_new), _abi.as_dp(used) if used is not None else None))
         return (logl_new, ncalls, used) if return_chol else (logl_new, ncalls)
 
     def live_runs_step_clustered(self, runs, kdead, ranks, lstar, wrapped=None, nsteps=10, max_rounds=200, seeds=(), nboot=30,
-                                 boot_seeds=(), return_distances=False):
+                                 boot_seeds=(), return_distances=False, proposal=None, step_width=None):
         """live_runs_step with the survivors of every listed run clustered on the device (rvll_live_runs_step_clustered; DESIGN
         §4e): run a's walkers are grouped by the cluster of their start row and whitened by that cluster's covariance, the
         clustering bootstrapped with boot_seeds[a].  Returns (logl_new [A, kdead] in walker order, ncalls [A], nclusters [A]).
@@ -614,16 +623,18 @@ class GpuRVModel:
             if np.ndim(nsteps) != 0 and np.shape(nsteps) != (A,):
                 raise ValueError("nsteps needs one entry per run (or one int for all)")
             logl_new, ncalls, nclusters, move, pair = self._live_runs_step_steps(runs, kdead, ranks, lstar, wr, nsteps, max_rounds,
-                                                                                 seeds, True, nboot, boot_seeds, return_distances)
+                                                                                 seeds, True, nboot, boot_seeds, return_distances,
+                                                                                 proposal, step_width)
             return (logl_new, ncalls, nclusters, move, pair) if return_distances else (logl_new, ncalls, nclusters)
         logl_new = np.empty((A, kdead), dtype=np.float64)
         ncalls = np.zeros(A, dtype=np.int64)
         nclusters = np.zeros(A, dtype=np.int32)
-        _abi.check(self._lib.rvll_live_runs_step_clustered(
-            self._h, _abi.as_ip(runs), A, kdead, _abi.as_ip(ranks), _abi.as_dp(lstar), _abi.as_ip(wr) if wr is not None else None,
-            int(nsteps), int(max_rounds), seeds.ctypes.data_as(C.POINTER(C.c_uint64)), int(nboot),
-            boot_seeds.ctypes.data_as(C.POINTER(C.c_uint64)), ncalls.ctypes.data_as(C.POINTER(C.c_int64)), _abi.as_dp(logl_new),
-            _abi.as_ip(nclusters)))
+        with self._proposal_for(proposal, step_width):
+            _abi.check(self._lib.rvll_live_runs_step_clustered(
+                self._h, _abi.as_ip(runs), A, kdead, _abi.as_ip(ranks), _abi.as_dp(lstar), _abi.as_ip(wr) if wr is not None else None,
+                int(nsteps), int(max_rounds), seeds.ctypes.data_as(C.POINTER(C.c_uint64)), int(nboot),
+                boot_seeds.ctypes.data_as(C.POINTER(C.c_uint64)), ncalls.ctypes.data_as(C.POINTER(C.c_int64)), _abi.as_dp(logl_new),
+                _abi.as_ip(nclusters)))
         return logl_new, ncalls, nclusters
 
     def live_runs_clusters(self, a):
@@ -763,6 +774,30 @@ class GpuRVModel:
         """Redo wandering Kepler solves (e >= 0.97: more than eight Newton steps) with correctly rounded sin / cos (include/rvll.h,
         rvll_set_wander_exact; default on)."""
         _abi.check(self._lib.rvll_set_wander_exact(self._h, 1 if on else 0))
+
+    def set_walk_proposal(self, kind, step_width=1.0):
+        """The proposal of every walk on this model from now on (rvll_set_walk_proposal): "chord" (the default:
+        hit-and-run along random unit directions, each move shrinking the whole unit-cube chord) or "stepout" (PolyChord's
+        stepping out along a cycled random orthonormal basis, brackets step_width whitened units wide; evidence_amd/stepout.py
+        is its definition).  The walk methods' proposal= / step_width= keywords override it for one call."""
+        kind, step_width = check_proposal(kind, step_width)
+        _abi.check(self._lib.rvll_set_walk_proposal(self._h, PROPOSALS.index(kind), step_width))
+        self._proposal = (kind, step_width)
+
+    @contextmanager
+    def _proposal_for(self, proposal, step_width):
+        """A walk method's proposal= / step_width= (None: the model's own, set_walk_proposal): set on the handle for the call
+        and put back after it."""
+        if proposal is None and step_width is None:
+            yield
+            return
+        own = getattr(self, "_proposal", ("chord", 1.0))
+        kind, width = check_proposal(own[0] if proposal is None else proposal, own[1] if step_width is None else step_width)
+        _abi.check(self._lib.rvll_set_walk_proposal(self._h, PROPOSALS.index(kind), width))
+        try:
+            yield
+        finally:
+            _abi.check(self._lib.rvll_set_walk_proposal(self._h, PROPOSALS.index(own[0]), own[1]))
 
     def set_walk_speculation(self, max_ahead):
         """Candidates a walker of slice_walk may evaluate ahead per iteration in otherwise free tile slots (include/rvll.h;

@@ -17,7 +17,8 @@ import time
 
 import numpy as np
 
-from .settings import ultranest_defaults
+from .settings import polychord_defaults, ultranest_defaults
+from .stepout import check_proposal
 
 
 @dataclass
@@ -288,6 +289,54 @@ def _default_clusterer(clusterer):
     return cluster_runs
 
 
+# ---- the proposal and PolyChord's stop rule (proposal=, precision_criterion=; DESIGN §4i, stepout.py) ---------------------------
+def _stop(logz, logx, logl, dlogz, precision_criterion):
+    """The stop test of a path that holds the whole live log-L array: the dlogz test, or PolyChord's rule when given."""
+    if precision_criterion is not None:
+        return _precision_stop(logz, logx, logl, precision_criterion)
+    return bool(np.max(logl) + logx < logz + np.log(np.expm1(dlogz)))
+
+
+def _walk_kwargs(proposal, step_width):
+    """The proposal keywords a walker= / walker_runs= / live= call gets: none for the chord walk, so that walker callables
+    written before the proposal existed keep working."""
+    proposal, step_width = check_proposal(proposal, step_width)
+    return {} if proposal == "chord" else {"proposal": proposal, "step_width": step_width}
+
+
+def _check_precision(precision_criterion):
+    if precision_criterion is not None and not (np.isfinite(precision_criterion) and 0.0 < precision_criterion < 1.0):
+        raise ValueError("precision_criterion must be in (0, 1)")
+
+
+def _precision_stop(logz, logx, logl_live, precision_criterion):
+    """PolyChord's stop rule: Z_live / (Z_dead + Z_live) < precision_criterion, Z_live = X mean(L_live).  The live log-L are
+    summed in ascending order, so that every path (full live array or the resident paths' sorted multiset) gets the same bits."""
+    ll = np.sort(np.asarray(logl_live, dtype=np.float64))
+    top = ll[-1]
+    lz_live = logx + top + np.log(np.mean(np.exp(ll - top)))
+    return bool(lz_live - np.logaddexp(logz, lz_live) < np.log(precision_criterion))
+
+
+def _multiset_step(ll, kdead, new):
+    """The live log-L multiset (ascending) of a resident run after an iteration: its kdead lowest died (the values the device
+    sort handed down are exactly those), the walkers' new log-L came in."""
+    return np.sort(np.concatenate([ll[kdead:], np.asarray(new, dtype=np.float64)]))
+
+
+def polychord_kwargs(ndim: int, polysettings: Optional[dict] = None) -> dict:
+    """The driver keywords (run_nested_slice / run_nested_ensemble) of a run configured with PolyChord's settings
+    (settings.polychord_defaults, type-checked as the reference does): nlive; nsteps = num_repeats; clustering =
+    do_clustering; precision_criterion; proposal = "stepout".  A nonzero boost_posterior raises ValueError (the drivers return
+    the dead points with their weights; they make no boosted posterior).  Ignored: write_resume, read_resume (no resume
+    files), feedback (no progress output), and any other key."""
+    s = polychord_defaults(ndim, polysettings)
+    if s["boost_posterior"] != 0:
+        raise ValueError("boost_posterior is not supported: the drivers return the dead points and their weights")
+    return {"nlive": s["nlive"], "nsteps": s["num_repeats"], "clustering": s["do_clustering"],
+            "precision_criterion": s["precision_criterion"], "proposal": "stepout"}
+
+
 # ---- step-count adaptation (adaptive_nsteps="move-distance"; DESIGN §4h, adapt.py) -----------------------------------------
 def _adapt_setup(adaptive_nsteps, nsteps, min_nsteps, max_nsteps, distances):
     """(min_nsteps, max_nsteps, distances) of an adaptive run, or None when adaptation is off."""
@@ -329,7 +378,8 @@ def run_nested_slice(prior: Callable, loglike: Callable, ndim: int, nlive: Optio
                      live=None, live_chol: str = "device", clustering: bool = False, nboot: int = 30,
                      clusterer: Optional[Callable] = None, walker_runs: Optional[Callable] = None,
                      adaptive_nsteps: Optional[str] = None, min_nsteps: Optional[int] = None, max_nsteps: Optional[int] = None,
-                     distances: Optional[Callable] = None) -> NestedResult:
+                     distances: Optional[Callable] = None, proposal: str = "chord", step_width: float = 1.0,
+                     precision_criterion: Optional[float] = None) -> NestedResult:
     """Nested sampling with `kbatch` deaths per iteration and batched hit-and-run slice sampling.
 
     `prior_loglike(cubes) -> (theta, logl)`, if given, replaces the prior + loglike pair inside the loop
@@ -373,7 +423,16 @@ def run_nested_slice(prior: Callable, loglike: Callable, ndim: int, nlive: Optio
     `distances` (adapt.walk_distances_runs by default, or GpuRVModel.walk_distances_runs) gives those distances, one call per
     iteration.  With `live` the run is the one-run resident ensemble, whose step measures the walkers on the device
     (`distances` is refused).  The rule draws nothing, so every draw is that of the same run without adaptation;
-    the results gain `nsteps_trace` and `far_fraction`."""
+    the results gain `nsteps_trace` and `far_fraction`.
+
+    proposal="stepout" (stepout.py) walks with PolyChord's stepping-out slice proposal instead of the chord walk:
+    directions along a random orthonormal basis cycled every ndim moves, brackets `step_width` whitened units wide that step
+    out while their ends are inside the slice.  The host walk runs stepout.walk; walker= / walker_runs= / live= get
+    proposal= and step_width= (only when the proposal is not "chord").  precision_criterion (PolyChord's stop rule) replaces
+    the dlogz test: stop when Z_live / (Z_dead + Z_live) < precision_criterion, Z_live = X mean(L_live).
+    polychord_kwargs(ndim, polysettings) gives the keywords of a run configured with PolyChord's settings."""
+    pk = _walk_kwargs(proposal, step_width)
+    _check_precision(precision_criterion)
     if clustering and walker is not None:
         raise ValueError("walker= has one whitening factor for all walkers: with clustering=True pass walker_runs= "
                          "(GpuRVModel.slice_walk_runs)")
@@ -383,11 +442,11 @@ def run_nested_slice(prior: Callable, loglike: Callable, ndim: int, nlive: Optio
             _check_resident_clustering(live, clusterer, live_chol, nboot)
         return _ensemble_resident(live, ndim, [int(seed)], nlive, kbatch, nsteps, dlogz, max_iter, max_calls, wrapped,
                                   clustering=clustering, nboot=nboot, adaptive_nsteps=adaptive_nsteps, min_nsteps=min_nsteps,
-                                  max_nsteps=max_nsteps)[0]
+                                  max_nsteps=max_nsteps, pk=pk, precision_criterion=precision_criterion)[0]
     if clustering and live is not None:
         _check_resident_clustering(live, clusterer, live_chol, nboot)
         return _ensemble_resident(live, ndim, [int(seed)], nlive, kbatch, nsteps, dlogz, max_iter, max_calls, wrapped,
-                                  clustering=True, nboot=nboot)[0]
+                                  clustering=True, nboot=nboot, pk=pk, precision_criterion=precision_criterion)[0]
     if walker is not None and walker_runs is not None:
         raise ValueError("pass walker= or walker_runs=, not both")
     if clustering:
@@ -423,6 +482,8 @@ def run_nested_slice(prior: Callable, loglike: Callable, ndim: int, nlive: Optio
     # at all — per iteration the log-L of the dying points comes down (the evidence sums need them), ranks go up
     device_order = live is not None and u is None and hasattr(live, "live_sort")
     top = float(np.max(logl)) if device_order else None
+    # precision_criterion on the device-ordered path: the live log-L multiset, from the values that come down anyway
+    live_ll = np.sort(logl) if device_order and precision_criterion is not None else None
     timing = {"order_s": 0.0, "step_wait_s": 0.0, "turns": 0}
     while it < max_iter and ncall < max_calls:
         timing["turns"] += 1
@@ -432,7 +493,7 @@ def run_nested_slice(prior: Callable, loglike: Callable, ndim: int, nlive: Optio
             timing["order_s"] += time.perf_counter() - t_turn
             ranks = rng.integers(0, nlive - kbatch, kbatch)          # (the draw the host order's alive[rng.integers(...)] makes)
             seed_it = int(rng.integers(0, 2 ** 62))
-            pending = _helper().submit(live.live_step, None, kbatch, ranks, lstar, wrapped, nsteps, 200, seed_it)
+            pending = _helper().submit(live.live_step, None, kbatch, ranks, lstar, wrapped, nsteps, 200, seed_it, **pk)
             order = dead = None
         else:
             order = _stable_argsort(logl)
@@ -451,7 +512,7 @@ def run_nested_slice(prior: Callable, loglike: Callable, ndim: int, nlive: Optio
             alive = order[kbatch:]
             start = alive[rng.integers(0, len(alive), kbatch)]
             seed_it = int(rng.integers(0, 2 ** 62))
-            pending = _helper().submit(live.live_step, order, kbatch, start, lstar, wrapped, nsteps, 200, seed_it)
+            pending = _helper().submit(live.live_step, order, kbatch, start, lstar, wrapped, nsteps, 200, seed_it, **pk)
         else:
             pending = None
         logw, logz, h, logx = _deaths(logz, h, logx, dl, nlive, kbatch)
@@ -466,10 +527,15 @@ def run_nested_slice(prior: Callable, loglike: Callable, ndim: int, nlive: Optio
             ncall += int(used)
             if device_order:
                 top = max(top, float(np.max(wl)))                     # the survivors' highest and the newcomers'
+                if live_ll is not None:
+                    live_ll = _multiset_step(live_ll, kbatch, wl)
             else:
                 logl[dead] = wl
                 top = np.max(logl)
-            if top + logx < logz + np.log(np.expm1(dlogz)):
+            if precision_criterion is not None:
+                if _precision_stop(logz, logx, live_ll if device_order else logl, precision_criterion):
+                    break
+            elif top + logx < logz + np.log(np.expm1(dlogz)):
                 break
             continue
         alive = order[kbatch:]
@@ -479,11 +545,12 @@ def run_nested_slice(prior: Callable, loglike: Callable, ndim: int, nlive: Optio
         start = alive[pick]
         if live is not None:
             # live_chol="host": order and start rows up, the new log-L of the replaced rows down, and the mirror of the rows
-            wl, used = live.live_step(order, kbatch, start, lstar, wrapped, nsteps, 200, int(rng.integers(0, 2 ** 62)), chol=chol)
+            wl, used = live.live_step(order, kbatch, start, lstar, wrapped, nsteps, 200, int(rng.integers(0, 2 ** 62)), chol=chol,
+                                      **pk)
             ncall += int(used)
             logl[dead] = wl
             u = live.live_get()[0]
-            if np.max(logl) + logx < logz + np.log(np.expm1(dlogz)):
+            if _stop(logz, logx, logl, dlogz, precision_criterion):
                 break
             continue
         wu, wt, wl = u[start], theta[start], logl[start]
@@ -499,18 +566,26 @@ def run_nested_slice(prior: Callable, loglike: Callable, ndim: int, nlive: Optio
             factors = _cluster_factors(ua, labels, int(ncl[0]), chol)
             cw = np.asarray(labels, dtype=np.intp)[pick]
         if walker is not None:
-            wu, wt, wl, used = walker(wu, wt, wl, lstar, chol, wrapped, nsteps, 200, int(rng.integers(0, 2 ** 62)))
+            wu, wt, wl, used = walker(wu, wt, wl, lstar, chol, wrapped, nsteps, 200, int(rng.integers(0, 2 ** 62)), **pk)
             ncall += int(used)
         elif walker_runs is not None:
             wo, sizes, gf, gseeds = _walk_groups(cw, factors, int(rng.integers(0, 2 ** 62)))
             gu, gt, gl, used = walker_runs(wu[wo], wt[wo], wl[wo], np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64),
-                                           np.full(len(sizes), lstar), np.stack(gf), wrapped, nsteps, 200, gseeds)
+                                           np.full(len(sizes), lstar), np.stack(gf), wrapped, nsteps, 200, gseeds, **pk)
             wu[wo], wt[wo], wl[wo] = gu, gt, gl
             ncall += int(np.sum(used))
         many = len(factors) > 1
         if many:
             wfac = np.stack(factors)[cw]                        # each walker's factor: that of its start row's cluster
-        for _ in range(0 if (walker is not None or walker_runs is not None) else nsteps):
+        if pk and walker is None and walker_runs is None:
+            def evaluate(cand):
+                if prior_loglike is not None:
+                    return prior_loglike(cand)
+                ct = np.asarray(prior(cand), dtype=np.float64)
+                return ct, np.asarray(loglike(ct), dtype=np.float64)
+            from .stepout import walk as stepout_walk
+            ncall += stepout_walk(wu, wt, wl, lstar, wfac if many else chol, wrapped, nsteps, 200, pk["step_width"], rng, evaluate)
+        for _ in range(0 if (walker is not None or walker_runs is not None or pk) else nsteps):
             z = rng.standard_normal((kbatch, ndim))
             d = np.einsum("kij,kj->ki", wfac, z) if many else z @ chol.T
             d /= np.linalg.norm(d, axis=1, keepdims=True)
@@ -546,7 +621,7 @@ def run_nested_slice(prior: Callable, loglike: Callable, ndim: int, nlive: Optio
             trace.append(nsteps)
             fars.append(float(far_fraction(f[0], c[0])))
             nsteps = next_nsteps(nsteps, int(f[0]), int(c[0]), adapting[0], adapting[1])
-        if np.max(logl) + logx < logz + np.log(np.expm1(dlogz)):
+        if _stop(logz, logx, logl, dlogz, precision_criterion):
             break
     if device_order:
         logl = live.live_get(cube=False, theta=False)[2]              # the live points' log-L: once, at the end
@@ -605,7 +680,8 @@ def run_nested_ensemble(prior: Callable, loglike: Callable, ndim: int, seeds, nl
                         walker_runs: Optional[Callable] = None, clustering: bool = False, nboot: int = 30,
                         clusterer: Optional[Callable] = None, live=None, adaptive_nsteps: Optional[str] = None,
                         min_nsteps: Optional[int] = None, max_nsteps: Optional[int] = None,
-                        distances: Optional[Callable] = None) -> list:
+                        distances: Optional[Callable] = None, proposal: str = "chord", step_width: float = 1.0,
+                        precision_criterion: Optional[float] = None) -> list:
     """len(seeds) independent runs of run_nested_slice in lockstep, their walks in ONE call per iteration.
 
     The reference's FIP workflow repeats independent runs of every model and takes the median and spread of ln Z over them
@@ -641,7 +717,12 @@ def run_nested_ensemble(prior: Callable, loglike: Callable, ndim: int, seeds, nl
     its own step count, the walk call gets them per group (an int when they are all equal), and one `distances` call per
     iteration measures the walkers of every run; result[r] is run_nested_slice(..., adaptive_nsteps=...) for seed r, bit for
     bit.  With live= the resident step takes the per-run counts and returns the distances from the device rows
-    (GpuRVModel.live_runs_step(nsteps=[...], return_distances=True)); result[r] is then the standalone resident adaptive run."""
+    (GpuRVModel.live_runs_step(nsteps=[...], return_distances=True)); result[r] is then the standalone resident adaptive run.
+
+    proposal= / step_width= / precision_criterion= as run_nested_slice takes them: result[r] is the standalone run of seed r with
+    the same keywords, bit for bit."""
+    pk = _walk_kwargs(proposal, step_width)
+    _check_precision(precision_criterion)
     seeds = [int(s) for s in seeds]
     if not seeds:
         raise ValueError("need at least one seed")
@@ -654,7 +735,7 @@ def run_nested_ensemble(prior: Callable, loglike: Callable, ndim: int, seeds, nl
             raise ValueError("pass walker_runs= or live=, not both")
         return _ensemble_resident(live, ndim, seeds, nlive, kbatch, nsteps, dlogz, max_iter, max_calls, wrapped,
                                   clustering=clustering, nboot=nboot, adaptive_nsteps=adaptive_nsteps, min_nsteps=min_nsteps,
-                                  max_nsteps=max_nsteps)
+                                  max_nsteps=max_nsteps, pk=pk, precision_criterion=precision_criterion)
     if walker_runs is None:
         raise ValueError("walker_runs is required (GpuRVModel.slice_walk_runs)")
     if clustering:
@@ -724,7 +805,7 @@ def run_nested_ensemble(prior: Callable, loglike: Callable, ndim: int, seeds, nl
                                        np.concatenate([r.logl[st[wo]] for r, _, st, _, _, _, wo, *_ in turn]),
                                        run_start, np.repeat([t[3] for t in turn], [len(t[7]) for t in turn]),
                                        np.stack([f for t in turn for f in t[8]]),
-                                       wrapped, steps, 200, [s for t in turn for s in t[9]])
+                                       wrapped, steps, 200, [s for t in turn for s in t[9]], **pk)
         t_walk = time.perf_counter() - t0
         g = 0
         for j, (r, dead, _st, _ls, _ch, _sd, wo, gsizes, *_rest) in enumerate(turn):
@@ -734,7 +815,10 @@ def run_nested_ensemble(prior: Callable, loglike: Callable, ndim: int, seeds, nl
             g += len(gsizes)
             back = dead[wo]                                  # the walkers' rows in group order
             r.u[back], r.theta[back], r.logl[back] = wu[rows], wt[rows], wl[rows]
-            if np.max(r.logl) + r.logx < r.logz + stop_gap:
+            if precision_criterion is not None:
+                if _precision_stop(r.logz, r.logx, r.logl, precision_criterion):
+                    r.done = True
+            elif np.max(r.logl) + r.logx < r.logz + stop_gap:
                 r.done = True
             r.timing["walk_s"] += t_walk
             r.timing["turns"] += 1
@@ -793,7 +877,7 @@ def _cluster_turn(turn, clusterer, wrapped, nboot, keep_groups=False):
 
 
 def _ensemble_resident(live, ndim, seeds, nlive, kbatch, nsteps, dlogz, max_iter, max_calls, wrapped, clustering=False, nboot=30,
-                       adaptive_nsteps=None, min_nsteps=None, max_nsteps=None):
+                       adaptive_nsteps=None, min_nsteps=None, max_nsteps=None, pk=None, precision_criterion=None):
     """run_nested_ensemble(live=model): the device_order branch of run_nested_slice for every seed, the runs' live sets resident
     side by side (run r = rows r nlive .. r nlive + nlive - 1 of the ensemble), their bookkeeping vectorised across runs.
     clustering: the clustered step, with run r's bootstrap seed (seeds[r] _BOOT_MUL + deaths after this iteration) mod 2^64 —
@@ -811,7 +895,11 @@ def _ensemble_resident(live, ndim, seeds, nlive, kbatch, nsteps, dlogz, max_iter
     steps = np.full(R, nsteps, dtype=np.int64)
     trace, fars = [[] for _ in range(R)], [[] for _ in range(R)]
     rngs = [np.random.default_rng(s) for s in seeds]
-    live.live_runs_init(np.concatenate([g.random((nlive, ndim)) for g in rngs]), R)
+    pk = pk or {}
+    ll0 = live.live_runs_init(np.concatenate([g.random((nlive, ndim)) for g in rngs]), R)
+    # precision_criterion: every run's live log-L multiset, kept from the values that come down anyway (init, the sort's dying
+    # values, the step's new log-L)
+    live_ll = [np.sort(ll0[r]) for r in range(R)] if precision_criterion is not None else None
     ncall = np.full(R, nlive, dtype=np.int64)
     logz, h = np.full(R, -np.inf), np.zeros(R)
     logx_run, niter = np.zeros(R), np.zeros(R, dtype=np.int64)
@@ -837,11 +925,12 @@ def _ensemble_resident(live, ndim, seeds, nlive, kbatch, nsteps, dlogz, max_iter
         dist = {"return_distances": True} if adapting else {}
         if clustering:
             boot = [(seeds[r] * _BOOT_MUL + it + kbatch) & _M64 for r in act]
-            wl, used, ncl, *md = live.live_runs_step_clustered(act, kbatch, ranks, lstar, wrapped, st, 200, walk_seeds, nboot, boot, **dist)
+            wl, used, ncl, *md = live.live_runs_step_clustered(act, kbatch, ranks, lstar, wrapped, st, 200, walk_seeds, nboot, boot,
+                                                               **dist, **pk)
             for j, r in enumerate(act):
                 ncls[r].append(int(ncl[j]))
         else:
-            wl, used, *md = live.live_runs_step(act, kbatch, ranks, lstar, wrapped, st, 200, walk_seeds, **dist)
+            wl, used, *md = live.live_runs_step(act, kbatch, ranks, lstar, wrapped, st, 200, walk_seeds, **dist, **pk)
         t2 = time.perf_counter()
         if adapting:
             from .adapt import far_fraction, next_nsteps
@@ -860,7 +949,13 @@ def _ensemble_resident(live, ndim, seeds, nlive, kbatch, nsteps, dlogz, max_iter
         ncall[act] += used
         wmax = np.max(wl, axis=1)
         top = np.where(wmax > top, wmax, top)       # max(top, max(wl)) as the standalone run takes it
-        done[act[top + logx < logz[act] + stop_gap]] = True
+        if precision_criterion is not None:
+            for j, r in enumerate(act):
+                live_ll[r] = _multiset_step(live_ll[r], kbatch, wl[j])
+                if _precision_stop(logz[r], logx, live_ll[r], precision_criterion):
+                    done[r] = True
+        else:
+            done[act[top + logx < logz[act] + stop_gap]] = True
         niter[act], logx_run[act] = it, logx
         host = (time.perf_counter() - t2 + t1 - t0) / act.size
         for r in act:

@@ -59,7 +59,8 @@ extern "C" {
                                   0.7: rvll_shrinkage_replicates
                                   0.8: rvll_live_births, rvll_live_runs_births, rvll_insertion_indexes;
                                        additions within 0.8 (new symbols only, no signature changed):
-                                       rvll_slice_walk_runs_steps, rvll_walk_distances_runs, rvll_live_runs_step_steps */
+                                       rvll_slice_walk_runs_steps, rvll_walk_distances_runs, rvll_live_runs_step_steps,
+                                       rvll_set_walk_proposal (RVLL_PROPOSAL_CHORD / _STEPOUT) */
 
 /* ---- error codes ------------------------------------------------------ */
 #define RVLL_OK             0
@@ -323,6 +324,20 @@ int rvll_cluster_runs(rvll_handle* h, const double* cube /*[N, ndim]*/, const in
  * rvll_slice_walk_evaluated: tile slots the last rvll_slice_walk evaluated (>= its ncalls: speculative candidates
  * that went unused are work done, not likelihood calls of the sampler).                                          */
 int rvll_set_walk_speculation(rvll_handle* h, int32_t max_ahead);
+/* The proposal of every walk on the handle from now on — rvll_slice_walk*, rvll_live_step, rvll_live_runs_step* with and
+ * without clustering.  RVLL_PROPOSAL_CHORD (the default): hit-and-run, each move shrinking the whole unit-cube
+ * chord along a random unit direction towards the walker.  RVLL_PROPOSAL_STEPOUT: PolyChord-style slice sampling — move m
+ * goes along L q_{m mod ndim}, q the vectors of a random orthonormal basis drawn anew every ndim moves (modified
+ * Gram-Schmidt), t in whitened units; a bracket `width` wide at a uniform offset around the walker, cut by the cube's walls
+ * (wrapped parameters set no limit), steps out by `width` at each end inside the slice (right end first), then shrinks as
+ * the chord walk does.  Expansions and shrink candidates count together against max_rounds.  Counter-based draws name the
+ * walker, so sharding (walker_base), run mode and the queue give the same bits as with the chord walk.  A stepout walk
+ * takes the single-kernel forms only (rvll_slice_walk_rounds reports 0; RVLL_WALK_ROWS -> RVLL_E_UNSUPPORTED), at most 64
+ * parameters, and per-walker-slot scratch of ndim^2 doubles.  RVLL_E_INVALID: an unknown kind, a width that is not
+ * positive and finite, or (at the walk) a stepout walk in which every parameter is wrapped.                       */
+#define RVLL_PROPOSAL_CHORD   0
+#define RVLL_PROPOSAL_STEPOUT 1
+int rvll_set_walk_proposal(rvll_handle* h, int32_t kind, double width);
 int rvll_slice_walk_evaluated(rvll_handle* h, int64_t* evaluated);
 /* Diagnostic build only (make -C evidence_amd/csrc walktrace; all zeros otherwise): where the workgroups of the last
  * rvll_slice_walk spent their time — 100 MHz ticks summed over workgroups for [0] directions + chord limits,
