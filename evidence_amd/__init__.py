@@ -15,9 +15,10 @@ from .engine import GpuRVModel
 from .nested import run_nested_ensemble
 from . import shrinkage
 from . import insertion
+from . import merge
 from .shrinkage import logz_error, replicates
 
 __all__ = ["GpuRVModel", "EpochTable", "ModelLayout", "compile_layout", "PriorSpec", "PriorError",
            "prior_constructor", "RvllError", "RvllLibraryError", "FLAG_INVALID_ORBIT", "FLAG_NONCONVERGED",
-           "FLAG_WANDERED", "run_nested_ensemble", "shrinkage", "replicates", "logz_error", "insertion"]
+           "FLAG_WANDERED", "run_nested_ensemble", "shrinkage", "replicates", "logz_error", "insertion", "merge"]
 __version__ = "0.1.0"

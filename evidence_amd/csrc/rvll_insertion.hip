@@ -30,6 +30,7 @@
 #pragma GCC visibility push(default)
 #include "rvll.h"
 #pragma GCC visibility pop
+#include "rvll_keys.h"
 
 namespace rvll {
 int report_error(int code, const char* fmt, ...);
@@ -57,13 +58,7 @@ typedef unsigned long long u64;
         }                                                                                      \
     } while (0)
 
-__host__ __device__ inline u64 key_of(double x)
-{
-    if (x == 0.0) x = 0.0;                                   // -0.0 and +0.0 compare equal: one key
-    u64 b;
-    __builtin_memcpy(&b, &x, sizeof b);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
+using rvll::key_of;                                          // -0.0 and +0.0 compare equal: one key
 
 // the two double columns, in place, as keys
 __global__ __launch_bounds__(kThreads)

@@ -39,6 +39,8 @@ class NestedResult:
                                    # lstar of the iteration that drew it (the insertion-index test reads it; insertion.py)
     nsteps_trace: np.ndarray = None  # adaptive_nsteps: the step count every iteration walked with (None when off; adapt.py)
     far_fraction: np.ndarray = None  # adaptive_nsteps: the far walkers' share of the counted ones per iteration, NaN where none counted
+    nlive_row: np.ndarray = None  # a merged run (merge.py): the live count at every death, which varies from row to row
+    run_index: np.ndarray = None  # a merged run: the input run every row comes from
 
 
 def _logaddexp_many(x):

@@ -60,7 +60,8 @@ extern "C" {
                                   0.8: rvll_live_births, rvll_live_runs_births, rvll_insertion_indexes;
                                        additions within 0.8 (new symbols only, no signature changed):
                                        rvll_slice_walk_runs_steps, rvll_walk_distances_runs, rvll_live_runs_step_steps,
-                                       rvll_set_walk_proposal (RVLL_PROPOSAL_CHORD / _STEPOUT) */
+                                       rvll_set_walk_proposal (RVLL_PROPOSAL_CHORD / _STEPOUT),
+                                       rvll_merge_runs, rvll_merge_replicates (rvll_merge_timing) */
 
 /* ---- error codes ------------------------------------------------------ */
 #define RVLL_OK             0
@@ -638,6 +639,41 @@ typedef struct rvll_insertion_timing {
 int rvll_insertion_indexes(int32_t device, const double* logl /*[n_rows]*/, const double* birth /*[n_rows]*/, int64_t n_rows,
                            const int64_t* run_start /*[n_runs + 1]*/, int32_t n_runs, int32_t* index_out /*[n_rows]*/,
                            int32_t* n_at_out /*[n_rows]*/, rvll_insertion_timing* timing);
+
+/* ---- merging finished runs by their birth contours (post-processing; independent of any model handle) ------------ */
+/* R runs become one run whose live count varies from death to death (Higson et al. 2018; dynesty's merge_runs).
+ * evidence_amd/merge.py is the definition.  Rows run_start[r] .. run_start[r+1] of logl / birth (n_rows in all,
+ * any order inside a run) are run r.  The merged order sorts every row stably by log-L, ties by run and then by position, so
+ * order_out[i] is the input row (run_start[r] + position) of merged row i.  A row with logl <= birth counts with the birth
+ * nextafter(logl, -inf) (*n_off_contour of them).  With run multiplicities w_r (1 each without the bootstrap), merged row i
+ * dies at n_i = sum_{birth_k < logl_i} w - sum_{k < i} w live points, w_{rho_i} times in a row at n_i, n_i - 1, ...; its
+ * shrinkage Delta_i sums -1 / (n_i - q) (RVLL_SHRINK_EXPECTED) or log(1 - uniform01(seed_s, c)) / (n_i - q) over q < w, c the
+ * copies that died before, seed_s = seed + s * 0xD1B54A32D192ED03.  logw_i = (logl_i + logX_{i-1}) + log(-expm1(Delta_i)),
+ * logz = logsumexp(logw), info = sum e^{logw - logz} logl - logz, logwt = logw - logz.  Bootstrap: w_r counts r among the
+ * draws floor(uniform01(seed_s ^ 0x5851F42D4C957F2D, t) * n_runs), t < n_runs.
+ * rvll_merge_runs: the merged run itself (expected shrinkage, no bootstrap): order_out, nlive_out (n_i), logz, info and
+ * logwt_out [n_rows] in merged order.  rvll_merge_replicates: logz[s], info[s] of nsamples replicates and, if logwt is not
+ * NULL, logwt[s * n_rows + i]; the weights go through a device block of at most block_bytes (0: 512 MiB), RVLL_E_NOMEM before
+ * any work when one replicate does not fit.  A replicate's results do not depend on the others of the call.
+ * RVLL_E_INVALID: n_runs < 1, n_rows outside [1, 2^30), a run_start that does not rise from 0 to n_rows, NaN births, NaN or
+ * infinite log-L, nsamples < 1, an unknown mode, bootstrap not 0 / 1, bootstrap with more than 8192 runs, negative
+ * block_bytes, null buffers.  timing may be NULL.  device < 0 uses the current device.                                     */
+typedef struct rvll_merge_timing {
+    double  kernel_ms;       /* HIP-event time of the device work (keys, two radix sorts, placement, replicate kernels)  */
+    double  total_ms;        /* the whole call: checks, allocation, uploads, kernels, downloads                          */
+    int64_t rows;            /* n_rows                                                                                    */
+    int64_t elements;        /* (row, replicate) pairs: n_rows * nsamples (n_rows for rvll_merge_runs)                    */
+    int32_t launches;        /* kernel launches issued (a rocPRIM sort counted as one)                                    */
+    int32_t threads;         /* per workgroup of the replicate kernel; one workgroup per replicate                       */
+} rvll_merge_timing;
+int rvll_merge_runs(int32_t device, const double* logl /*[n_rows]*/, const double* birth /*[n_rows]*/, int64_t n_rows,
+                    const int64_t* run_start /*[n_runs + 1]*/, int32_t n_runs, int64_t* order_out /*[n_rows]*/,
+                    int64_t* nlive_out /*[n_rows]*/, double* logz, double* info, double* logwt_out /*[n_rows]*/,
+                    int64_t* n_off_contour, rvll_merge_timing* timing);
+int rvll_merge_replicates(int32_t device, const double* logl /*[n_rows]*/, const double* birth /*[n_rows]*/, int64_t n_rows,
+                          const int64_t* run_start /*[n_runs + 1]*/, int32_t n_runs, int32_t nsamples, int32_t mode,
+                          int32_t bootstrap, uint64_t seed, double* logz /*[nsamples]*/, double* info /*[nsamples]*/,
+                          double* logwt /*NULL or [nsamples * n_rows]*/, int64_t block_bytes, rvll_merge_timing* timing);
 
 /* ---- diagnostics -------------------------------------------------------------- */
 /* Evaluate one device math routine elementwise (tests only; no reference counterpart):
