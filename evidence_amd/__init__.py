@@ -16,9 +16,10 @@ from .nested import run_nested_ensemble
 from . import shrinkage
 from . import insertion
 from . import merge
+from . import posterior
 from .shrinkage import logz_error, replicates
 
 __all__ = ["GpuRVModel", "EpochTable", "ModelLayout", "compile_layout", "PriorSpec", "PriorError",
            "prior_constructor", "RvllError", "RvllLibraryError", "FLAG_INVALID_ORBIT", "FLAG_NONCONVERGED",
-           "FLAG_WANDERED", "run_nested_ensemble", "shrinkage", "replicates", "logz_error", "insertion", "merge"]
+           "FLAG_WANDERED", "run_nested_ensemble", "shrinkage", "replicates", "logz_error", "insertion", "merge", "posterior"]
 __version__ = "0.1.0"

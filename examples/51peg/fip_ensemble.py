@@ -2,7 +2,8 @@
 """The reference's FIP workflow (evidence/fip_criterion.py) end to end on one GPU, for the 51 Peg example: for k = 0, 1, 2
 planets, R independent nested-sampling runs through nested.run_nested_ensemble (their walks in one device walk per
 iteration), then p(k | y) from the median ln Z over the runs (fip.model_probabilities) and the FIP periodogram of every run
-(fip.fip_periodogram).  Needs a GPU.
+(fip.fip_periodogram); and last the parameter table of the k = 1 model from its R runs merged by their birth contours, every entry
+with the scatter over bootstrap replicates of the runs as its error (posterior.table).  Needs a GPU.
     python3 examples/51peg/fip_ensemble.py [R]          (default 8 runs per model)"""
 import sys
 import time
@@ -11,7 +12,7 @@ from pathlib import Path
 import numpy as np
 
 sys.path.insert(0, str(Path(__file__).resolve().parents[2]))
-from evidence_amd import GpuRVModel, fip, run_nested_ensemble      # noqa: E402
+from evidence_amd import GpuRVModel, fip, posterior, run_nested_ensemble      # noqa: E402
 from evidence_amd.callbacks import make_ultranest_callbacks, wrapped_params   # noqa: E402
 from evidence_amd.config import read_config                        # noqa: E402
 
@@ -33,6 +34,8 @@ for k in range(3):
             logzs[r, k] = out.logz
             if k:
                 posteriors[r][k] = (out.samples[:, cols], np.exp(out.logwt))
+        if k == 1:
+            one_planet, one_planet_names = res, list(m.parnames)
     print(f"{rundict['target']}, {k} planet(s), {R} runs in {dt:.2f} s: ln Z median {np.median(logzs[:, k]):.3f}, "
           f"std {np.std(logzs[:, k]):.3f}")
 
@@ -45,3 +48,7 @@ s = fip.fip_summary(fapnu, nu)
 best = int(np.argmin(s["median"]))
 print(f"FIP periodogram over {R} runs, {nu.size} frequencies: lowest median log10 FIP {s['median'][best]:.2f} at "
       f"P = {s['periods'][best]:.4f} d; converged across runs: {s['converged']}")
+
+# the k = 1 model's parameters from its merged runs: point estimates, and the scatter over 1000 bootstrap replicates as errors
+print(f"\n1 planet, {R} runs merged:")
+print(posterior.format_table(posterior.table(one_planet, one_planet_names, nsamples=1000, seed=1, device=0)))

@@ -61,7 +61,8 @@ extern "C" {
                                        additions within 0.8 (new symbols only, no signature changed):
                                        rvll_slice_walk_runs_steps, rvll_walk_distances_runs, rvll_live_runs_step_steps,
                                        rvll_set_walk_proposal (RVLL_PROPOSAL_CHORD / _STEPOUT),
-                                       rvll_merge_runs, rvll_merge_replicates (rvll_merge_timing) */
+                                       rvll_merge_runs, rvll_merge_replicates (rvll_merge_timing),
+                                       rvll_posterior_replicates (rvll_posterior_timing) */
 
 /* ---- error codes ------------------------------------------------------ */
 #define RVLL_OK             0
@@ -674,6 +675,42 @@ int rvll_merge_replicates(int32_t device, const double* logl /*[n_rows]*/, const
                           const int64_t* run_start /*[n_runs + 1]*/, int32_t n_runs, int32_t nsamples, int32_t mode,
                           int32_t bootstrap, uint64_t seed, double* logz /*[nsamples]*/, double* info /*[nsamples]*/,
                           double* logwt /*NULL or [nsamples * n_rows]*/, int64_t block_bytes, rvll_merge_timing* timing);
+
+/* ---- posterior summaries of the merged run's replicates (post-processing; independent of any model handle) ------- */
+/* Per replicate s of rvll_merge_replicates (same seeds, multiplicities and merged order) and per column c of values
+ * [n_rows, n_cols] (row-major, in input row order; any parameter or derived quantity), with p_i = exp(logwt_i) (0 for a row
+ * without weight), P = sum p and x_i the column's value in merged row i (evidence_amd/posterior.py is the definition, DESIGN
+ * §4k):  mean[s * n_cols + c] = sum p x / P;  sd[s * n_cols + c] = sqrt(sum p (x - mean)^2 / P), the spread about the
+ * replicate's own mean;  quant[(s * n_q + k) * n_cols + c] = the inverted weighted CDF at quantiles[k]: x of the first row, in
+ * the order of x, whose inclusive running sum of p reaches quantiles[k] * P (numpy's quantile(x, q, weights=p,
+ * method="inverted_cdf")); and logz[s], info[s] as rvll_merge_replicates gives them.  The weights stay on the device: a block
+ * of replicates is reduced where it was written.  block_bytes bounds the per-call tables (values in merged order and one
+ * permutation a column: 12 * n_rows * n_cols bytes) plus the block of weights (8 * n_rows a replicate); 0 stands for the
+ * tables plus 8 GiB, of which only nsamples replicates are allocated.  RVLL_E_NOMEM before any work when the tables and one
+ * replicate do not fit.  A replicate's results do not depend on the others of the call or on the batching.  A replicate in
+ * which no row has weight (a bootstrap of empty runs) gives NaN.
+ * RVLL_E_INVALID: everything rvll_merge_replicates refuses; n_cols outside [1, 64], n_q outside [1, 16], a level outside the
+ * open interval (0, 1), a value that is not finite, null buffers.  timing may be NULL.  device < 0 uses the current device. */
+typedef struct rvll_posterior_timing {
+    double  kernel_ms;       /* HIP-event time of all device work: setup_ms + weights_ms + reduce_ms                       */
+    double  total_ms;        /* the whole call: checks, allocation, uploads, kernels, downloads                            */
+    double  setup_ms;        /* the merge's setup, the permutation of values and one radix sort a column                    */
+    double  weights_ms;      /* the replicate kernels (what rvll_merge_replicates spends on the same input)                 */
+    double  reduce_ms;       /* exp of the block and the (replicate, column) summary kernel                                 */
+    int64_t rows;            /* n_rows                                                                                      */
+    int64_t elements;        /* (row, replicate) pairs: n_rows * nsamples                                                   */
+    int32_t launches;        /* 5 + 2 * n_cols for the setup, then 3 a block of replicates (a rocPRIM sort counted as one)  */
+    int32_t threads;         /* per workgroup; one workgroup per replicate (weights) and per (replicate, column) (summary)  */
+    int32_t blocks;          /* blocks of replicates the call was split into                                                */
+    int32_t reserved;
+} rvll_posterior_timing;
+int rvll_posterior_replicates(int32_t device, const double* logl /*[n_rows]*/, const double* birth /*[n_rows]*/, int64_t n_rows,
+                              const int64_t* run_start /*[n_runs + 1]*/, int32_t n_runs,
+                              const double* values /*[n_rows * n_cols]*/, int32_t n_cols, const double* quantiles /*[n_q]*/,
+                              int32_t n_q, int32_t nsamples, int32_t mode, int32_t bootstrap, uint64_t seed,
+                              double* logz /*[nsamples]*/, double* info /*[nsamples]*/, double* mean /*[nsamples * n_cols]*/,
+                              double* sd /*[nsamples * n_cols]*/, double* quant /*[nsamples * n_q * n_cols]*/,
+                              int64_t block_bytes, rvll_posterior_timing* timing);
 
 /* ---- diagnostics -------------------------------------------------------------- */
 /* Evaluate one device math routine elementwise (tests only; no reference counterpart):
