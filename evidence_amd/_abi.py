@@ -106,6 +106,12 @@ class PosteriorTiming(C.Structure):
                 ("threads", C.c_int32), ("blocks", C.c_int32), ("reserved", C.c_int32)]
 
 
+class FipMergedTiming(C.Structure):
+    _fields_ = [("kernel_ms", C.c_double), ("total_ms", C.c_double), ("setup_ms", C.c_double), ("weights_ms", C.c_double),
+                ("reduce_ms", C.c_double), ("rows", C.c_int64), ("elements", C.c_int64), ("events", C.c_int64),
+                ("launches", C.c_int32), ("threads", C.c_int32), ("blocks", C.c_int32), ("key_bits", C.c_int32)]
+
+
 SHRINK_RANDOM, SHRINK_EXPECTED = 0, 1
 FIP_MAX_PLANETS = 8
 Handle = C.c_void_p
@@ -202,6 +208,9 @@ PROTOTYPES = {
     "rvll_posterior_replicates": (C.c_int, [C.c_int32, _dp, _dp, C.c_int64, C.POINTER(C.c_int64), C.c_int32, _dp, C.c_int32, _dp,
                                             C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, _dp, _dp, _dp, _dp, _dp,
                                             C.c_int64, C.POINTER(PosteriorTiming)]),
+    "rvll_fip_replicates": (C.c_int, [C.c_int32, _dp, _dp, C.c_int64, C.POINTER(C.c_int64), C.c_int32, _dp, C.c_int32, _dp, _dp,
+                                      C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, _dp, _dp, _dp, C.c_int64,
+                                      C.POINTER(FipMergedTiming)]),
     "rvll_dev_trace_loglike": (C.c_int, [Handle, C.c_int64, C.c_int32, C.POINTER(C.c_uint64), C.c_int64, _ip, _ip]),
     "rvll_debug_eval": (C.c_int, [Handle, C.c_int32, _dp, _dp, C.c_int64, _dp]),
     "rvll_last_error": (C.c_char_p, []),

@@ -26,6 +26,7 @@
 #pragma GCC visibility push(default)
 #include "rvll.h"
 #pragma GCC visibility pop
+#include "rvll_fip_search.h"
 
 namespace rvll {
 int report_error(int code, const char* fmt, ...);
@@ -50,28 +51,8 @@ constexpr int kDenseHits = 16;          // rows of a 64-row group that must touc
         }                                                                                      \
     } while (0)
 
-// number of a[i] <= v (numpy.searchsorted(a, v, 'right')); a NaN v compares false everywhere -> 0, and the
-// matching lower bound is 0 too, i.e. the same empty interval numpy's (n, n) is
-__device__ int count_le(const double* __restrict__ a, int n, double v)
-{
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (a[mid] <= v) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-// number of a[i] < v (numpy.searchsorted(a, v, 'left'))
-__device__ int count_lt(const double* __restrict__ a, int n, double v)
-{
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (a[mid] < v) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
+using rvll::count_le;              // rvll_fip_search.h
+using rvll::count_lt;
 
 __global__ __launch_bounds__(kThreads)
 void fip_index_kernel(const double* __restrict__ periods, long long n_rows, int np,

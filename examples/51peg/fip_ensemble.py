@@ -3,7 +3,8 @@
 planets, R independent nested-sampling runs through nested.run_nested_ensemble (their walks in one device walk per
 iteration), then p(k | y) from the median ln Z over the runs (fip.model_probabilities) and the FIP periodogram of every run
 (fip.fip_periodogram); and last the parameter table of the k = 1 model from its R runs merged by their birth contours, every entry
-with the scatter over bootstrap replicates of the runs as its error (posterior.table).  Needs a GPU.
+with the scatter over bootstrap replicates of the runs as its error (posterior.table), and the FIP periodogram of the merged runs
+of every model with the same scatter as the error of log10 FIP and of p(k | y) (fip.merged_fip).  Needs a GPU.
     python3 examples/51peg/fip_ensemble.py [R]          (default 8 runs per model)"""
 import sys
 import time
@@ -21,6 +22,7 @@ cfg = Path(__file__).with_name("config_51peg.py")
 seeds = list(range(1, R + 1))
 logzs = np.empty((R, 3))
 posteriors = [[None] * 3 for _ in range(R)]              # posteriors[r][k] = (periods [n, k], weights [n]), k >= 1
+per_model, period_columns = [], []                       # the runs of every k and the sample columns of its periods
 for k in range(3):
     rundict, datadict, priordict, fixed = read_config(cfg, nplanets=k)
     with GpuRVModel(fixed, datadict, list(priordict), priordict=priordict) as m:
@@ -30,6 +32,8 @@ for k in range(3):
                                   wrapped=wrapped_params(m.parnames), walker_runs=m.slice_walk_runs)
         dt = time.perf_counter() - t0
         cols = [m.parnames.index(f"planet{j}_period") for j in range(1, k + 1)]
+        per_model.append(res)
+        period_columns.append(cols)
         for r, out in enumerate(res):
             logzs[r, k] = out.logz
             if k:
@@ -52,3 +56,10 @@ print(f"FIP periodogram over {R} runs, {nu.size} frequencies: lowest median log1
 # the k = 1 model's parameters from its merged runs: point estimates, and the scatter over 1000 bootstrap replicates as errors
 print(f"\n1 planet, {R} runs merged:")
 print(posterior.format_table(posterior.table(one_planet, one_planet_names, nsamples=1000, seed=1, device=0)))
+
+# the periodogram of the merged runs of every model: every replicate has its own p(k | y) from its own ln Z
+mf = fip.merged_fip(per_model, period_columns, nua, nub, nsamples=1000, seed=1, device=0, nu=nu)
+best = int(np.argmin(mf["log10fip"]))
+print(f"\nFIP periodogram of the merged runs, 1000 bootstrap replicates: lowest log10 FIP {mf['log10fip'][best]:.2f} +/- "
+      f"{mf['log10fip_err'][best]:.2f} at P = {mf['periods'][best]:.4f} d")
+print("p(k | y) for k = 0, 1, 2:", " ".join(f"{p:.4g} +/- {e:.2g}" for p, e in zip(mf["pky"], mf["pky_err"])))

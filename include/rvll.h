@@ -62,7 +62,8 @@ extern "C" {
                                        rvll_slice_walk_runs_steps, rvll_walk_distances_runs, rvll_live_runs_step_steps,
                                        rvll_set_walk_proposal (RVLL_PROPOSAL_CHORD / _STEPOUT),
                                        rvll_merge_runs, rvll_merge_replicates (rvll_merge_timing),
-                                       rvll_posterior_replicates (rvll_posterior_timing) */
+                                       rvll_posterior_replicates (rvll_posterior_timing),
+                                       rvll_fip_replicates (rvll_fip_merged_timing) */
 
 /* ---- error codes ------------------------------------------------------ */
 #define RVLL_OK             0
@@ -711,6 +712,43 @@ int rvll_posterior_replicates(int32_t device, const double* logl /*[n_rows]*/, c
                               double* logz /*[nsamples]*/, double* info /*[nsamples]*/, double* mean /*[nsamples * n_cols]*/,
                               double* sd /*[nsamples * n_cols]*/, double* quant /*[nsamples * n_q * n_cols]*/,
                               int64_t block_bytes, rvll_posterior_timing* timing);
+
+/* ---- FIP periodogram of the merged run's replicates (post-processing; independent of any model handle) ----------- */
+/* Per replicate s of rvll_merge_replicates (same seeds, multiplicities and merged order) the true inclusion probability of
+ * every frequency bin of one planet model (evidence_amd/fip.py, merged_tip_arrays, is the definition).  periods
+ * [n_rows, n_planets] is row-major in input row order, finite and positive.  Row i and planet j span the bins [beg, end) with
+ * omega = 6.283185307179586 / P_ij, beg = #{nub <= omega}, end = #{nua < omega} (rvll_fip_accumulate's spans; empty when
+ * beg >= end); the row covers the union of its spans, a bin once.  With p_i = exp(logwt_i) (0 for a row without weight) and
+ * P = sum p:  tip[s * nfreq + b] = sum of p_i over the rows that cover b, over P, clamped to [0, 1]; exactly 0 for a bin that no
+ * row covers (decided from integer counts); NaN in a replicate in which no row has weight.  logz[s], info[s] as
+ * rvll_merge_replicates gives them.  The weights stay on the device: a block of replicates is reduced where it was written.
+ * block_bytes bounds the per-call event tables (with m = n_rows * n_planets and t = ceil(m / 1024): 8 m + 8 nfreq + 8 (t + 1)
+ * bytes) plus, a replicate, its weights and its two running sums (8 n_rows + 16 nfreq bytes); 0 stands for the tables plus
+ * 8 GiB, of which only nsamples replicates are allocated.  RVLL_E_NOMEM before any work when the tables and one replicate do
+ * not fit.  A replicate's results do not depend on the others of the call or on the batching.
+ * RVLL_E_INVALID: everything rvll_merge_replicates refuses; n_planets outside [1, RVLL_FIP_MAX_PLANETS], nfreq outside
+ * [1, 2^30], n_rows * n_planets >= 2^31, nua or nub that decrease or hold NaN, a period that is not finite and positive, null
+ * buffers.  timing may be NULL.  device < 0 uses the current device. */
+typedef struct rvll_fip_merged_timing {
+    double  kernel_ms;       /* HIP-event time of all device work: setup_ms + weights_ms + reduce_ms                       */
+    double  total_ms;        /* the whole call: checks, allocation, uploads, kernels, downloads                            */
+    double  setup_ms;        /* the merge's setup, the span kernel, two radix sorts, the count and tile tables              */
+    double  weights_ms;      /* the replicate kernels (what rvll_merge_replicates spends on the same input)                 */
+    double  reduce_ms;       /* exp and P of the block, the (replicate, list) coverage kernel and the TIP kernel            */
+    int64_t rows;            /* n_rows                                                                                      */
+    int64_t elements;        /* (row, replicate) pairs: n_rows * nsamples                                                   */
+    int64_t events;          /* entries of the two event lists together: 2 * n_rows * n_planets                             */
+    int32_t launches;        /* 11 for the setup, then 4 a block of replicates (a rocPRIM sort counted as one)              */
+    int32_t threads;         /* per workgroup; one workgroup per replicate (weights, exp) and per (replicate, list)         */
+    int32_t blocks;          /* blocks of replicates the call was split into                                                */
+    int32_t key_bits;        /* bits of a bin key that the radix sorts pass over: ceil(log2(nfreq + 1))                     */
+} rvll_fip_merged_timing;
+int rvll_fip_replicates(int32_t device, const double* logl /*[n_rows]*/, const double* birth /*[n_rows]*/, int64_t n_rows,
+                        const int64_t* run_start /*[n_runs + 1]*/, int32_t n_runs,
+                        const double* periods /*[n_rows * n_planets]*/, int32_t n_planets, const double* nua /*[nfreq]*/,
+                        const double* nub /*[nfreq]*/, int32_t nfreq, int32_t nsamples, int32_t mode, int32_t bootstrap,
+                        uint64_t seed, double* logz /*[nsamples]*/, double* info /*[nsamples]*/,
+                        double* tip /*[nsamples * nfreq]*/, int64_t block_bytes, rvll_fip_merged_timing* timing);
 
 /* ---- diagnostics -------------------------------------------------------------- */
 /* Evaluate one device math routine elementwise (tests only; no reference counterpart):
