@@ -112,6 +112,12 @@ class FipMergedTiming(C.Structure):
                 ("launches", C.c_int32), ("threads", C.c_int32), ("blocks", C.c_int32), ("key_bits", C.c_int32)]
 
 
+class MarginalTiming(C.Structure):
+    _fields_ = [("kernel_ms", C.c_double), ("total_ms", C.c_double), ("setup_ms", C.c_double), ("weights_ms", C.c_double),
+                ("reduce_ms", C.c_double), ("rows", C.c_int64), ("elements", C.c_int64), ("bins", C.c_int64),
+                ("launches", C.c_int32), ("threads", C.c_int32), ("blocks", C.c_int32), ("groups", C.c_int32)]
+
+
 SHRINK_RANDOM, SHRINK_EXPECTED = 0, 1
 FIP_MAX_PLANETS = 8
 Handle = C.c_void_p
@@ -211,6 +217,10 @@ PROTOTYPES = {
     "rvll_fip_replicates": (C.c_int, [C.c_int32, _dp, _dp, C.c_int64, C.POINTER(C.c_int64), C.c_int32, _dp, C.c_int32, _dp, _dp,
                                       C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, _dp, _dp, _dp, C.c_int64,
                                       C.POINTER(FipMergedTiming)]),
+    "rvll_marginal_replicates": (C.c_int, [C.c_int32, _dp, _dp, C.c_int64, C.POINTER(C.c_int64), C.c_int32, _dp, C.c_int32, _dp,
+                                           _ip, C.POINTER(C.c_int64), C.c_int32, _ip, C.c_int32, C.c_int32, C.c_int32,
+                                           C.c_int32, C.c_uint64, _dp, _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _dp,
+                                           _dp, _dp, C.c_int64, C.POINTER(MarginalTiming)]),
     "rvll_dev_trace_loglike": (C.c_int, [Handle, C.c_int64, C.c_int32, C.POINTER(C.c_uint64), C.c_int64, _ip, _ip]),
     "rvll_debug_eval": (C.c_int, [Handle, C.c_int32, _dp, _dp, C.c_int64, _dp]),
     "rvll_last_error": (C.c_char_p, []),

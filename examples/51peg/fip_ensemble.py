@@ -4,7 +4,8 @@ planets, R independent nested-sampling runs through nested.run_nested_ensemble (
 iteration), then p(k | y) from the median ln Z over the runs (fip.model_probabilities) and the FIP periodogram of every run
 (fip.fip_periodogram); and last the parameter table of the k = 1 model from its R runs merged by their birth contours, every entry
 with the scatter over bootstrap replicates of the runs as its error (posterior.table), and the FIP periodogram of the merged runs
-of every model with the same scatter as the error of log10 FIP and of p(k | y) (fip.merged_fip).  Needs a GPU.
+of every model with the same scatter as the error of log10 FIP and of p(k | y) (fip.merged_fip), and the period marginal of the k = 1 model with
+the same scatter as the error of every bin (marginals.marginals).  Needs a GPU.
     python3 examples/51peg/fip_ensemble.py [R]          (default 8 runs per model)"""
 import sys
 import time
@@ -13,7 +14,7 @@ from pathlib import Path
 import numpy as np
 
 sys.path.insert(0, str(Path(__file__).resolve().parents[2]))
-from evidence_amd import GpuRVModel, fip, posterior, run_nested_ensemble      # noqa: E402
+from evidence_amd import GpuRVModel, fip, marginals, posterior, run_nested_ensemble      # noqa: E402
 from evidence_amd.callbacks import make_ultranest_callbacks, wrapped_params   # noqa: E402
 from evidence_amd.config import read_config                        # noqa: E402
 
@@ -63,3 +64,11 @@ best = int(np.argmin(mf["log10fip"]))
 print(f"\nFIP periodogram of the merged runs, 1000 bootstrap replicates: lowest log10 FIP {mf['log10fip'][best]:.2f} +/- "
       f"{mf['log10fip_err'][best]:.2f} at P = {mf['periods'][best]:.4f} d")
 print("p(k | y) for k = 0, 1, 2:", " ".join(f"{p:.4g} +/- {e:.2g}" for p, e in zip(mf["pky"], mf["pky_err"])))
+
+# the period marginal of the k = 1 model from its merged runs: the density of every bin with its scatter over the replicates
+mg = marginals.marginals(one_planet, one_planet_names, columns=["planet1_period"], bins=20, corner=False, nsamples=1000, seed=1,
+                         device=0)["panels"][0]
+print("\nplanet1_period marginal (density per day, +/- over 1000 bootstrap replicates, min .. max):")
+for lo, hi, d, e, a, b in zip(mg["edges"][0][:-1], mg["edges"][0][1:], mg["density"], mg["density_err"], mg["density_min"],
+                              mg["density_max"]):
+    print(f"  [{lo:.6f}, {hi:.6f})  {d:10.1f} +/- {e:8.1f}   {a:10.1f} .. {b:10.1f}")

@@ -63,7 +63,8 @@ extern "C" {
                                        rvll_set_walk_proposal (RVLL_PROPOSAL_CHORD / _STEPOUT),
                                        rvll_merge_runs, rvll_merge_replicates (rvll_merge_timing),
                                        rvll_posterior_replicates (rvll_posterior_timing),
-                                       rvll_fip_replicates (rvll_fip_merged_timing) */
+                                       rvll_fip_replicates (rvll_fip_merged_timing),
+                                       rvll_marginal_replicates (rvll_marginal_timing) */
 
 /* ---- error codes ------------------------------------------------------ */
 #define RVLL_OK             0
@@ -749,6 +750,54 @@ int rvll_fip_replicates(int32_t device, const double* logl /*[n_rows]*/, const d
                         const double* nub /*[nfreq]*/, int32_t nfreq, int32_t nsamples, int32_t mode, int32_t bootstrap,
                         uint64_t seed, double* logz /*[nsamples]*/, double* info /*[nsamples]*/,
                         double* tip /*[nsamples * nfreq]*/, int64_t block_bytes, rvll_fip_merged_timing* timing);
+
+/* ---- marginal histograms of the merged run's replicates (post-processing; independent of any model handle) ------- */
+/* Per replicate s of rvll_merge_replicates (same seeds, multiplicities and merged order) the posterior mass of every bin of a
+ * list of one- and two-dimensional histograms of the columns of values [n_rows, n_cols] (row-major, in input row order), and per
+ * bin the statistics of that mass over the replicates (evidence_amd/marginals.py is the definition).  Axis a is the
+ * column axis_col[a] with the edges edges[axis_edge_start[a] .. axis_edge_start[a + 1]) (2 to 4097 of them, finite, strictly
+ * increasing).  The bin of x is numpy's histogram's: #{edges <= x} - 1, x equal to the last edge in the last bin, x below the
+ * first or above the last edge outside.  Panel t has the axes panel_axes[2 t] and panel_axes[2 t + 1] (-1: one-dimensional; else
+ * its bins are row-major with the first axis the major index; a row outside either axis is outside the panel) and at most 4096
+ * bins, which are panel_start[t] .. panel_start[t + 1] of one flat array of nbins bins, panel after panel.
+ * counts[b]: the rows in bin b; outside_count[t]: the rows outside panel t.  With p_i = exp(logwt_i) (0 for a row without
+ * weight), m_i = rint(p_i 2^62) as int64 and M = sum m:  mass = (double)(sum of m_i over the rows of the bin) / (double)M and
+ * the same for a panel's outside rows; NaN throughout a replicate with M = 0 (a bootstrap of empty runs).  Every sum over rows
+ * is an integer sum.  stats[k * nbins + b], k = 0 .. 3: mean, standard deviation (ddof 0), minimum and maximum of mass over the
+ * replicates that are not NaN, by a sequential Welford update in replicate order (NaN where there is none).  mass
+ * [nsamples * nbins] and outside [nsamples * n_panels] may each be NULL.  logz[s], info[s] as rvll_merge_replicates gives them.
+ * block_bytes bounds the bin table (2 * n_rows * n_axes bytes) plus, a replicate, its weights and its histograms
+ * (8 * (n_rows + nbins + n_panels) bytes); 0 stands for the table plus 8 GiB, of which only nsamples replicates are allocated.
+ * RVLL_E_NOMEM before any work when the table and one replicate do not fit.  The results do not depend on the batching, on the
+ * other replicates or on the other panels of the call.
+ * RVLL_E_INVALID: everything rvll_merge_replicates refuses; n_cols outside [1, 64], n_axes outside [1, 128], n_panels outside
+ * [1, 256], an axis with fewer than 2 or more than 4097 edges, edges that are not finite or do not strictly increase, a panel of
+ * more than 4096 bins, an axis or column index out of range, a value that is not finite, null required buffers.  timing may be
+ * NULL.  device < 0 uses the current device. */
+typedef struct rvll_marginal_timing {
+    double  kernel_ms;       /* HIP-event time of all device work: setup_ms + weights_ms + reduce_ms                       */
+    double  total_ms;        /* the whole call: checks, allocation, uploads, kernels, downloads                            */
+    double  setup_ms;        /* the merge's setup, the bin table and the counts                                            */
+    double  weights_ms;      /* the replicate kernels (what rvll_merge_replicates spends on the same input)                 */
+    double  reduce_ms;       /* fixed point, the histogram kernel and the statistics                                       */
+    int64_t rows;            /* n_rows                                                                                      */
+    int64_t elements;        /* (row, replicate) pairs: n_rows * nsamples                                                   */
+    int64_t bins;            /* nbins: the bins of all panels together                                                      */
+    int32_t launches;        /* 6 for the setup, then 4 a block of replicates (a rocPRIM sort counted as one)               */
+    int32_t threads;         /* per workgroup of the histogram kernel                                                       */
+    int32_t blocks;          /* blocks of replicates the call was split into                                                */
+    int32_t groups;          /* panel groups: each is one pass over a replicate's weights                                   */
+} rvll_marginal_timing;
+int rvll_marginal_replicates(int32_t device, const double* logl /*[n_rows]*/, const double* birth /*[n_rows]*/, int64_t n_rows,
+                             const int64_t* run_start /*[n_runs + 1]*/, int32_t n_runs,
+                             const double* values /*[n_rows * n_cols]*/, int32_t n_cols, const double* edges,
+                             const int32_t* axis_col /*[n_axes]*/, const int64_t* axis_edge_start /*[n_axes + 1]*/,
+                             int32_t n_axes, const int32_t* panel_axes /*[2 * n_panels]*/, int32_t n_panels, int32_t nsamples,
+                             int32_t mode, int32_t bootstrap, uint64_t seed, double* logz /*[nsamples]*/,
+                             double* info /*[nsamples]*/, int64_t* counts /*[nbins]*/, int64_t* outside_count /*[n_panels]*/,
+                             double* stats /*[4 * nbins]*/, double* mass /*NULL or [nsamples * nbins]*/,
+                             double* outside /*NULL or [nsamples * n_panels]*/, int64_t block_bytes,
+                             rvll_marginal_timing* timing);
 
 /* ---- diagnostics -------------------------------------------------------------- */
 /* Evaluate one device math routine elementwise (tests only; no reference counterpart):
