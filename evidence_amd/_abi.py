@@ -221,6 +221,10 @@ PROTOTYPES = {
                                            _ip, C.POINTER(C.c_int64), C.c_int32, _ip, C.c_int32, C.c_int32, C.c_int32,
                                            C.c_int32, C.c_uint64, _dp, _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _dp,
                                            _dp, _dp, C.c_int64, C.POINTER(MarginalTiming)]),
+    "rvll_region_draw_runs": (C.c_int, [Handle, _dp, C.POINTER(C.c_int64), C.c_int64, _dp, _dp, _dp, C.POINTER(C.c_uint64), _ip,
+                                        C.c_int32, C.c_int64, C.c_int64, C.c_int32, _dp, _dp, _dp, _ip, C.POINTER(C.c_int64),
+                                        C.c_int64, _dp, _ip, _ip, _dp, C.POINTER(C.c_int64), _ip]),
+    "rvll_region_tile_rows": (C.c_int, [C.c_int32, _ip]),
     "rvll_dev_trace_loglike": (C.c_int, [Handle, C.c_int64, C.c_int32, C.POINTER(C.c_uint64), C.c_int64, _ip, _ip]),
     "rvll_debug_eval": (C.c_int, [Handle, C.c_int32, _dp, _dp, C.c_int64, _dp]),
     "rvll_last_error": (C.c_char_p, []),

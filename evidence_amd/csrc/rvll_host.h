@@ -5,6 +5,7 @@
 //   rvll_walk_host.hip  the sampler's proposal step: the device walk in its forms, the resident live set (rvll_live_*)
 //   rvll_comm.hip       multi-GPU: RCCL communicators, lanes, all-gathers
 //   rvll_cluster_host.hip  MLFriends clustering of many row sets (rvll_cluster_runs)
+//   rvll_region.hip     MLFriends region sampling (rvll_region_draw_runs): kernels and host side
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -210,6 +211,9 @@ struct rvll_handle {
     size_t adapt_cap = 0;                                     // bytes
     void* d_adapt_in = nullptr;                               // rvll_walk_distances_runs' inputs; the resident step's walker start rows
     size_t adapt_in_cap = 0;                                  // bytes
+    // region sampling (rvll_region_draw_runs): one grow-only block of inputs, per-candidate work, per-run state, outputs, trace
+    void* d_region = nullptr;
+    size_t region_cap = 0;                                    // bytes
     // the clustered step of the resident ensemble (rvll_live_runs_step_clustered): grow-only block of the per-(run, cluster) segments
     // — (offset, rows) [S][2], fold scales [S][2], mean [S][D], covariance [S][D, D] — and what the last clustered step found, for
     // rvll_live_runs_clusters: per listed run the survivors' labels in rank order [A m], the metric scale [A D], the cluster count,

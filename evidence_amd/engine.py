@@ -415,6 +415,60 @@ class GpuRVModel:
             _abi.as_ip(labels), _abi.as_ip(nclusters), _abi.as_dp(radius2)))
         return labels, nclusters, radius2
 
+    def region_tile_rows(self):
+        """The survivors of a run that one LDS image of the region sampler's neighbour count holds (more are tiled)."""
+        rows = C.c_int32(0)
+        _abi.check(self._lib.rvll_region_tile_rows(self.ndim, C.byref(rows)))
+        return int(rows.value)
+
+    def region_draw_runs(self, survivors, run_start, scale, radius2, lstar, seeds, kdraw, wrapped=None, max_candidates=None,
+                         trace=False, first=0, block=None, trace_cap=None, return_rounds=False):
+        """MLFriends region sampling of R runs in one device call (rvll_region_draw_runs; region.draw_runs is the
+        definition, with this model's prior transform and log-L as its `evaluate`).  Returns (cube [R, kdraw, ndim], theta
+        [R, kdraw, ndim], logl [R, kdraw], nfound [R] int32, ncalls [R] int64), rows past nfound NaN.  trace=True adds a list
+        of R dicts (c, cube, flags, n, logl) over the first trace_cap candidates every run evaluated (default: all of them);
+        return_rounds=True adds the rounds the call took.  Needs the priors (priordict=)."""
+        from . import region as _region
+        if max_candidates is None:
+            max_candidates = _region.DEFAULT_MAX_CANDIDATES
+        if block is None:
+            block = _region.DEFAULT_BLOCK
+        survivors = np.ascontiguousarray(self._theta2d(survivors), dtype=np.float64)
+        survivors, run_start, scale, radius2, lstar, seeds, kdraw, wr, first, max_candidates, block = _region.check_args(
+            survivors, run_start, scale, radius2, lstar, seeds, kdraw, wrapped, first, max_candidates, block)
+        R, D = run_start.shape[0] - 1, self.ndim
+        wi = None if wr is None else np.ascontiguousarray(wr.astype(np.int32))
+        cube = np.full((R, kdraw, D), np.nan)
+        theta = np.full((R, kdraw, D), np.nan)
+        logl = np.full((R, kdraw), np.nan)
+        nfound = np.zeros(R, dtype=np.int32)
+        ncalls = np.zeros(R, dtype=np.int64)
+        cap = 0
+        if trace:
+            cap = int(max_candidates if trace_cap is None else trace_cap)
+        tcube = np.full((R, cap, D), np.nan)
+        tflags = np.zeros((R, cap), dtype=np.int32)
+        tn = np.zeros((R, cap), dtype=np.int32)
+        tlogl = np.full((R, cap), np.nan)
+        tcount = np.zeros(R, dtype=np.int64)
+        rounds = C.c_int32(0)
+        i64 = C.POINTER(C.c_int64)
+        _abi.check(self._lib.rvll_region_draw_runs(
+            self._h, _abi.as_dp(survivors), run_start.ctypes.data_as(i64), R, _abi.as_dp(scale), _abi.as_dp(radius2),
+            _abi.as_dp(lstar), seeds.ctypes.data_as(C.POINTER(C.c_uint64)), _abi.as_ip(wi) if wi is not None else None,
+            kdraw, first, max_candidates, block, _abi.as_dp(cube), _abi.as_dp(theta), _abi.as_dp(logl), _abi.as_ip(nfound),
+            ncalls.ctypes.data_as(i64), cap, _abi.as_dp(tcube) if cap else None, _abi.as_ip(tflags) if cap else None,
+            _abi.as_ip(tn) if cap else None, _abi.as_dp(tlogl) if cap else None, tcount.ctypes.data_as(i64) if cap else None,
+            C.byref(rounds)))
+        out = (cube, theta, logl, nfound, ncalls)
+        if trace:
+            out += ([{"c": np.arange(first, first + int(tcount[r]), dtype=np.uint64), "cube": tcube[r, :tcount[r]].copy(),
+                      "flags": tflags[r, :tcount[r]].copy(), "n": tn[r, :tcount[r]].astype(np.int64),
+                      "logl": tlogl[r, :tcount[r]].copy()} for r in range(R)],)
+        if return_rounds:
+            out += (int(rounds.value),)
+        return out
+
     def cluster(self, cube, scale, wrapped=None, nboot=30, seed=0):
         """One run of cluster_runs: (labels [N], nclusters, radius2)."""
         cube = self._theta2d(cube)

@@ -41,6 +41,10 @@ class NestedResult:
     far_fraction: np.ndarray = None  # adaptive_nsteps: the far walkers' share of the counted ones per iteration, NaN where none counted
     nlive_row: np.ndarray = None  # a merged run (merge.py): the live count at every death, which varies from row to row
     run_index: np.ndarray = None  # a merged run: the input run every row comes from
+    region_fallbacks: int = None  # proposal="region": the points the chord walk supplied because the region draw stayed short
+    region_efficiency: np.ndarray = None  # proposal="region": accepted / likelihood calls of the region draw, per iteration (NaN: no call)
+    region_calls: np.ndarray = None  # proposal="region": the region draw's likelihood calls per iteration
+    region_fallback_calls: int = None  # proposal="region": the likelihood calls of the fallback walks
 
 
 def _logaddexp_many(x):
@@ -373,6 +377,186 @@ def _adapt_counts(entries, distances, wrapped):
     return far_counts(pair, move, wg, np.concatenate(wr), len(entries))
 
 
+# ---- MLFriends region sampling (proposal="region"; DESIGN §4n, region.py) ----------------------------------------------------
+_REGION_MUL = 0xA0761D6478BD642F        # region seed of an iteration: seed * _REGION_MUL + it
+
+
+def _check_region(live, walker, adaptive_nsteps, step_width=1.0):
+    """The arguments that proposal="region" refuses."""
+    if live is not None:
+        raise ValueError('proposal="region" does not work with live=: the resident live sets keep their slice walks '
+                         "(region sampling runs in the host-managed drivers only)")
+    if walker is not None:
+        raise ValueError('proposal="region" finishes short runs through walker_runs= (GpuRVModel.slice_walk_runs) or the host '
+                         "walk, not through walker=")
+    if adaptive_nsteps is not None:
+        raise ValueError('adaptive_nsteps does not apply with proposal="region": a region draw takes no steps')
+
+
+def _host_chord_walk(wu, wt, wl, lstar, chol, wrapped, nsteps, rng, evaluate):
+    """nsteps chord moves of every walker inside logL > lstar, as run_nested_slice's host loop makes them (one whitening
+    factor); wu / wt / wl are updated in place.  Returns the likelihood calls."""
+    k, ndim = wu.shape
+    ncall = 0
+    for _ in range(nsteps):
+        z = rng.standard_normal((k, ndim))
+        d = z @ chol.T
+        d /= np.linalg.norm(d, axis=1, keepdims=True)
+        tmin, tmax = _chord(wu, d, wrapped)
+        todo = np.arange(k)
+        rounds = 0
+        while todo.size and rounds < 200:
+            t = tmin[todo] + (tmax[todo] - tmin[todo]) * rng.random(todo.size)
+            cand = wu[todo] + t[:, None] * d[todo]
+            if wrapped is not None:
+                cand[:, wrapped] %= 1.0
+            cand = np.clip(cand, 0.0, np.nextafter(1.0, 0.0))
+            ct, cl = evaluate(cand)
+            ncall += todo.size
+            ok = cl > lstar
+            acc = todo[ok]
+            wu[acc], wt[acc], wl[acc] = cand[ok], ct[ok], cl[ok]
+            rej = todo[~ok]
+            neg = t[~ok] < 0
+            tmin[rej[neg]] = t[~ok][neg]
+            tmax[rej[~neg]] = t[~ok][~neg]
+            todo = rej
+            rounds += 1
+    return ncall
+
+
+def _region_ensemble(prior, loglike, ndim, seeds, nlive, kbatch, nsteps, dlogz, max_iter, max_calls, wrapped, walker_runs, nboot,
+                     clusterer, region_runs, region_max_candidates, precision_criterion, prior_loglike=None):
+    """proposal="region" of run_nested_slice (one seed) and run_nested_ensemble: the runs in lockstep, per iteration ONE
+    clusterer call (every running run's scale and MLFriends radius2) and ONE region_runs call (kbatch draws of every running
+    run), then the chord walk for whatever a run is short of.  Every draw of a run depends on its own seed, iteration and
+    survivors alone, so result[r] is the one-seed run bit for bit."""
+    from . import region as _region
+    clusterer = _default_clusterer(clusterer)
+    defaults = ultranest_defaults(ndim)
+    nlive = int(nlive or defaults["nlive"])
+    kbatch = int(kbatch or max(1, nlive // 4))
+    if not 1 <= kbatch < nlive:
+        raise ValueError("need 1 <= kbatch < nlive")
+    nsteps = int(nsteps or defaults["nsteps"])
+    cap = int(_region.DEFAULT_MAX_CANDIDATES if region_max_candidates is None else region_max_candidates)
+    if cap < 0:
+        raise ValueError("region_max_candidates must not be negative")
+    wrapped = None if wrapped is None else np.asarray(wrapped, dtype=bool)
+
+    def evaluate(cand):
+        if prior_loglike is not None:
+            ct, cl = prior_loglike(cand)
+            return np.asarray(ct, dtype=np.float64), np.asarray(cl, dtype=np.float64)
+        ct = np.asarray(prior(cand), dtype=np.float64)
+        return ct, np.asarray(loglike(ct), dtype=np.float64)
+
+    if region_runs is None:
+        def region_runs(surv, run_start, scale, radius2, lstar, rseeds, kdraw, wrapped=None, max_candidates=cap):
+            return _region.draw_runs(surv, run_start, scale, radius2, lstar, rseeds, kdraw, evaluate, wrapped=wrapped,
+                                     max_candidates=max_candidates)
+    runs = [_EnsembleRun(s, nlive, ndim) for s in seeds]
+    for r in runs:
+        r.fallbacks, r.fallback_calls, r.eff, r.rcalls = 0, 0, [], []
+    theta, logl = evaluate(np.concatenate([r.u for r in runs]))
+    for i, r in enumerate(runs):
+        r.theta, r.logl = theta[i * nlive:(i + 1) * nlive].copy(), logl[i * nlive:(i + 1) * nlive].copy()
+    stop_gap = np.log(np.expm1(dlogz))
+    while True:
+        turn = []                                   # (run, dead rows, lstar, surviving rows in rank order)
+        for r in runs:
+            if r.done:
+                continue
+            if not (r.it < max_iter and r.ncall < max_calls):
+                r.done = True
+                continue
+            t0 = time.perf_counter()
+            order = _stable_argsort(r.logl)
+            dead = order[:kbatch]
+            lstar = r.logl[dead[-1]]
+            dl = r.logl[dead]
+            logw, r.logz, r.h, r.logx = _deaths(r.logz, r.h, r.logx, dl, nlive, kbatch)
+            r.dead_theta.append(r.theta[dead])
+            r.dead_logl.append(dl); r.dead_logw.append(logw)
+            r.dead_birth.append(r.birth[dead])
+            r.birth[dead] = lstar
+            r.it += kbatch
+            turn.append((r, dead, lstar, order[kbatch:]))
+            r.timing["host_s"] += time.perf_counter() - t0
+        if not turn:
+            break
+        t0 = time.perf_counter()
+        uas = [r.u[alive] for r, _d, _l, alive in turn]
+        run_start = np.concatenate([[0], np.cumsum([len(ua) for ua in uas])]).astype(np.int64)
+        surv = np.concatenate(uas)
+        scales = np.stack([_cluster_scale(ua) for ua in uas])
+        _lab, ncl, radius2 = clusterer(surv, run_start, scales, wrapped, nboot, [(r.seed * _BOOT_MUL + r.it) & _M64 for r, *_x in turn])
+        t1 = time.perf_counter()
+        cu, ct, cl, nfound, ncalls = region_runs(surv, run_start, scales, np.asarray(radius2, dtype=np.float64),
+                                                 np.array([t[2] for t in turn], dtype=np.float64),
+                                                 [(r.seed * _REGION_MUL + r.it) & _M64 for r, *_x in turn], kbatch,
+                                                 wrapped=wrapped, max_candidates=cap)
+        t2 = time.perf_counter()
+        # the chord walk for the points a run is short of: start rows and walk seed from the run's own generator
+        short = []
+        for j, (r, dead, lstar, alive) in enumerate(turn):
+            nf = int(nfound[j])
+            r.nclusters.append(int(ncl[j]))
+            r.rcalls.append(int(ncalls[j]))
+            r.eff.append(nf / int(ncalls[j]) if int(ncalls[j]) > 0 else float("nan"))
+            r.ncall += int(ncalls[j])
+            rows = dead[:nf]
+            r.u[rows], r.theta[rows], r.logl[rows] = cu[j, :nf], ct[j, :nf], cl[j, :nf]
+            if nf < kbatch:
+                k = kbatch - nf
+                start = alive[r.rng.integers(0, len(alive), k)]
+                short.append((r, dead[nf:], lstar, _whitening(uas[j]), start, int(r.rng.integers(0, 2 ** 62))))
+                r.fallbacks += k
+        if short and walker_runs is not None:
+            sizes = [len(rows) for _r, rows, *_x in short]
+            wu, wt, wl, used = walker_runs(np.concatenate([r.u[st] for r, _rows, _l, _c, st, _s in short]),
+                                           np.concatenate([r.theta[st] for r, _rows, _l, _c, st, _s in short]),
+                                           np.concatenate([r.logl[st] for r, _rows, _l, _c, st, _s in short]),
+                                           np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64),
+                                           np.array([t[2] for t in short], dtype=np.float64), np.stack([t[3] for t in short]),
+                                           wrapped, nsteps, 200, [t[5] for t in short])
+            a = 0
+            for g, (r, rows, *_x) in enumerate(short):
+                b = a + len(rows)
+                r.u[rows], r.theta[rows], r.logl[rows] = wu[a:b], wt[a:b], wl[a:b]
+                r.ncall += int(used[g]); r.fallback_calls += int(used[g])
+                a = b
+        else:
+            for r, rows, lstar, chol, start, _wseed in short:
+                wu, wt, wl = r.u[start], r.theta[start], r.logl[start]
+                used = _host_chord_walk(wu, wt, wl, lstar, chol, wrapped, nsteps, r.rng, evaluate)
+                r.u[rows], r.theta[rows], r.logl[rows] = wu, wt, wl
+                r.ncall += used; r.fallback_calls += used
+        t3 = time.perf_counter()
+        for r, *_x in turn:
+            if precision_criterion is not None:
+                if _precision_stop(r.logz, r.logx, r.logl, precision_criterion):
+                    r.done = True
+            elif np.max(r.logl) + r.logx < r.logz + stop_gap:
+                r.done = True
+            r.timing["walk_s"] += t3 - t1
+            r.timing["turns"] += 1
+            r.timing["host_s"] += (t1 - t0) / len(turn)
+    out = []
+    for r in runs:
+        logw_live = r.logx - np.log(nlive) + r.logl
+        logz_final = np.logaddexp(r.logz, _logaddexp_many(logw_live))
+        all_theta = np.vstack([a.reshape(-1, ndim) for a in r.dead_theta] + [r.theta])
+        all_logl = np.concatenate(r.dead_logl + [r.logl])
+        all_logw = np.concatenate(r.dead_logw + [logw_live]) - logz_final
+        out.append(NestedResult(float(logz_final), float(np.sqrt(max(r.h, 0.0) / nlive)), r.it, r.ncall, float(r.h),
+                                all_theta, all_logl, all_logw, r.timing, np.array(r.nclusters, dtype=np.int64), nlive=nlive,
+                                kbatch=kbatch, logl_birth=np.concatenate(r.dead_birth + [r.birth]),
+                                region_fallbacks=int(r.fallbacks), region_efficiency=np.array(r.eff, dtype=np.float64),
+                                region_calls=np.array(r.rcalls, dtype=np.int64), region_fallback_calls=int(r.fallback_calls)))
+    return out
+
+
 def run_nested_slice(prior: Callable, loglike: Callable, ndim: int, nlive: Optional[int] = None, kbatch: Optional[int] = None,
                      nsteps: Optional[int] = None, dlogz: float = 0.5, max_iter: int = 10_000_000,
                      max_calls: int = 50_000_000, wrapped=None, seed: int = 0,
@@ -381,7 +565,8 @@ def run_nested_slice(prior: Callable, loglike: Callable, ndim: int, nlive: Optio
                      clusterer: Optional[Callable] = None, walker_runs: Optional[Callable] = None,
                      adaptive_nsteps: Optional[str] = None, min_nsteps: Optional[int] = None, max_nsteps: Optional[int] = None,
                      distances: Optional[Callable] = None, proposal: str = "chord", step_width: float = 1.0,
-                     precision_criterion: Optional[float] = None) -> NestedResult:
+                     precision_criterion: Optional[float] = None, region_runs: Optional[Callable] = None,
+                     region_max_candidates: Optional[int] = None) -> NestedResult:
     """Nested sampling with `kbatch` deaths per iteration and batched hit-and-run slice sampling.
 
     `prior_loglike(cubes) -> (theta, logl)`, if given, replaces the prior + loglike pair inside the loop
@@ -432,7 +617,23 @@ def run_nested_slice(prior: Callable, loglike: Callable, ndim: int, nlive: Optio
     out while their ends are inside the slice.  The host walk runs stepout.walk; walker= / walker_runs= / live= get
     proposal= and step_width= (only when the proposal is not "chord").  precision_criterion (PolyChord's stop rule) replaces
     the dlogz test: stop when Z_live / (Z_dead + Z_live) < precision_criterion, Z_live = X mean(L_live).
-    polychord_kwargs(ndim, polysettings) gives the keywords of a run configured with PolyChord's settings."""
+    polychord_kwargs(ndim, polysettings) gives the keywords of a run configured with PolyChord's settings.
+
+    proposal="region" (region.py) draws the replacements by MLFriends region sampling instead of a walk: uniform
+    rejection sampling from the union of the balls around the survivors, every accepted point an exact, independent draw from
+    the prior inside the contour.  Per iteration `clusterer` (clustering.cluster_runs, or GpuRVModel.cluster_runs) gives the
+    survivors' MLFriends radius (`nboot` bootstraps) and `region_runs` (region.draw_runs on the callbacks by default, or
+    GpuRVModel.region_draw_runs) draws the kbatch points from at most `region_max_candidates` candidates (default
+    region.DEFAULT_MAX_CANDIDATES).  Points a draw stays short of come from the chord walk (`walker_runs`, or the host walk)
+    and are counted in the result's `region_fallbacks`; `region_efficiency` and `region_calls` hold every iteration's
+    accepted / calls and calls.  The run is run_nested_ensemble(..., [seed], proposal="region")[0].  Not with live= (the
+    resident live sets keep their walks), walker= or adaptive_nsteps."""
+    if proposal == "region":
+        _check_region(live, walker, adaptive_nsteps)
+        _check_precision(precision_criterion)
+        return _region_ensemble(prior, loglike, ndim, [int(seed)], nlive, kbatch, nsteps, dlogz, max_iter, max_calls, wrapped,
+                                walker_runs, nboot, clusterer, region_runs, region_max_candidates, precision_criterion,
+                                prior_loglike=prior_loglike)[0]
     pk = _walk_kwargs(proposal, step_width)
     _check_precision(precision_criterion)
     if clustering and walker is not None:
@@ -683,7 +884,8 @@ def run_nested_ensemble(prior: Callable, loglike: Callable, ndim: int, seeds, nl
                         clusterer: Optional[Callable] = None, live=None, adaptive_nsteps: Optional[str] = None,
                         min_nsteps: Optional[int] = None, max_nsteps: Optional[int] = None,
                         distances: Optional[Callable] = None, proposal: str = "chord", step_width: float = 1.0,
-                        precision_criterion: Optional[float] = None) -> list:
+                        precision_criterion: Optional[float] = None, region_runs: Optional[Callable] = None,
+                        region_max_candidates: Optional[int] = None) -> list:
     """len(seeds) independent runs of run_nested_slice in lockstep, their walks in ONE call per iteration.
 
     The reference's FIP workflow repeats independent runs of every model and takes the median and spread of ln Z over them
@@ -722,7 +924,20 @@ def run_nested_ensemble(prior: Callable, loglike: Callable, ndim: int, seeds, nl
     (GpuRVModel.live_runs_step(nsteps=[...], return_distances=True)); result[r] is then the standalone resident adaptive run.
 
     proposal= / step_width= / precision_criterion= as run_nested_slice takes them: result[r] is the standalone run of seed r with
-    the same keywords, bit for bit."""
+    the same keywords, bit for bit.
+
+    proposal="region" (with region_runs=, region_max_candidates=, nboot, clusterer as run_nested_slice takes them): one clusterer
+    call and one region_runs call per iteration for all running runs; walker_runs is optional then (it finishes short runs;
+    without it the host walk does).  result[r] is run_nested_slice(..., seed=seeds[r], proposal="region") bit for bit.  Not
+    with live=."""
+    if proposal == "region":
+        _check_region(live, None, adaptive_nsteps)
+        _check_precision(precision_criterion)
+        seeds = [int(s) for s in seeds]
+        if not seeds:
+            raise ValueError("need at least one seed")
+        return _region_ensemble(prior, loglike, ndim, seeds, nlive, kbatch, nsteps, dlogz, max_iter, max_calls, wrapped,
+                                walker_runs, nboot, clusterer, region_runs, region_max_candidates, precision_criterion)
     pk = _walk_kwargs(proposal, step_width)
     _check_precision(precision_criterion)
     seeds = [int(s) for s in seeds]

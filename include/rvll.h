@@ -64,7 +64,8 @@ extern "C" {
                                        rvll_merge_runs, rvll_merge_replicates (rvll_merge_timing),
                                        rvll_posterior_replicates (rvll_posterior_timing),
                                        rvll_fip_replicates (rvll_fip_merged_timing),
-                                       rvll_marginal_replicates (rvll_marginal_timing) */
+                                       rvll_marginal_replicates (rvll_marginal_timing),
+                                       rvll_region_draw_runs, rvll_region_tile_rows */
 
 /* ---- error codes ------------------------------------------------------ */
 #define RVLL_OK             0
@@ -798,6 +799,38 @@ int rvll_marginal_replicates(int32_t device, const double* logl /*[n_rows]*/, co
                              double* stats /*[4 * nbins]*/, double* mass /*NULL or [nsamples * nbins]*/,
                              double* outside /*NULL or [nsamples * n_panels]*/, int64_t block_bytes,
                              rvll_marginal_timing* timing);
+
+/* ---- MLFriends region sampling (evidence_amd/region.py holds the definition) -----------------------------------
+ * kdraw draws from the constrained prior of each of R runs by uniform rejection sampling from the union of the balls of
+ * radius2[r] (in the metric scale[r], as rvll_cluster_runs takes and returns them) around the run's survivors (rows
+ * run_start[r] .. run_start[r + 1] of `survivors`, unit-cube rows).  Candidates are numbered first, first + 1, ..., at most
+ * max_candidates of them a run; every random number of candidate c is uniform01(seeds[r], c << 8 | draw), so a candidate does
+ * not depend on the block, the round or the call that handles it.  Candidate c: a centre row, an offset uniform in the ball
+ * (the walk's normals), wrapped dimensions folded, any other dimension outside [0, 1) flags it RVLL_REGION_OUTSIDE; n = the
+ * survivors within radius2 (n = 0: RVLL_REGION_LOST); kept iff U n < 1; kept candidates get theta and log-L from the prior and
+ * log-L kernels of rvll_prior_loglike_batch (the same bits); accepted iff log-L > lstar[r].  In rounds, every run that is still
+ * short proposes `block` candidates (1 .. 2^20); a run's points are its first kdraw accepted candidates in candidate order:
+ * cube_out / theta_out [R, kdraw, ndim], logl_out [R, kdraw] (rows past nfound[r]: NaN), ncalls[r] = the kept candidates up to
+ * the last one taken (all kept ones when nfound[r] < kdraw).  A run without survivors, or whose ball meets its own image in a
+ * wrapped dimension (sqrt(radius2) / scale >= 0.5), draws nothing.  The results do not depend on block or on the other runs.
+ * Trace (trace_cap > 0, else the pointers may be NULL): per run the first trace_cap candidates it evaluated, trace_count[r] of
+ * them: cube [R, trace_cap, ndim], flags, n, log-L (NaN where not kept).  rounds (may be NULL): the rounds the call took.
+ * rvll_region_tile_rows: the survivors one LDS image holds at ndim parameters (more are counted tile by tile).
+ * Needs rvll_set_priors (RVLL_E_NOPRIORS).  RVLL_E_INVALID: run_start not rising from 0, a scale that is not finite and
+ * positive, a radius2 that is not finite and non-negative, a NaN lstar, kdraw / first / max_candidates negative, block out of
+ * range, a required pointer NULL; RVLL_E_UNSUPPORTED: ndim above 64; RVLL_E_NOMEM: more than 4 GiB of device work space.   */
+#define RVLL_REGION_OUTSIDE  1
+#define RVLL_REGION_LOST     2
+#define RVLL_REGION_KEPT     4
+#define RVLL_REGION_ACCEPTED 8
+int rvll_region_draw_runs(rvll_handle* h, const double* survivors /*[N, ndim]*/, const int64_t* run_start /*[R + 1]*/, int64_t R,
+                          const double* scale /*[R, ndim]*/, const double* radius2 /*[R]*/, const double* lstar /*[R]*/,
+                          const uint64_t* seeds /*[R]*/, const int32_t* wrapped /*NULL or [ndim]*/, int32_t kdraw, int64_t first,
+                          int64_t max_candidates, int32_t block, double* cube_out, double* theta_out, double* logl_out,
+                          int32_t* nfound /*[R]*/, int64_t* ncalls /*[R]*/, int64_t trace_cap, double* trace_cube,
+                          int32_t* trace_flags, int32_t* trace_n, double* trace_logl, int64_t* trace_count /*[R]*/,
+                          int32_t* rounds);
+int rvll_region_tile_rows(int32_t ndim, int32_t* rows);
 
 /* ---- diagnostics -------------------------------------------------------------- */
 /* Evaluate one device math routine elementwise (tests only; no reference counterpart):
