@@ -1,5 +1,5 @@
 // The true inclusion probability (TIP) of every frequency bin, for every replicate of a merged run, on gfx950: the FIP periodogram
-// of the merged runs of one planet model, reduced on the device from the weights that the replicate kernel of rvll_merge_setup.h
+// of the merged runs of one planet model, reduced on the device from the weights that the replicate kernel of rvll_merge_setup.hip
 // writes.  No weight leaves the device.  evidence_amd/fip.py (merged_tip_arrays) holds the numpy definition; DESIGN §4l.
 //
 // Row i of the merged run covers the union of the spans [beg, end) of its periods (the two binary searches of fip_index_kernel,
@@ -8,7 +8,7 @@
 // and both are running sums over event lists that do not depend on the replicate.
 //
 // Once per call:
-//     setup     the merge's own (rvll_merge_setup.h: keys, two sorts, place) -> the merged order and the event stream
+//     setup     the merge's own (rvll_merge_setup.hip: keys, two sorts, place) -> the merged order and the event stream
 //     spans     one thread per merged row: the spans of its np <= 8 periods, sorted by beg and merged in registers, written as
 //               np start keys and np end keys at e = i * np + k (an unused slot: the sentinel bin nfreq) with the position i
 //     sorts     per list one stable rocPRIM radix sort over ceil(log2(nfreq + 1)) key bits: the events by (bin, merged position)
@@ -28,17 +28,18 @@
 //     tip       TIP = clamp((A - E) / P) in place of A, 0 where the counts say that no interval is open, NaN without weight
 // No floating-point atomics, fixed reduction trees.  A (replicate, list) workgroup reads its replicate's slot and the per-call
 // tables only, so a replicate's bits depend on the input, the seed and its index: the same alone, in any batch, from call to call.
+// The call itself (device, stream, buffers, blocks of replicates, timing) is rvll_merge_setup.h's Replicates.
 #include "rvll_merge_setup.h"
 #include "rvll_fip_search.h"
 #include <climits>
+#include <rocprim/rocprim.hpp>
+
+using namespace rvll::merge;
 
 namespace {
 
 constexpr int kMaxPlanets = RVLL_FIP_MAX_PLANETS;
 constexpr int kMaxFreq = 1 << 30;
-// The default block of weights, as rvll_posterior.hip's: the replicate kernel runs one workgroup a replicate, so a small block
-// leaves most of the device idle (profiles/posterior_probe.txt: 2.8 s with 512 MiB against 0.24 s with 8 GiB at 2.6e6 rows).
-constexpr long long kDefaultWeightBytes = 8ll << 30;
 constexpr int kAcc = 4;
 
 // per merged row: the union of its spans as disjoint, non-touching intervals in rising order
@@ -121,19 +122,6 @@ void tile_kernel(const int32_t* __restrict__ cnt, int nfreq, long long ntiles, i
         }
         first[t] = lo;
     }
-}
-
-// the sum of v over the workgroup, in every thread: butterfly inside a wave, then the waves in order
-__device__ double block_sum(double v, double* sh)
-{
-    for (int off = 1; off < kWave; off <<= 1) v += __shfl_xor(v, off, kWave);
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    if (lane == 0) sh[wave] = v;
-    __syncthreads();
-    double r = sh[0];
-    for (int w = 1; w < kWaves; ++w) r += sh[w];
-    __syncthreads();
-    return r;
 }
 
 __global__ __launch_bounds__(kThreads)
@@ -255,165 +243,100 @@ int run_fip(int32_t device, const double* logl, const double* birth, int64_t n, 
             const double* periods, int32_t np, const double* nua, const double* nub, int32_t nfreq, int32_t nsamples, int expected,
             int bootstrap, uint64_t seed, double* logz, double* info, double* tip, int64_t block_bytes, rvll_fip_merged_timing* timing)
 {
-    const auto t_start = std::chrono::steady_clock::now();
     const long long m = n * (long long)np;                                // events a list
     const long long ntiles = (m + kTile - 1) / kTile;
     const long long per_rep = n * (long long)sizeof(double) + 2ll * nfreq * (long long)sizeof(double);
     const long long tables = 2 * m * (long long)sizeof(int32_t) + 2ll * nfreq * (long long)sizeof(int32_t) +
                              2 * (ntiles + 1) * (long long)sizeof(int32_t);
-    const long long bound = block_bytes > 0 ? block_bytes : tables + kDefaultWeightBytes;
-    if (tables + per_rep > bound)
-        return rvll::report_error(RVLL_E_NOMEM, "the event tables (%lld bytes) and one replicate of the weights and of A and E (%lld "
-                                  "bytes) are above the device block bound of %lld", tables, per_rep, bound);
-    const long long s_blk = std::min<long long>(std::min<long long>(nsamples, kMaxGroups), (bound - tables) / per_rep);
+    Replicates rep(device, logl, birth, n, run_start, n_runs, nsamples, expected, bootstrap, seed);
+    MRG_OK(rep.plan_blocks(block_bytes, tables + kDefaultWeightBytes, tables, per_rep, kMaxGroups, "the event tables",
+                           "the weights and of A and E"));
+    const long long s_blk = rep.s_blk;
     int key_bits = 1;
     while ((1ll << key_bits) <= (long long)nfreq) ++key_bits;             // ceil(log2(nfreq + 1))
-    int status = RVLL_OK;
-    int prev_device = -1;
-    double *d_logz = nullptr, *d_info = nullptr, *d_psum = nullptr, *d_w = nullptr, *d_a = nullptr, *d_e = nullptr;
-    double *d_periods = nullptr, *d_nua = nullptr, *d_nub = nullptr;
+    double *d_psum = nullptr, *d_a = nullptr, *d_e = nullptr, *d_periods = nullptr, *d_nua = nullptr, *d_nub = nullptr;
     uint32_t *d_key_a = nullptr, *d_key_e = nullptr, *d_key_s = nullptr;
     int32_t *d_pos = nullptr, *d_pos_a = nullptr, *d_pos_e = nullptr, *d_cnt_a = nullptr, *d_cnt_e = nullptr, *d_first_a = nullptr,
             *d_first_e = nullptr;
-    void* d_temp = nullptr;
+    char* d_temp = nullptr;
     size_t temp_bytes = 0;
-    MergeSetup su;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    double setup_ms = 0., weights_ms = 0., reduce_ms = 0.;
-    int launches = 0, blocks = 0;
-    const size_t shmem = bootstrap ? sizeof(int32_t) * (size_t)n_runs : 0;
     const size_t fbytes = sizeof(double) * (size_t)nfreq;
 
-    MRG_TRY(su.query(n));
     MRG_TRY(rocprim::radix_sort_pairs(nullptr, temp_bytes, d_key_a, d_key_s, d_pos, d_pos_a, (unsigned int)m, 0, key_bits,
                                       (hipStream_t) nullptr));
     temp_bytes = std::max<size_t>(temp_bytes, 1);
-    MRG_TRY(hipGetDevice(&prev_device));
-    if (device >= 0) MRG_TRY(hipSetDevice(device));
-    MRG_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-    for (auto& e : ev) MRG_TRY(hipEventCreate(&e));
-    // every device block before the first launch: running out of memory fails the call before any work
-    MRG_TRY(su.alloc(n, n_runs));
-    MRG_TRY(hipMalloc(&d_logz, sizeof(double) * (size_t)nsamples));
-    MRG_TRY(hipMalloc(&d_info, sizeof(double) * (size_t)nsamples));
-    MRG_TRY(hipMalloc(&d_psum, sizeof(double) * (size_t)nsamples));
-    MRG_TRY(hipMalloc(&d_nua, fbytes));
-    MRG_TRY(hipMalloc(&d_nub, fbytes));
-    MRG_TRY(hipMalloc(&d_pos_a, sizeof(int32_t) * (size_t)m));
-    MRG_TRY(hipMalloc(&d_pos_e, sizeof(int32_t) * (size_t)m));
-    MRG_TRY(hipMalloc(&d_cnt_a, sizeof(int32_t) * (size_t)nfreq));
-    MRG_TRY(hipMalloc(&d_cnt_e, sizeof(int32_t) * (size_t)nfreq));
-    MRG_TRY(hipMalloc(&d_first_a, sizeof(int32_t) * (size_t)(ntiles + 1)));
-    MRG_TRY(hipMalloc(&d_first_e, sizeof(int32_t) * (size_t)(ntiles + 1)));
-    MRG_TRY(hipMalloc(&d_w, sizeof(double) * (size_t)(s_blk * n)));
-    MRG_TRY(hipMalloc(&d_a, fbytes * (size_t)s_blk));
-    MRG_TRY(hipMalloc(&d_e, fbytes * (size_t)s_blk));
+    MRG_OK(rep.begin());
+    MergeSetup& su = rep.su;
+    const hipStream_t stream = rep.stream;
+    MRG_TRY(rep.alloc(d_psum, (size_t)nsamples));
+    MRG_TRY(rep.alloc(d_nua, (size_t)nfreq));
+    MRG_TRY(rep.alloc(d_nub, (size_t)nfreq));
+    MRG_TRY(rep.alloc(d_pos_a, (size_t)m));
+    MRG_TRY(rep.alloc(d_pos_e, (size_t)m));
+    MRG_TRY(rep.alloc(d_cnt_a, (size_t)nfreq));
+    MRG_TRY(rep.alloc(d_cnt_e, (size_t)nfreq));
+    MRG_TRY(rep.alloc(d_first_a, (size_t)(ntiles + 1)));
+    MRG_TRY(rep.alloc(d_first_e, (size_t)(ntiles + 1)));
+    MRG_TRY(rep.alloc(d_a, (size_t)nfreq * (size_t)s_blk));
+    MRG_TRY(rep.alloc(d_e, (size_t)nfreq * (size_t)s_blk));
     // what only the setup needs: freed before the first block of replicates
-    MRG_TRY(hipMalloc(&d_periods, sizeof(double) * (size_t)m));
-    MRG_TRY(hipMalloc(&d_key_a, sizeof(uint32_t) * (size_t)m));
-    MRG_TRY(hipMalloc(&d_key_e, sizeof(uint32_t) * (size_t)m));
-    MRG_TRY(hipMalloc(&d_key_s, sizeof(uint32_t) * (size_t)m));
-    MRG_TRY(hipMalloc(&d_pos, sizeof(int32_t) * (size_t)m));
-    MRG_TRY(hipMalloc(&d_temp, temp_bytes));
-    MRG_TRY(su.upload(logl, birth, run_start, n, n_runs, stream));
+    MRG_TRY(rep.alloc(d_periods, (size_t)m));
+    MRG_TRY(rep.alloc(d_key_a, (size_t)m));
+    MRG_TRY(rep.alloc(d_key_e, (size_t)m));
+    MRG_TRY(rep.alloc(d_key_s, (size_t)m));
+    MRG_TRY(rep.alloc(d_pos, (size_t)m));
+    MRG_TRY(rep.alloc(d_temp, temp_bytes));
     MRG_TRY(hipMemcpyAsync(d_periods, periods, sizeof(double) * (size_t)m, hipMemcpyHostToDevice, stream));
     MRG_TRY(hipMemcpyAsync(d_nua, nua, fbytes, hipMemcpyHostToDevice, stream));
     MRG_TRY(hipMemcpyAsync(d_nub, nub, fbytes, hipMemcpyHostToDevice, stream));
 
-    MRG_TRY(hipEventRecord(ev[0], stream));
-    MRG_TRY(su.launch(n, n_runs, stream));
-    {
-        hipError_t e = hipSuccess;
-        switch (np) {
-        case 1: e = launch_spans<1>(d_periods, su.order, n, d_nua, d_nub, nfreq, d_key_a, d_key_e, d_pos, stream); break;
-        case 2: e = launch_spans<2>(d_periods, su.order, n, d_nua, d_nub, nfreq, d_key_a, d_key_e, d_pos, stream); break;
-        case 3: e = launch_spans<3>(d_periods, su.order, n, d_nua, d_nub, nfreq, d_key_a, d_key_e, d_pos, stream); break;
-        case 4: e = launch_spans<4>(d_periods, su.order, n, d_nua, d_nub, nfreq, d_key_a, d_key_e, d_pos, stream); break;
-        case 5: e = launch_spans<5>(d_periods, su.order, n, d_nua, d_nub, nfreq, d_key_a, d_key_e, d_pos, stream); break;
-        case 6: e = launch_spans<6>(d_periods, su.order, n, d_nua, d_nub, nfreq, d_key_a, d_key_e, d_pos, stream); break;
-        case 7: e = launch_spans<7>(d_periods, su.order, n, d_nua, d_nub, nfreq, d_key_a, d_key_e, d_pos, stream); break;
-        default: e = launch_spans<8>(d_periods, su.order, n, d_nua, d_nub, nfreq, d_key_a, d_key_e, d_pos, stream); break;
+    MRG_OK(rep.setup([&]() -> hipError_t {
+        static constexpr decltype(&launch_spans<1>) spans[] = {launch_spans<1>, launch_spans<2>, launch_spans<3>, launch_spans<4>,
+                                                               launch_spans<5>, launch_spans<6>, launch_spans<7>, launch_spans<8>};
+        hipError_t e = spans[np - 1](d_periods, su.order, n, d_nua, d_nub, nfreq, d_key_a, d_key_e, d_pos, stream);
+        ++rep.launches;
+        for (int list = 0; list < 2 && e == hipSuccess; ++list) {
+            int32_t* cnt = list ? d_cnt_e : d_cnt_a;
+            e = rocprim::radix_sort_pairs(d_temp, temp_bytes, list ? d_key_e : d_key_a, d_key_s, d_pos, list ? d_pos_e : d_pos_a,
+                                          (unsigned int)m, 0, key_bits, stream);
+            if (e != hipSuccess) break;
+            hipLaunchKernelGGL(count_kernel, dim3(blocks_for(nfreq, kThreads)), dim3(kThreads), 0, stream, d_key_s, m, (int)nfreq, cnt);
+            if ((e = hipGetLastError()) != hipSuccess) break;
+            hipLaunchKernelGGL(tile_kernel, dim3(blocks_for(ntiles + 1, kThreads)), dim3(kThreads), 0, stream, cnt, (int)nfreq, ntiles,
+                               list ? d_first_e : d_first_a);
+            e = hipGetLastError();
+            rep.launches += 3;
         }
-        MRG_TRY(e);
-    }
-    launches += 5;
-    for (int list = 0; list < 2; ++list) {
-        int32_t* cnt = list ? d_cnt_e : d_cnt_a;
-        MRG_TRY(rocprim::radix_sort_pairs(d_temp, temp_bytes, list ? d_key_e : d_key_a, d_key_s, d_pos, list ? d_pos_e : d_pos_a,
-                                          (unsigned int)m, 0, key_bits, stream));
-        hipLaunchKernelGGL(count_kernel, dim3(blocks_for(nfreq, kThreads)), dim3(kThreads), 0, stream, d_key_s, m, (int)nfreq, cnt);
-        MRG_TRY(hipGetLastError());
-        hipLaunchKernelGGL(tile_kernel, dim3(blocks_for(ntiles + 1, kThreads)), dim3(kThreads), 0, stream, cnt, (int)nfreq, ntiles,
-                           list ? d_first_e : d_first_a);
-        MRG_TRY(hipGetLastError());
-        launches += 3;
-    }
-    MRG_TRY(hipEventRecord(ev[1], stream));
-    MRG_TRY(hipEventSynchronize(ev[1]));
-    {
-        float ms = 0.f;
-        MRG_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
-        setup_ms += ms;
-    }
-    for (void** p : {(void**)&d_periods, (void**)&d_key_a, (void**)&d_key_e, (void**)&d_key_s, (void**)&d_pos, &d_temp}) {
-        MRG_TRY(hipFree(*p));
-        *p = nullptr;
-    }
-    for (long long s0 = 0; s0 < nsamples; s0 += s_blk) {
-        const long long sb = std::min<long long>(s_blk, nsamples - s0);
-        MRG_TRY(hipEventRecord(ev[0], stream));
-        hipLaunchKernelGGL(replicate_kernel, dim3((unsigned)sb), dim3(kThreads), shmem, stream, su.ev, su.L, su.rho, (long long)n,
-                           (int)n_runs, (int)s0, (u64)seed, expected, bootstrap, d_logz, d_info, d_w);
-        MRG_TRY(hipGetLastError());
-        MRG_TRY(hipEventRecord(ev[1], stream));
+        return e;
+    }));
+    MRG_TRY(rep.free_now(d_periods));
+    MRG_TRY(rep.free_now(d_key_a));
+    MRG_TRY(rep.free_now(d_key_e));
+    MRG_TRY(rep.free_now(d_key_s));
+    MRG_TRY(rep.free_now(d_pos));
+    MRG_TRY(rep.free_now(d_temp));
+    MRG_OK(rep.run_blocks(nullptr, [&](long long s0, long long sb, double* d_w, hipStream_t) -> hipError_t {
         hipLaunchKernelGGL(exp_sum_kernel, dim3((unsigned)sb), dim3(kThreads), 0, stream, d_w, (long long)n, (int)s0, d_psum);
-        MRG_TRY(hipGetLastError());
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
         hipLaunchKernelGGL(coverage_kernel, dim3((unsigned)(2 * sb)), dim3(kThreads), 0, stream, d_w, (long long)n, d_pos_a, d_pos_e,
                            d_cnt_a, d_cnt_e, d_first_a, d_first_e, (int)nfreq, d_a, d_e);
-        MRG_TRY(hipGetLastError());
+        if ((e = hipGetLastError()) != hipSuccess) return e;
         hipLaunchKernelGGL(tip_kernel, dim3(blocks_for(sb * nfreq, kThreads)), dim3(kThreads), 0, stream, d_a, d_e, d_psum, d_cnt_a,
                            d_cnt_e, (int)nfreq, (int)s0, sb * (long long)nfreq);
-        MRG_TRY(hipGetLastError());
-        MRG_TRY(hipEventRecord(ev[2], stream));
-        launches += 4;
-        ++blocks;
-        MRG_TRY(hipMemcpyAsync(tip + s0 * (long long)nfreq, d_a, fbytes * (size_t)sb, hipMemcpyDeviceToHost, stream));
-        MRG_TRY(hipStreamSynchronize(stream));
-        float ms = 0.f;
-        MRG_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
-        weights_ms += ms;
-        MRG_TRY(hipEventElapsedTime(&ms, ev[1], ev[2]));
-        reduce_ms += ms;
-    }
-    MRG_TRY(hipMemcpyAsync(logz, d_logz, sizeof(double) * (size_t)nsamples, hipMemcpyDeviceToHost, stream));
-    MRG_TRY(hipMemcpyAsync(info, d_info, sizeof(double) * (size_t)nsamples, hipMemcpyDeviceToHost, stream));
-    MRG_TRY(hipStreamSynchronize(stream));
+        rep.launches += 3;
+        return hipGetLastError();
+    }, [&](long long s0, long long sb, double*, hipStream_t) {
+        return hipMemcpyAsync(tip + s0 * (long long)nfreq, d_a, fbytes * (size_t)sb, hipMemcpyDeviceToHost, stream);
+    }));
+    MRG_OK(rep.finish(logz, info));
+    rep.report(timing);
     if (timing) {
-        timing->kernel_ms = setup_ms + weights_ms + reduce_ms;
-        timing->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
-        timing->setup_ms = setup_ms;
-        timing->weights_ms = weights_ms;
-        timing->reduce_ms = reduce_ms;
-        timing->rows = n;
-        timing->elements = n * (long long)nsamples;
         timing->events = 2 * m;
-        timing->launches = launches;
         timing->threads = kThreads;
-        timing->blocks = blocks;
         timing->key_bits = key_bits;
     }
-
-done:
-    su.release();
-    for (void* p : {(void*)d_logz, (void*)d_info, (void*)d_psum, (void*)d_w, (void*)d_a, (void*)d_e, (void*)d_periods, (void*)d_nua,
-                    (void*)d_nub, (void*)d_key_a, (void*)d_key_e, (void*)d_key_s, (void*)d_pos, (void*)d_pos_a, (void*)d_pos_e,
-                    (void*)d_cnt_a, (void*)d_cnt_e, (void*)d_first_a, (void*)d_first_e, d_temp})
-        if (p) (void)hipFree(p);
-    for (auto& e : ev) if (e) (void)hipEventDestroy(e);
-    if (stream) (void)hipStreamDestroy(stream);
-    if (prev_device >= 0 && device >= 0) (void)hipSetDevice(prev_device);
-    return status;
+    return RVLL_OK;
 }
 
 }  // namespace
@@ -423,15 +346,8 @@ extern "C" int rvll_fip_replicates(int32_t device, const double* logl, const dou
                                    int32_t nfreq, int32_t nsamples, int32_t mode, int32_t bootstrap, uint64_t seed, double* logz,
                                    double* info, double* tip, int64_t block_bytes, rvll_fip_merged_timing* timing)
 {
-    const int rc = check_common(logl, birth, n_rows, run_start, n_runs);
-    if (rc != RVLL_OK) return rc;
-    if (nsamples < 1) return rvll::report_error(RVLL_E_INVALID, "nsamples must be >= 1");
-    if (mode != RVLL_SHRINK_RANDOM && mode != RVLL_SHRINK_EXPECTED)
-        return rvll::report_error(RVLL_E_INVALID, "mode %d is neither RVLL_SHRINK_RANDOM nor RVLL_SHRINK_EXPECTED", mode);
-    if (bootstrap != 0 && bootstrap != 1) return rvll::report_error(RVLL_E_INVALID, "bootstrap must be 0 or 1");
-    if (bootstrap && n_runs > kMaxBootRuns)
-        return rvll::report_error(RVLL_E_INVALID, "the run bootstrap takes at most %d runs", kMaxBootRuns);
-    if (block_bytes < 0) return rvll::report_error(RVLL_E_INVALID, "negative block_bytes");
+    MRG_OK(check_common(logl, birth, n_rows, run_start, n_runs));
+    MRG_OK(check_replicate_args(nsamples, mode, bootstrap, n_runs, block_bytes));
     if (n_planets < 1 || n_planets > kMaxPlanets)
         return rvll::report_error(RVLL_E_INVALID, "n_planets must be in [1, %d]", kMaxPlanets);
     if (nfreq < 1 || nfreq > kMaxFreq) return rvll::report_error(RVLL_E_INVALID, "nfreq must be in [1, %d]", kMaxFreq);

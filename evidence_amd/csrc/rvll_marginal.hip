@@ -1,10 +1,10 @@
 // Marginal posterior histograms of the replicates of a merged run on gfx950: per replicate the posterior mass of every bin of a
 // list of 1-D and 2-D panels, and per bin the mean, standard deviation, minimum and maximum of that mass over the replicates,
-// reduced on the device from the weights that the replicate kernel of rvll_merge_setup.h writes.  No weight leaves the device.
+// reduced on the device from the weights that the replicate kernel of rvll_merge_setup.hip writes.  No weight leaves the device.
 // evidence_amd/marginals.py holds the numpy definition; DESIGN §4m.
 //
 // Once per call:
-//     setup     the merge's own (rvll_merge_setup.h: keys, two sorts, place) -> the merged order
+//     setup     the merge's own (rvll_merge_setup.hip: keys, two sorts, place) -> the merged order
 //     bin       one thread per (merged row, axis): the binary search of the axis's edges by numpy's histogram convention
 //               (searchsorted(edges, x, "right") - 1, the last edge belongs to the last bin) -> a uint16 bin index, 0xFFFF for a
 //               row outside, in an axis-major table in merged order (2 N n_axes bytes).  The bin of a row does not depend on the
@@ -25,8 +25,11 @@
 // Every sum over rows is an integer sum and the sum over replicates is sequential, so the bits do not depend on the grouping of
 // panels, the chunking of rows, the block bound, the other panels or the other replicates of the call.  No floating-point
 // atomics.
+// The call itself (device, stream, buffers, blocks of replicates, timing) is rvll_merge_setup.h's Replicates.
 #include "rvll_merge_setup.h"
 #include <cstdlib>
+
+using namespace rvll::merge;
 
 namespace {
 
@@ -42,7 +45,6 @@ constexpr unsigned kOutsideBin = 0xFFFFu;
 constexpr long long kMinChunkRows = 1024;                 // chunks shrink to this only while the launch is short of workgroups
 constexpr long long kTargetGroups = 4096;                 // workgroups a hist launch aims at
 constexpr long long kMaxBlockReps = 32768;                // grid y
-constexpr long long kDefaultWeightBytes = 8ll << 30;      // as rvll_posterior.hip: a small block leaves the replicate kernel idle
 constexpr double kScale = 4611686018427387904.0;          // 2^62
 
 struct Panel {
@@ -257,36 +259,26 @@ int run_marginal(int32_t device, const double* logl, const double* birth, int64_
                  double* info, int64_t* counts, int64_t* outside_count, double* stats, double* mass, double* outside,
                  int64_t block_bytes, rvll_marginal_timing* timing)
 {
-    const auto t_start = std::chrono::steady_clock::now();
     const long long nbins = plan.nbins, nentries = nbins + n_panels;
     const long long per_rep = (n + nentries) * (long long)sizeof(double);
     const long long tables = n * (long long)n_axes * (long long)sizeof(uint16_t);
-    const long long bound = block_bytes > 0 ? block_bytes : tables + kDefaultWeightBytes;
-    if (tables + per_rep > bound)
-        return rvll::report_error(RVLL_E_NOMEM, "the bin table of %d axes (%lld bytes) and one replicate of the weights and its "
-                                  "histograms (%lld bytes) are above the device block bound of %lld", (int)n_axes, tables, per_rep,
-                                  bound);
-    const long long s_blk = std::min<long long>(std::min<long long>(nsamples, kMaxBlockReps), (bound - tables) / per_rep);
+    char what[64];
+    snprintf(what, sizeof what, "the bin table of %d axes", (int)n_axes);
+    Replicates rep(device, logl, birth, n, run_start, n_runs, nsamples, expected, bootstrap, seed);
+    MRG_OK(rep.plan_blocks(block_bytes, tables + kDefaultWeightBytes, tables, per_rep, kMaxBlockReps, what,
+                           "the weights and its histograms"));
+    const long long s_blk = rep.s_blk;
     const char* env = std::getenv("RVLL_MARGINAL_WAVE_REDUCE");
     const bool wave_reduce = env && env[0] == '1';        // off: it lost 12 - 14 % on 51 Peg (profiles/marginals_probe.txt)
     const int ngroups = (int)plan.group_first.size() - 1;
     const size_t lds = sizeof(unsigned long long) * (size_t)plan.max_entries;
     const size_t n_edges = (size_t)plan.axis_start[n_axes];
-    int status = RVLL_OK;
-    int prev_device = -1;
-    double *d_logz = nullptr, *d_info = nullptr, *d_w = nullptr, *d_vin = nullptr, *d_edges = nullptr, *d_state = nullptr;
-    double *d_mass = nullptr, *d_outside = nullptr;
+    double *d_vin = nullptr, *d_edges = nullptr, *d_state = nullptr, *d_mass = nullptr, *d_outside = nullptr;
     unsigned long long *d_h = nullptr, *d_msum = nullptr, *d_counts = nullptr;
     uint16_t* d_bins = nullptr;
     int32_t *d_axis_col = nullptr, *d_group_first = nullptr;
     long long* d_axis_start = nullptr;
     Panel* d_panels = nullptr;
-    MergeSetup su;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    double setup_ms = 0., weights_ms = 0., reduce_ms = 0.;
-    int launches = 0, blocks = 0;
-    const size_t shmem = bootstrap ? sizeof(int32_t) * (size_t)n_runs : 0;
     const size_t nc = (size_t)n * (size_t)ncols;
     std::vector<double> state((size_t)(5 * nbins), 0.0);
     std::vector<long long> cnt((size_t)nentries);
@@ -295,30 +287,22 @@ int run_marginal(int32_t device, const double* logl, const double* birth, int64_
         state[(size_t)(4 * nbins + b)] = -INFINITY;
     }
 
-    MRG_TRY(su.query(n));
-    MRG_TRY(hipGetDevice(&prev_device));
-    if (device >= 0) MRG_TRY(hipSetDevice(device));
-    MRG_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-    for (auto& e : ev) MRG_TRY(hipEventCreate(&e));
-    // every device block before the first launch: running out of memory fails the call before any work
-    MRG_TRY(su.alloc(n, n_runs));
-    MRG_TRY(hipMalloc(&d_logz, sizeof(double) * (size_t)nsamples));
-    MRG_TRY(hipMalloc(&d_info, sizeof(double) * (size_t)nsamples));
-    MRG_TRY(hipMalloc(&d_edges, sizeof(double) * n_edges));
-    MRG_TRY(hipMalloc(&d_axis_col, sizeof(int32_t) * (size_t)n_axes));
-    MRG_TRY(hipMalloc(&d_axis_start, sizeof(long long) * (size_t)(n_axes + 1)));
-    MRG_TRY(hipMalloc(&d_panels, sizeof(Panel) * (size_t)n_panels));
-    MRG_TRY(hipMalloc(&d_group_first, sizeof(int32_t) * (size_t)(ngroups + 1)));
-    MRG_TRY(hipMalloc(&d_state, sizeof(double) * state.size()));
-    MRG_TRY(hipMalloc(&d_counts, sizeof(unsigned long long) * (size_t)nentries));
-    MRG_TRY(hipMalloc(&d_msum, sizeof(unsigned long long) * (size_t)s_blk));
-    MRG_TRY(hipMalloc(&d_h, sizeof(unsigned long long) * (size_t)(s_blk * nentries)));
-    if (mass) MRG_TRY(hipMalloc(&d_mass, sizeof(double) * (size_t)(s_blk * nbins)));
-    if (outside) MRG_TRY(hipMalloc(&d_outside, sizeof(double) * (size_t)(s_blk * n_panels)));
-    MRG_TRY(hipMalloc(&d_bins, sizeof(uint16_t) * (size_t)n * (size_t)n_axes));
-    MRG_TRY(hipMalloc(&d_w, sizeof(double) * (size_t)(s_blk * n)));
-    MRG_TRY(hipMalloc(&d_vin, sizeof(double) * nc));       // the input's copy: freed once it is binned
-    MRG_TRY(su.upload(logl, birth, run_start, n, n_runs, stream));
+    MRG_OK(rep.begin());
+    MergeSetup& su = rep.su;
+    const hipStream_t stream = rep.stream;
+    MRG_TRY(rep.alloc(d_edges, n_edges));
+    MRG_TRY(rep.alloc(d_axis_col, (size_t)n_axes));
+    MRG_TRY(rep.alloc(d_axis_start, (size_t)(n_axes + 1)));
+    MRG_TRY(rep.alloc(d_panels, (size_t)n_panels));
+    MRG_TRY(rep.alloc(d_group_first, (size_t)(ngroups + 1)));
+    MRG_TRY(rep.alloc(d_state, state.size()));
+    MRG_TRY(rep.alloc(d_counts, (size_t)nentries));
+    MRG_TRY(rep.alloc(d_msum, (size_t)s_blk));
+    MRG_TRY(rep.alloc(d_h, (size_t)(s_blk * nentries)));
+    if (mass) MRG_TRY(rep.alloc(d_mass, (size_t)(s_blk * nbins)));
+    if (outside) MRG_TRY(rep.alloc(d_outside, (size_t)(s_blk * n_panels)));
+    MRG_TRY(rep.alloc(d_bins, (size_t)n * (size_t)n_axes));
+    MRG_TRY(rep.alloc(d_vin, nc));                         // the input's copy: freed once it is binned
     MRG_TRY(hipMemcpyAsync(d_vin, values, sizeof(double) * nc, hipMemcpyHostToDevice, stream));
     MRG_TRY(hipMemcpyAsync(d_edges, edges, sizeof(double) * n_edges, hipMemcpyHostToDevice, stream));
     MRG_TRY(hipMemcpyAsync(d_axis_col, axis_col, sizeof(int32_t) * (size_t)n_axes, hipMemcpyHostToDevice, stream));
@@ -330,67 +314,50 @@ int run_marginal(int32_t device, const double* logl, const double* birth, int64_
     MRG_TRY(hipMemcpyAsync(d_state, state.data(), sizeof(double) * state.size(), hipMemcpyHostToDevice, stream));
     MRG_TRY(hipMemsetAsync(d_counts, 0, sizeof(unsigned long long) * (size_t)nentries, stream));
 
-    MRG_TRY(hipEventRecord(ev[0], stream));
-    MRG_TRY(su.launch(n, n_runs, stream));
-    hipLaunchKernelGGL(bin_kernel, dim3(blocks_for(n * (long long)n_axes, kThreads)), dim3(kThreads), 0, stream, d_vin, su.order,
-                       (long long)n, (int)ncols, (int)n_axes, d_edges, d_axis_col, d_axis_start, d_bins);
-    MRG_TRY(hipGetLastError());
-    {
+    MRG_OK(rep.setup([&]() -> hipError_t {
+        hipLaunchKernelGGL(bin_kernel, dim3(blocks_for(n * (long long)n_axes, kThreads)), dim3(kThreads), 0, stream, d_vin, su.order,
+                           (long long)n, (int)ncols, (int)n_axes, d_edges, d_axis_col, d_axis_start, d_bins);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
         const long long chunk = chunk_rows_for(n, ngroups, 1);
         const long long chunks = (n + chunk - 1) / chunk;
-        MRG_TRY(launch_hist<true>(wave_reduce, dim3((unsigned)(chunks * ngroups), 1), lds, stream, nullptr, d_bins, (long long)n,
-                                  d_panels, d_group_first, ngroups, chunk, nbins, nentries, d_counts));
-    }
-    launches += 6;
-    MRG_TRY(hipEventRecord(ev[1], stream));
+        rep.launches += 2;
+        return launch_hist<true>(wave_reduce, dim3((unsigned)(chunks * ngroups), 1), lds, stream, nullptr, d_bins, (long long)n,
+                                 d_panels, d_group_first, ngroups, chunk, nbins, nentries, d_counts);
+    }));
+    // the counts come down behind the setup's clock; the first block's synchronise covers them
     MRG_TRY(hipMemcpyAsync(cnt.data(), d_counts, sizeof(long long) * (size_t)nentries, hipMemcpyDeviceToHost, stream));
-    MRG_TRY(hipStreamSynchronize(stream));
-    {
-        float ms = 0.f;
-        MRG_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
-        setup_ms += ms;
-    }
-    MRG_TRY(hipFree(d_vin));
-    d_vin = nullptr;
-    for (long long s0 = 0; s0 < nsamples; s0 += s_blk) {
-        const long long sb = std::min<long long>(s_blk, nsamples - s0);
+    MRG_TRY(rep.free_now(d_vin));
+    MRG_OK(rep.run_blocks([&](long long, long long sb, double*, hipStream_t) -> hipError_t {
+        const hipError_t e = hipMemsetAsync(d_msum, 0, sizeof(unsigned long long) * (size_t)sb, stream);
+        if (e != hipSuccess) return e;
+        return hipMemsetAsync(d_h, 0, sizeof(unsigned long long) * (size_t)(sb * nentries), stream);
+    }, [&](long long, long long sb, double* d_w, hipStream_t) -> hipError_t {
         const long long chunk = chunk_rows_for(n, ngroups, sb);
         const long long chunks = (n + chunk - 1) / chunk;
-        MRG_TRY(hipMemsetAsync(d_msum, 0, sizeof(unsigned long long) * (size_t)sb, stream));
-        MRG_TRY(hipMemsetAsync(d_h, 0, sizeof(unsigned long long) * (size_t)(sb * nentries), stream));
-        MRG_TRY(hipEventRecord(ev[0], stream));
-        hipLaunchKernelGGL(replicate_kernel, dim3((unsigned)sb), dim3(kThreads), shmem, stream, su.ev, su.L, su.rho, (long long)n,
-                           (int)n_runs, (int)s0, (u64)seed, expected, bootstrap, d_logz, d_info, d_w);
-        MRG_TRY(hipGetLastError());
-        MRG_TRY(hipEventRecord(ev[1], stream));
         hipLaunchKernelGGL(fixed_kernel, dim3((unsigned)std::min<long long>(blocks_for(n, kThreads), 1024), (unsigned)sb),
                            dim3(kThreads), 0, stream, d_w, (long long)n, d_msum);
-        MRG_TRY(hipGetLastError());
-        MRG_TRY(launch_hist<false>(wave_reduce, dim3((unsigned)(chunks * ngroups), (unsigned)sb), lds, stream,
-                                   reinterpret_cast<const long long*>(d_w), d_bins, (long long)n, d_panels, d_group_first, ngroups,
-                                   chunk, nbins, nentries, d_h));
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        e = launch_hist<false>(wave_reduce, dim3((unsigned)(chunks * ngroups), (unsigned)sb), lds, stream,
+                               reinterpret_cast<const long long*>(d_w), d_bins, (long long)n, d_panels, d_group_first, ngroups,
+                               chunk, nbins, nentries, d_h);
+        if (e != hipSuccess) return e;
         hipLaunchKernelGGL(stats_kernel, dim3(blocks_for(nentries, kThreads)), dim3(kThreads), 0, stream, d_h, d_msum, nbins,
                            nentries, (int)sb, d_state, d_mass, d_outside);
-        MRG_TRY(hipGetLastError());
-        MRG_TRY(hipEventRecord(ev[2], stream));
+        rep.launches += 3;
+        return hipGetLastError();
+    }, [&](long long s0, long long sb, double*, hipStream_t) -> hipError_t {
+        hipError_t e = hipSuccess;
         if (mass)
-            MRG_TRY(hipMemcpyAsync(mass + s0 * nbins, d_mass, sizeof(double) * (size_t)(sb * nbins), hipMemcpyDeviceToHost, stream));
-        if (outside)
-            MRG_TRY(hipMemcpyAsync(outside + s0 * n_panels, d_outside, sizeof(double) * (size_t)(sb * n_panels),
-                                   hipMemcpyDeviceToHost, stream));
-        launches += 4;
-        ++blocks;
-        MRG_TRY(hipStreamSynchronize(stream));
-        float ms = 0.f;
-        MRG_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
-        weights_ms += ms;
-        MRG_TRY(hipEventElapsedTime(&ms, ev[1], ev[2]));
-        reduce_ms += ms;
-    }
-    MRG_TRY(hipMemcpyAsync(logz, d_logz, sizeof(double) * (size_t)nsamples, hipMemcpyDeviceToHost, stream));
-    MRG_TRY(hipMemcpyAsync(info, d_info, sizeof(double) * (size_t)nsamples, hipMemcpyDeviceToHost, stream));
+            e = hipMemcpyAsync(mass + s0 * nbins, d_mass, sizeof(double) * (size_t)(sb * nbins), hipMemcpyDeviceToHost, stream);
+        if (outside && e == hipSuccess)
+            e = hipMemcpyAsync(outside + s0 * n_panels, d_outside, sizeof(double) * (size_t)(sb * n_panels), hipMemcpyDeviceToHost,
+                               stream);
+        return e;
+    }));
     MRG_TRY(hipMemcpyAsync(state.data(), d_state, sizeof(double) * state.size(), hipMemcpyDeviceToHost, stream));
-    MRG_TRY(hipStreamSynchronize(stream));
+    MRG_OK(rep.finish(logz, info));
     for (long long b = 0; b < nbins; ++b) {
         const double c = state[(size_t)b];
         const bool any = c > 0.0;
@@ -401,31 +368,13 @@ int run_marginal(int32_t device, const double* logl, const double* birth, int64_
         counts[b] = cnt[(size_t)b];
     }
     for (int t = 0; t < n_panels; ++t) outside_count[t] = cnt[(size_t)(nbins + t)];
+    rep.report(timing);
     if (timing) {
-        timing->kernel_ms = setup_ms + weights_ms + reduce_ms;
-        timing->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
-        timing->setup_ms = setup_ms;
-        timing->weights_ms = weights_ms;
-        timing->reduce_ms = reduce_ms;
-        timing->rows = n;
-        timing->elements = n * (long long)nsamples;
         timing->bins = nbins;
-        timing->launches = launches;
         timing->threads = kHistThreads;
-        timing->blocks = blocks;
         timing->groups = ngroups;
     }
-
-done:
-    su.release();
-    for (void* p : {(void*)d_logz, (void*)d_info, (void*)d_w, (void*)d_vin, (void*)d_edges, (void*)d_state, (void*)d_mass,
-                    (void*)d_outside, (void*)d_h, (void*)d_msum, (void*)d_counts, (void*)d_bins, (void*)d_axis_col,
-                    (void*)d_group_first, (void*)d_axis_start, (void*)d_panels})
-        if (p) (void)hipFree(p);
-    for (auto& e : ev) if (e) (void)hipEventDestroy(e);
-    if (stream) (void)hipStreamDestroy(stream);
-    if (prev_device >= 0 && device >= 0) (void)hipSetDevice(prev_device);
-    return status;
+    return RVLL_OK;
 }
 
 }  // namespace
@@ -438,15 +387,8 @@ extern "C" int rvll_marginal_replicates(int32_t device, const double* logl, cons
                                         int64_t* counts, int64_t* outside_count, double* stats, double* mass, double* outside,
                                         int64_t block_bytes, rvll_marginal_timing* timing)
 {
-    const int rc = check_common(logl, birth, n_rows, run_start, n_runs);
-    if (rc != RVLL_OK) return rc;
-    if (nsamples < 1) return rvll::report_error(RVLL_E_INVALID, "nsamples must be >= 1");
-    if (mode != RVLL_SHRINK_RANDOM && mode != RVLL_SHRINK_EXPECTED)
-        return rvll::report_error(RVLL_E_INVALID, "mode %d is neither RVLL_SHRINK_RANDOM nor RVLL_SHRINK_EXPECTED", mode);
-    if (bootstrap != 0 && bootstrap != 1) return rvll::report_error(RVLL_E_INVALID, "bootstrap must be 0 or 1");
-    if (bootstrap && n_runs > kMaxBootRuns)
-        return rvll::report_error(RVLL_E_INVALID, "the run bootstrap takes at most %d runs", kMaxBootRuns);
-    if (block_bytes < 0) return rvll::report_error(RVLL_E_INVALID, "negative block_bytes");
+    MRG_OK(check_common(logl, birth, n_rows, run_start, n_runs));
+    MRG_OK(check_replicate_args(nsamples, mode, bootstrap, n_runs, block_bytes));
     if (n_cols < 1 || n_cols > kMaxCols) return rvll::report_error(RVLL_E_INVALID, "n_cols must be in [1, %d]", kMaxCols);
     if (n_axes < 1 || n_axes > kMaxAxes) return rvll::report_error(RVLL_E_INVALID, "n_axes must be in [1, %d]", kMaxAxes);
     if (n_panels < 1 || n_panels > kMaxPanels)
@@ -492,10 +434,7 @@ extern "C" int rvll_marginal_replicates(int32_t device, const double* logl, cons
         plan.nbins += na * nb;
     }
     plan.group_first.push_back(n_panels);
-    for (int64_t i = 0; i < n_rows * (int64_t)n_cols; ++i)
-        if (!std::isfinite(values[i]))
-            return rvll::report_error(RVLL_E_INVALID, "row %lld, column %lld: value is not finite", (long long)(i / n_cols),
-                                      (long long)(i % n_cols));
+    MRG_OK(check_finite_values(values, n_rows, n_cols));
     if (timing) *timing = rvll_marginal_timing{0., 0., 0., 0., 0., n_rows, 0, plan.nbins, 0, kHistThreads, 0, 0};
     return run_marginal(device, logl, birth, n_rows, run_start, n_runs, values, n_cols, edges, axis_col, n_axes, plan, n_panels,
                         nsamples, mode == RVLL_SHRINK_EXPECTED ? 1 : 0, bootstrap, seed, logz, info, counts, outside_count, stats,

@@ -1,6 +1,8 @@
 // Merging finished nested-sampling runs by their birth contours on gfx950, and replicates of the merged run (simulated
 // shrinkage, optionally on top of a bootstrap of the runs).  evidence_amd/merge.py holds the numpy definition; DESIGN §4j.
-// The kernels, the setup and the argument checks described here are in rvll_merge_setup.h, which rvll_posterior.hip shares.
+// The kernels, the setup and the argument checks described here are in rvll_merge_setup.hip, with the driver of a call
+// (Replicates, declared in rvll_merge_setup.h) that the reducers of a merged run share: rvll_posterior.hip, rvll_fip_merged.hip
+// and rvll_marginal.hip.
 //
 // Once per call:
 //     keys      the log-L and the (off-contour corrected) birth of every row as order-preserving uint64 keys (rvll_keys.h),
@@ -29,6 +31,8 @@
 // LDS counts are integers, and no workgroup reads another's data — alone or inside any batch, the bits are the same.
 #include "rvll_merge_setup.h"
 
+using namespace rvll::merge;
+
 namespace {
 
 // the whole call: checks done by the caller; nsamples replicates, or (merge != 0) the merged run with its order and counts
@@ -36,89 +40,35 @@ int run_merge(int32_t device, const double* logl, const double* birth, int64_t n
               int32_t nsamples, int expected, int bootstrap, uint64_t seed, double* logz, double* info, double* logwt,
               int64_t block_bytes, int64_t* order_out, int64_t* nlive_out, rvll_merge_timing* timing)
 {
-    const auto t_start = std::chrono::steady_clock::now();
-    long long s_blk = std::min<long long>(nsamples, kMaxGroups);
-    const long long bound = block_bytes > 0 ? block_bytes : kDefaultBlockBytes;
-    if (logwt) {
-        const long long per_rep = n * (long long)sizeof(double);
-        if (per_rep > bound)
-            return rvll::report_error(RVLL_E_NOMEM, "one replicate of the weights needs %lld bytes, above the device block "
-                                      "bound of %lld", per_rep, bound);
-        s_blk = std::min<long long>(s_blk, bound / per_rep);
-    }
-    int status = RVLL_OK;
-    int prev_device = -1;
-    double *d_logz = nullptr, *d_info = nullptr, *d_w = nullptr;
-    MergeSetup su;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    double kernel_ms = 0.;
-    int launches = 0;
-    const size_t shmem = bootstrap ? sizeof(int32_t) * (size_t)n_runs : 0;
+    Replicates rep(device, logl, birth, n, run_start, n_runs, nsamples, expected, bootstrap, seed);
+    MRG_OK(rep.plan_blocks(block_bytes, kDefaultBlockBytes, 0, n * (long long)sizeof(double), kMaxGroups, nullptr, "the weights",
+                           logwt != nullptr));
     std::vector<int32_t> order32;
-
-    MRG_TRY(su.query(n));
-    MRG_TRY(hipGetDevice(&prev_device));
-    if (device >= 0) MRG_TRY(hipSetDevice(device));
-    MRG_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-    for (auto& e : ev) MRG_TRY(hipEventCreate(&e));
-    // every device block before the first launch: running out of memory fails the call before any work
-    MRG_TRY(su.alloc(n, n_runs));
-    MRG_TRY(hipMalloc(&d_logz, sizeof(double) * (size_t)nsamples));
-    MRG_TRY(hipMalloc(&d_info, sizeof(double) * (size_t)nsamples));
-    if (logwt) MRG_TRY(hipMalloc(&d_w, sizeof(double) * (size_t)(s_blk * n)));
-    MRG_TRY(su.upload(logl, birth, run_start, n, n_runs, stream));
-
-    MRG_TRY(hipEventRecord(ev[0], stream));
-    MRG_TRY(su.launch(n, n_runs, stream));
-    MRG_TRY(hipEventRecord(ev[1], stream));
-    launches += 4;
-    MRG_TRY(hipEventSynchronize(ev[1]));
-    {
-        float ms = 0.f;
-        MRG_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
-        kernel_ms += ms;
-    }
-    for (long long s0 = 0; s0 < nsamples; s0 += s_blk) {
-        const long long sb = std::min<long long>(s_blk, nsamples - s0);
-        MRG_TRY(hipEventRecord(ev[0], stream));
-        hipLaunchKernelGGL(replicate_kernel, dim3((unsigned)sb), dim3(kThreads), shmem, stream, su.ev, su.L, su.rho, (long long)n,
-                           (int)n_runs, (int)s0, (u64)seed, expected, bootstrap, d_logz, d_info, d_w);
-        MRG_TRY(hipGetLastError());
-        MRG_TRY(hipEventRecord(ev[1], stream));
-        ++launches;
-        if (d_w) MRG_TRY(hipMemcpyAsync(logwt + s0 * n, d_w, sizeof(double) * (size_t)(sb * n), hipMemcpyDeviceToHost, stream));
-        MRG_TRY(hipEventSynchronize(ev[1]));
-        float ms = 0.f;
-        MRG_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
-        kernel_ms += ms;
-    }
-    MRG_TRY(hipMemcpyAsync(logz, d_logz, sizeof(double) * (size_t)nsamples, hipMemcpyDeviceToHost, stream));
-    MRG_TRY(hipMemcpyAsync(info, d_info, sizeof(double) * (size_t)nsamples, hipMemcpyDeviceToHost, stream));
-    if (nlive_out) MRG_TRY(hipMemcpyAsync(nlive_out, su.nlive, sizeof(long long) * (size_t)n, hipMemcpyDeviceToHost, stream));
+    MRG_OK(rep.begin());
+    MRG_OK(rep.setup(nullptr));
+    Replicates::Step download;
+    if (logwt)
+        download = [&](long long s0, long long sb, double* d_w, hipStream_t stream) {
+            return hipMemcpyAsync(logwt + s0 * n, d_w, sizeof(double) * (size_t)(sb * n), hipMemcpyDeviceToHost, stream);
+        };
+    MRG_OK(rep.run_blocks(nullptr, nullptr, download));
+    if (nlive_out)
+        MRG_TRY(hipMemcpyAsync(nlive_out, rep.su.nlive, sizeof(long long) * (size_t)n, hipMemcpyDeviceToHost, rep.stream));
     if (order_out) {
         order32.resize((size_t)n);
-        MRG_TRY(hipMemcpyAsync(order32.data(), su.order, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, stream));
+        MRG_TRY(hipMemcpyAsync(order32.data(), rep.su.order, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, rep.stream));
     }
-    MRG_TRY(hipStreamSynchronize(stream));
+    MRG_OK(rep.finish(logz, info));
     if (order_out) std::copy(order32.begin(), order32.end(), order_out);
     if (timing) {
-        timing->kernel_ms = kernel_ms;
-        timing->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+        timing->kernel_ms = rep.setup_ms + rep.weights_ms;
+        timing->total_ms = rep.elapsed_ms();
         timing->rows = n;
         timing->elements = n * (long long)nsamples;
-        timing->launches = launches;
+        timing->launches = rep.launches;
         timing->threads = kThreads;
     }
-
-done:
-    su.release();
-    for (void* p : {(void*)d_logz, (void*)d_info, (void*)d_w})
-        if (p) (void)hipFree(p);
-    for (auto& e : ev) if (e) (void)hipEventDestroy(e);
-    if (stream) (void)hipStreamDestroy(stream);
-    if (prev_device >= 0 && device >= 0) (void)hipSetDevice(prev_device);
-    return status;
+    return RVLL_OK;
 }
 
 }  // namespace
@@ -127,8 +77,7 @@ extern "C" int rvll_merge_runs(int32_t device, const double* logl, const double*
                                int32_t n_runs, int64_t* order_out, int64_t* nlive_out, double* logz, double* info,
                                double* logwt_out, int64_t* n_off_contour, rvll_merge_timing* timing)
 {
-    const int rc = check_common(logl, birth, n_rows, run_start, n_runs);
-    if (rc != RVLL_OK) return rc;
+    MRG_OK(check_common(logl, birth, n_rows, run_start, n_runs));
     if (!order_out || !nlive_out || !logz || !info || !logwt_out || !n_off_contour)
         return rvll::report_error(RVLL_E_INVALID, "null argument");
     if (timing) *timing = rvll_merge_timing{0., 0., n_rows, n_rows, 0, kThreads};
@@ -144,15 +93,8 @@ extern "C" int rvll_merge_replicates(int32_t device, const double* logl, const d
                                      uint64_t seed, double* logz, double* info, double* logwt, int64_t block_bytes,
                                      rvll_merge_timing* timing)
 {
-    const int rc = check_common(logl, birth, n_rows, run_start, n_runs);
-    if (rc != RVLL_OK) return rc;
-    if (nsamples < 1) return rvll::report_error(RVLL_E_INVALID, "nsamples must be >= 1");
-    if (mode != RVLL_SHRINK_RANDOM && mode != RVLL_SHRINK_EXPECTED)
-        return rvll::report_error(RVLL_E_INVALID, "mode %d is neither RVLL_SHRINK_RANDOM nor RVLL_SHRINK_EXPECTED", mode);
-    if (bootstrap != 0 && bootstrap != 1) return rvll::report_error(RVLL_E_INVALID, "bootstrap must be 0 or 1");
-    if (bootstrap && n_runs > kMaxBootRuns)
-        return rvll::report_error(RVLL_E_INVALID, "the run bootstrap takes at most %d runs", kMaxBootRuns);
-    if (block_bytes < 0) return rvll::report_error(RVLL_E_INVALID, "negative block_bytes");
+    MRG_OK(check_common(logl, birth, n_rows, run_start, n_runs));
+    MRG_OK(check_replicate_args(nsamples, mode, bootstrap, n_runs, block_bytes));
     if (!logz || !info) return rvll::report_error(RVLL_E_INVALID, "null argument");
     if (timing) *timing = rvll_merge_timing{0., 0., n_rows, 0, 0, kThreads};
     return run_merge(device, logl, birth, n_rows, run_start, n_runs, nsamples, mode == RVLL_SHRINK_EXPECTED ? 1 : 0, bootstrap,

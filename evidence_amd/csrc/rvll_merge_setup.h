@@ -1,15 +1,18 @@
-// What rvll_merge.hip and rvll_posterior.hip share: the setup of a merge by birth contours (keys, two radix sorts, placement and
-// the event stream), the replicate kernel and the argument checks.  rvll_merge.hip's header comment describes them; DESIGN §4j.
-// Everything here sits in an anonymous namespace: each of the two translation units compiles its own copy of the same text.
+// What the merged-run entry points share (rvll_merge.hip, rvll_posterior.hip, rvll_fip_merged.hip, rvll_marginal.hip): the setup
+// of a merge by birth contours (keys, two radix sorts, placement and the event stream), the replicate kernel, the argument checks
+// and the driver of a call that reduces replicates of the merged run block by block.  rvll_merge_setup.hip defines them, once
+// for the library; rvll_merge.hip's header comment describes the kernels; DESIGN §4j.  This header declares them and holds the
+// small inline helpers that the reducers' own kernels use.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <chrono>
 #include <cmath>
 #include <cstdint>
+#include <cstdio>
 #include <algorithm>
+#include <functional>
 #include <vector>
 #include <cstring>
-#include <rocprim/rocprim.hpp>
 
 #pragma GCC visibility push(default)
 #include "rvll.h"
@@ -19,9 +22,8 @@
 
 namespace rvll {
 int report_error(int code, const char* fmt, ...);
-}
 
-namespace {
+namespace merge {
 
 constexpr int kThreads = 256;
 constexpr int kWave = 64;
@@ -29,126 +31,30 @@ constexpr int kWaves = kThreads / kWave;
 constexpr int kPer = 4;                                   // stream entries a lane holds per tile
 constexpr long long kTile = (long long)kThreads * kPer;
 constexpr int kMaxBlocks = 8192;
-constexpr long long kMaxRows = (1ll << 30) - 1;           // 2N stream positions stay below 2^31
-constexpr int kMaxBootRuns = 8192;                        // LDS multiplicities: 32 KiB
 constexpr long long kMaxGroups = 1ll << 22;               // replicates per launch (grid x * 256 threads < 2^32)
-constexpr long long kDefaultBlockBytes = 512ll << 20;     // device bound on a block of weights
-constexpr unsigned long long kSeedMul = 0xD1B54A32D192ED03ull;
-constexpr unsigned long long kBootXor = 0x5851F42D4C957F2Dull;
+constexpr long long kDefaultBlockBytes = 512ll << 20;     // rvll_merge_replicates: device bound on a block of weights
+// The default block of weights of the reducers.  A block holds bound / (8 N) replicates and the replicate kernel runs one workgroup a
+// replicate, so a small block leaves most of the device idle: at 2.6e6 rows, 512 MiB (24 replicates) took 2.8 s for the weights of
+// 1000 replicates and 8 GiB 0.24 s (profiles/posterior_probe.txt).  Only min(nsamples, bound / (8 N)) replicates are allocated.
+constexpr long long kDefaultWeightBytes = 8ll << 30;
 
 typedef unsigned long long u64;
 
-#define MRG_TRY(expr)                                                                          \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess) {                                                                \
-            status = rvll::report_error(e_ == hipErrorOutOfMemory ? RVLL_E_NOMEM : RVLL_E_HIP, \
-                                        "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
-                                        __FILE__, __LINE__);                                   \
-            goto done;                                                                         \
-        }                                                                                      \
+// a failed HIP call ends the entry point: RVLL_E_NOMEM or RVLL_E_HIP with the call's text
+int report_hip(hipError_t e, const char* expr, const char* file, int line);
+
+#define MRG_TRY(expr)                                                                                   \
+    do {                                                                                                \
+        hipError_t e_ = (expr);                                                                         \
+        if (e_ != hipSuccess) return rvll::merge::report_hip(e_, #expr, __FILE__, __LINE__);            \
     } while (0)
 
-int blocks_for(long long total, int per_block)
+#define MRG_OK(expr) do { const int rc_ = (expr); if (rc_ != RVLL_OK) return rc_; } while (0)
+
+inline int blocks_for(long long total, int per_block)
 {
     const long long b = (total + per_block - 1) / per_block;
     return (int)(b < 1 ? 1 : b > kMaxBlocks ? kMaxBlocks : b);
-}
-
-// keys of every row, its index and its run (the last r with run_start[r] <= g)
-__global__ __launch_bounds__(kThreads)
-void keys_kernel(const double* __restrict__ logl, const double* __restrict__ birth, long long n, const long long* __restrict__ rs,
-                 int nruns, u64* __restrict__ kl, u64* __restrict__ kb, int32_t* __restrict__ idx, int32_t* __restrict__ run)
-{
-    for (long long g = (long long)blockIdx.x * kThreads + threadIdx.x; g < n; g += (long long)gridDim.x * kThreads) {
-        const double l = logl[g], b = birth[g];
-        kl[g] = rvll::key_of(l);
-        kb[g] = rvll::key_of(l <= b ? nextafter(l, -INFINITY) : b);
-        idx[g] = (int32_t)g;
-        int lo = 0, hi = nruns;
-        while (hi - lo > 1) {
-            const int mid = lo + ((hi - lo) >> 1);
-            if (rs[mid] <= g) lo = mid; else hi = mid;
-        }
-        run[g] = lo;
-    }
-}
-
-// first position in s[0 .. n) whose key is > v (upper) or >= v (lower)
-__device__ inline long long upper_bound(const u64* s, long long n, u64 v)
-{
-    long long lo = 0, hi = n;
-    while (lo < hi) {
-        const long long mid = lo + ((hi - lo) >> 1);
-        if (s[mid] <= v) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-__device__ inline long long lower_bound(const u64* s, long long n, u64 v)
-{
-    long long lo = 0, hi = n;
-    while (lo < hi) {
-        const long long mid = lo + ((hi - lo) >> 1);
-        if (s[mid] < v) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-// per merged row: L, rho, n (unweighted) and its death's place in the stream; per sorted birth: its place
-__global__ __launch_bounds__(kThreads)
-void place_kernel(const double* __restrict__ logl, const u64* __restrict__ sl, const int32_t* __restrict__ order,
-                  const u64* __restrict__ sb, const int32_t* __restrict__ rb, const int32_t* __restrict__ run, long long n,
-                  double* __restrict__ L, int32_t* __restrict__ rho, long long* __restrict__ nlive, int32_t* __restrict__ ev)
-{
-    for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < n; i += (long long)gridDim.x * kThreads) {
-        const int32_t g = order[i];
-        L[i] = logl[g];
-        rho[i] = run[g];
-        const long long cntb = lower_bound(sb, n, sl[i]);     // #{birth < L_i}, >= i + 1
-        nlive[i] = cntb - i;
-        ev[i + cntb] = (int32_t)i;
-        const long long dj = upper_bound(sl, n, sb[i]);       // #{deaths with L <= b_i}: the deaths before birth i
-        ev[i + dj] = -1 - rb[i];
-    }
-}
-
-// (max, sum of exp(w - max), sum of exp(w - max) * L); m = -inf: no row with weight
-struct Tri {
-    double m, s, a;
-};
-
-__device__ __forceinline__ void tri_add(Tri& t, double w, double l)
-{
-    if (!(w > -INFINITY)) return;
-    const double d = w - t.m;
-    const double x = exp(-fabs(d));
-    const bool up = d > 0.0;
-    t.s = up ? t.s * x + 1.0 : t.s + x;
-    t.a = up ? t.a * x + l : t.a + x * l;
-    t.m = up ? w : t.m;
-}
-
-__device__ __forceinline__ Tri tri_join(Tri p, Tri q)
-{
-    if (!(q.m > -INFINITY)) return p;
-    if (!(p.m > -INFINITY)) return q;
-    const double mx = fmax(p.m, q.m);
-    const double cp = exp(p.m - mx), cq = exp(q.m - mx);
-    return Tri{mx, p.s * cp + q.s * cq, p.a * cp + q.a * cq};
-}
-
-__device__ Tri tri_reduce(Tri t, Tri* sh)
-{
-    for (int off = 1; off < kWave; off <<= 1)
-        t = tri_join(t, Tri{__shfl_xor(t.m, off, kWave), __shfl_xor(t.s, off, kWave), __shfl_xor(t.a, off, kWave)});
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    if (lane == 0) sh[wave] = t;
-    __syncthreads();
-    Tri r = sh[0];
-    for (int w = 1; w < kWaves; ++w) r = tri_join(r, sh[w]);
-    __syncthreads();
-    return r;
 }
 
 // inclusive 64-lane scan
@@ -162,223 +68,124 @@ __device__ __forceinline__ T wave_scan(T v, int lane)
     return v;
 }
 
-__global__ __launch_bounds__(kThreads) void replicate_kernel(
-    const int32_t* __restrict__ ev, const double* __restrict__ L, const int32_t* __restrict__ rho, long long n, int nruns,
-    int s0, u64 seed, int expected, int bootstrap, double* __restrict__ logz, double* __restrict__ info,
-    double* __restrict__ logw_out)
+// the sum of v over the workgroup, in every thread: butterfly inside a wave, then the waves in order
+__device__ inline double block_sum(double v, double* sh)
 {
-    extern __shared__ int32_t sh_w[];                     // bootstrap: the multiplicity of every run
-    __shared__ long long sh_n[2][kWaves], sh_d[2][kWaves];
-    __shared__ double sh_x[2][kWaves];
-    __shared__ Tri sh_tri[kWaves];
-    __shared__ double sh_lnz;
-    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
-    const int s = s0 + (int)blockIdx.x;
-    const u64 seed_s = seed + (u64)s * kSeedMul;
-    const long long E = 2 * n;
-    double* wout = logw_out ? logw_out + (long long)blockIdx.x * n : nullptr;
-
-    if (bootstrap) {
-        for (int r = tid; r < nruns; r += kThreads) sh_w[r] = 0;
-        __syncthreads();
-        const u64 bseed = seed_s ^ kBootXor;
-        for (int t = tid; t < nruns; t += kThreads) {
-            const int d = (int)fmin(floor(rvll::uniform01(bseed, (u64)t) * (double)nruns), (double)(nruns - 1));
-            atomicAdd(&sh_w[d], 1);
-        }
-        __syncthreads();
-    }
-
-    Tri acc{-INFINITY, 0.0, 0.0};
-    long long carry_n = 0, carry_d = 0;
-    double carry_hi = 0.0, carry_lo = 0.0;               // logX before the tile, as a compensated pair
-    int parity = 0;
-    for (long long t0 = 0; t0 < E; t0 += kTile, parity ^= 1) {
-        const long long e0 = t0 + (long long)tid * kPer;
-        int32_t v[kPer];
-        int wt[kPer];
-        long long sn = 0, sd = 0;
-#pragma unroll
-        for (int k = 0; k < kPer; ++k) {
-            const long long e = e0 + k;
-            v[k] = e < E ? ev[e] : INT32_MIN;
-            const int r = v[k] >= 0 ? rho[v[k]] : v[k] == INT32_MIN ? -1 : -1 - v[k];
-            wt[k] = r < 0 ? 0 : bootstrap ? sh_w[r] : 1;
-            if (v[k] >= 0) { sn -= wt[k]; sd += wt[k]; } else sn += wt[k];
-        }
-        const long long in_n = wave_scan(sn, lane), in_d = wave_scan(sd, lane);
-        if (lane == kWave - 1) { sh_n[parity][wave] = in_n; sh_d[parity][wave] = in_d; }
-        __syncthreads();
-        long long bn = 0, bd = 0, tn = 0, td = 0;
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) {
-            const long long a = sh_n[parity][w], b = sh_d[parity][w];
-            if (w < wave) { bn += a; bd += b; }
-            tn += a;
-            td += b;
-        }
-        long long nl = carry_n + bn + (in_n - sn), dl = carry_d + bd + (in_d - sd);
-        double dt[kPer];
-        double xs = 0.0;
-#pragma unroll
-        for (int k = 0; k < kPer; ++k) {
-            dt[k] = 0.0;
-            if (v[k] >= 0) {
-                for (int q = 0; q < wt[k]; ++q) {
-                    const double nn = (double)(nl - q);
-                    dt[k] += expected ? -1.0 / nn : log(1.0 - rvll::uniform01(seed_s, (u64)(dl + q))) / nn;
-                }
-                nl -= wt[k];
-                dl += wt[k];
-            } else {
-                nl += wt[k];
-            }
-            xs += dt[k];
-        }
-        carry_n += tn;
-        carry_d += td;
-        const double in_x = wave_scan(xs, lane);
-        if (lane == kWave - 1) sh_x[parity][wave] = in_x;
-        __syncthreads();
-        double bx = 0.0, tx = 0.0;
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) {
-            const double a = sh_x[parity][w];
-            if (w < wave) bx += a;
-            tx += a;
-        }
-        double loc = bx + (in_x - xs);
-#pragma unroll
-        for (int k = 0; k < kPer; ++k) {
-            if (v[k] >= 0) {
-                const double l = L[v[k]];
-                const double lx = carry_hi + (carry_lo + loc);
-                const double w = wt[k] > 0 ? (l + lx) + log(-expm1(dt[k])) : -INFINITY;
-                tri_add(acc, w, l);
-                if (wout) wout[v[k]] = w;
-            }
-            loc += dt[k];
-        }
-        // two-sum of carry_hi + tx
-        const double sum = carry_hi + tx, bv = sum - carry_hi;
-        carry_lo += (carry_hi - (sum - bv)) + (tx - bv);
-        carry_hi = sum;
-    }
-    acc = tri_reduce(acc, sh_tri);
-    if (tid == 0) {
-        const bool any = acc.m > -INFINITY;
-        const double lnz = any ? acc.m + log(acc.s) : -INFINITY;
-        logz[s] = lnz;
-        info[s] = any ? acc.a / acc.s - lnz : 0.0;
-        sh_lnz = lnz;
-    }
-    if (!wout) return;
+    for (int off = 1; off < kWave; off <<= 1) v += __shfl_xor(v, off, kWave);
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    if (lane == 0) sh[wave] = v;
     __syncthreads();
-    const double lnz = sh_lnz;
-    for (long long t0 = 0; t0 < E; t0 += kTile)
-        for (int k = 0; k < kPer; ++k) {
-            const long long e = t0 + (long long)tid * kPer + k;
-            if (e < E) {
-                const int32_t i = ev[e];
-                if (i >= 0) wout[i] -= lnz;
-            }
-        }
+    double r = sh[0];
+    for (int w = 1; w < kWaves; ++w) r += sh[w];
+    __syncthreads();
+    return r;
 }
 
-int check_common(const double* logl, const double* birth, int64_t n_rows, const int64_t* run_start, int32_t n_runs)
-{
-    if (n_runs < 1) return rvll::report_error(RVLL_E_INVALID, "n_runs must be >= 1");
-    if (n_rows < 1 || n_rows > kMaxRows) return rvll::report_error(RVLL_E_INVALID, "n_rows must be in [1, %lld]", kMaxRows);
-    if (!logl || !birth || !run_start) return rvll::report_error(RVLL_E_INVALID, "null argument");
-    if (run_start[0] != 0 || run_start[n_runs] != n_rows)
-        return rvll::report_error(RVLL_E_INVALID, "run_start must run from 0 to n_rows = %lld", (long long)n_rows);
-    for (int32_t r = 0; r < n_runs; ++r)
-        if (run_start[r + 1] < run_start[r])
-            return rvll::report_error(RVLL_E_INVALID, "run_start must be non-decreasing (run %d)", (int)r);
-    for (int64_t i = 0; i < n_rows; ++i) {
-        if (!std::isfinite(logl[i])) return rvll::report_error(RVLL_E_INVALID, "row %lld: log-L is not finite", (long long)i);
-        if (std::isnan(birth[i])) return rvll::report_error(RVLL_E_INVALID, "row %lld: NaN birth", (long long)i);
-    }
-    return RVLL_OK;
-}
+int check_common(const double* logl, const double* birth, int64_t n_rows, const int64_t* run_start, int32_t n_runs);
+// what every replicate entry point asks of nsamples, mode, bootstrap and block_bytes
+int check_replicate_args(int32_t nsamples, int32_t mode, int32_t bootstrap, int32_t n_runs, int64_t block_bytes);
+int check_finite_values(const double* values, int64_t n_rows, int32_t n_cols);
+
+struct Replicates;
 
 // The device tables of one merge and the four launches that fill them (keys, two sorts, place).  After launch() the merged order
 // (order), L, rho, nlive and the event stream ev are final; kl, kb, sl, sb, run, rb and temp are scratch a caller may reuse, and
-// idx still holds 0 .. n - 1.
+// idx still holds 0 .. n - 1.  The tables belong to the call (owner) and go with it.
 struct MergeSetup {
     double *logl = nullptr, *birth = nullptr, *L = nullptr;
     u64 *kl = nullptr, *kb = nullptr, *sl = nullptr, *sb = nullptr;
     int32_t *idx = nullptr, *order = nullptr, *run = nullptr, *rb = nullptr, *rho = nullptr, *ev = nullptr;
     long long *rs = nullptr, *nlive = nullptr;
-    void* temp = nullptr;
+    char* temp = nullptr;
     size_t temp_bytes = 0;
 
-    hipError_t query(long long n)
-    {
-        size_t b1 = 0;
-        u64* k = nullptr;
-        int32_t* o = nullptr;
-        const hipError_t e = rocprim::radix_sort_pairs(nullptr, b1, k, k, o, o, (unsigned int)n, 0, 64, (hipStream_t) nullptr);
-        temp_bytes = std::max<size_t>(b1, 1);
-        return e;
-    }
-
-    hipError_t alloc(long long n, int n_runs)
-    {
-        hipError_t e;
-#define MRG_SETUP_ALLOC(p, bytes) if ((e = hipMalloc(&p, (bytes))) != hipSuccess) return e
-        MRG_SETUP_ALLOC(logl, sizeof(double) * (size_t)n);
-        MRG_SETUP_ALLOC(birth, sizeof(double) * (size_t)n);
-        MRG_SETUP_ALLOC(L, sizeof(double) * (size_t)n);
-        MRG_SETUP_ALLOC(kl, sizeof(u64) * (size_t)n);
-        MRG_SETUP_ALLOC(kb, sizeof(u64) * (size_t)n);
-        MRG_SETUP_ALLOC(sl, sizeof(u64) * (size_t)n);
-        MRG_SETUP_ALLOC(sb, sizeof(u64) * (size_t)n);
-        MRG_SETUP_ALLOC(idx, sizeof(int32_t) * (size_t)n);
-        MRG_SETUP_ALLOC(order, sizeof(int32_t) * (size_t)n);
-        MRG_SETUP_ALLOC(run, sizeof(int32_t) * (size_t)n);
-        MRG_SETUP_ALLOC(rb, sizeof(int32_t) * (size_t)n);
-        MRG_SETUP_ALLOC(rho, sizeof(int32_t) * (size_t)n);
-        MRG_SETUP_ALLOC(ev, sizeof(int32_t) * (size_t)(2 * n));
-        MRG_SETUP_ALLOC(nlive, sizeof(long long) * (size_t)n);
-        MRG_SETUP_ALLOC(rs, sizeof(long long) * (size_t)(n_runs + 1));
-        MRG_SETUP_ALLOC(temp, temp_bytes);
-#undef MRG_SETUP_ALLOC
-        return hipSuccess;
-    }
-
+    hipError_t query(long long n);
+    hipError_t alloc(Replicates& owner, long long n, int n_runs);
     hipError_t upload(const double* h_logl, const double* h_birth, const int64_t* run_start, long long n, int n_runs,
-                      hipStream_t stream)
-    {
-        hipError_t e = hipMemcpyAsync(logl, h_logl, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, stream);
-        if (e != hipSuccess) return e;
-        e = hipMemcpyAsync(birth, h_birth, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, stream);
-        if (e != hipSuccess) return e;
-        return hipMemcpyAsync(rs, run_start, sizeof(long long) * (size_t)(n_runs + 1), hipMemcpyHostToDevice, stream);
-    }
-
+                      hipStream_t stream);
     // four launches
-    hipError_t launch(long long n, int n_runs, hipStream_t stream)
-    {
-        hipLaunchKernelGGL(keys_kernel, dim3(blocks_for(n, kThreads)), dim3(kThreads), 0, stream, logl, birth, n, rs, n_runs, kl, kb,
-                           idx, run);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        e = rocprim::radix_sort_pairs(temp, temp_bytes, kl, sl, idx, order, (unsigned int)n, 0, 64, stream);
-        if (e != hipSuccess) return e;
-        e = rocprim::radix_sort_pairs(temp, temp_bytes, kb, sb, run, rb, (unsigned int)n, 0, 64, stream);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(place_kernel, dim3(blocks_for(n, kThreads)), dim3(kThreads), 0, stream, logl, sl, order, sb, rb, run, n, L,
-                           rho, nlive, ev);
-        return hipGetLastError();
-    }
-
-    void release()
-    {
-        for (void* p : {(void*)logl, (void*)birth, (void*)L, (void*)kl, (void*)kb, (void*)sl, (void*)sb, (void*)idx, (void*)order,
-                        (void*)run, (void*)rb, (void*)rho, (void*)ev, (void*)rs, (void*)nlive, temp})
-            if (p) (void)hipFree(p);
-    }
+    hipError_t launch(long long n, int n_runs, hipStream_t stream);
+    // one launch sequence: the stable rocPRIM radix sort of n 64-bit keys carrying int32 values, in temp
+    hipError_t sort(u64* keys_in, u64* keys_out, int32_t* vals_in, int32_t* vals_out, long long n, hipStream_t stream);
 };
 
-}  // namespace
+// One call that reduces replicates of a merged run: the device, the stream and the events, every device buffer, the setup, the
+// blocks of replicates and their timing.  A caller (checks done) goes through plan_blocks, begin, its own alloc and uploads on
+// `stream`, setup, free_now of what only the setup needed, run_blocks and finish, and returns at the first status that is not
+// RVLL_OK: the destructor frees every buffer, destroys the stream and the events and restores the device.
+struct Replicates {
+    // a step of a block of sb replicates from s0 whose weights are in d_w; it queues on stream
+    typedef std::function<hipError_t(long long s0, long long sb, double* d_w, hipStream_t stream)> Step;
+
+    Replicates(int32_t device, const double* logl, const double* birth, long long n, const int64_t* run_start, int n_runs,
+               int nsamples, int expected, int bootstrap, uint64_t seed);
+    ~Replicates();
+    Replicates(const Replicates&) = delete;
+
+    // s_blk = min(nsamples, max_reps, (bound - tables) / per_rep) with bound = block_bytes or, when that is 0, default_bound.
+    // RVLL_E_NOMEM when tables + per_rep is above the bound: "<tables_name> (.. bytes) and one replicate of <rep_name> (.. bytes)
+    // are above ..", or without tables_name "one replicate of <rep_name> needs .. bytes, above ..".  weights = false: no block of
+    // weights and no bound.
+    int plan_blocks(int64_t block_bytes, long long default_bound, long long tables, long long per_rep, long long max_reps,
+                    const char* tables_name, const char* rep_name, bool weights = true);
+    int begin();
+    // device memory that lives until the call ends, or until free_now
+    template <class T>
+    hipError_t alloc(T*& p, size_t count)
+    {
+        return alloc_bytes(reinterpret_cast<void**>(&p), sizeof(T) * count);
+    }
+    template <class T>
+    hipError_t free_now(T*& p)
+    {
+        return free_bytes(reinterpret_cast<void**>(&p));
+    }
+    // event 0, the merge's launches, own(), event 1, synchronise: setup_ms
+    int setup(const std::function<hipError_t()>& own);
+    // per block: before (untimed), event 0, replicate_kernel, event 1, reduce, event 2, after (untimed: the block's downloads),
+    // one synchronise: weights_ms and reduce_ms.  An empty step is skipped.
+    int run_blocks(const Step& before, const Step& reduce, const Step& after);
+    int finish(double* logz, double* info);
+    double elapsed_ms() const;                            // since the constructor: total_ms
+    // the fields that the timing structs with the three phases share; what else a struct has is its entry point's
+    template <class T>
+    void report(T* t) const
+    {
+        if (!t) return;
+        t->kernel_ms = setup_ms + weights_ms + reduce_ms;
+        t->total_ms = elapsed_ms();
+        t->setup_ms = setup_ms;
+        t->weights_ms = weights_ms;
+        t->reduce_ms = reduce_ms;
+        t->rows = n;
+        t->elements = n * (long long)nsamples;
+        t->launches = launches;
+        t->blocks = blocks;
+    }
+
+    MergeSetup su;
+    hipStream_t stream = nullptr;
+    double *d_logz = nullptr, *d_info = nullptr, *d_w = nullptr;
+    long long s_blk = 0;
+    double setup_ms = 0., weights_ms = 0., reduce_ms = 0.;
+    int launches = 0, blocks = 0;                         // the driver counts its own launches, the caller adds its own
+
+private:
+    hipError_t alloc_bytes(void** p, size_t bytes);
+    hipError_t free_bytes(void** p);
+
+    const int32_t device;
+    const double *logl, *birth;
+    const long long n;
+    const int64_t* run_start;
+    const int n_runs, nsamples, expected, bootstrap;
+    const uint64_t seed;
+    const std::chrono::steady_clock::time_point t_start;
+    int prev_device = -1;
+    bool weights = true;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    std::vector<void*> owned;
+};
+
+}  // namespace merge
+}  // namespace rvll

@@ -1,10 +1,10 @@
 // Posterior summaries of the replicates of a merged run on gfx950: per replicate and per column of `values` the weighted mean,
 // the weighted standard deviation about that mean and weighted quantiles (the inverted weighted CDF), reduced on the device
-// from the weights that the replicate kernel of rvll_merge_setup.h writes.  No weight leaves the device.
+// from the weights that the replicate kernel of rvll_merge_setup.hip writes.  No weight leaves the device.
 // evidence_amd/posterior.py holds the numpy definition; DESIGN §4k.
 //
 // Once per call:
-//     setup     the merge's own (rvll_merge_setup.h: keys, two sorts, place) -> the merged order and the event stream
+//     setup     the merge's own (rvll_merge_setup.hip: keys, two sorts, place) -> the merged order and the event stream
 //     permute   values [N, C] in input row order -> column-major [C, N] in merged order
 //     columns   per column one rocPRIM radix sort of key_of(x) carrying the merged position -> perm_c, the column's rows by
 //               value (stable: ties keep the merged order; the quantile does not depend on it)
@@ -25,17 +25,16 @@
 //
 // A (replicate, column) workgroup reads its replicate's slot and the per-call tables only, so its results depend on the input,
 // the seed and the replicate's index: the same bits alone, in any batch, from call to call.
+// The call itself (device, stream, buffers, blocks of replicates, timing) is rvll_merge_setup.h's Replicates.
 #include "rvll_merge_setup.h"
 #include <climits>
+
+using namespace rvll::merge;
 
 namespace {
 
 constexpr int kMaxCols = 64;
 constexpr int kMaxQ = 16;
-// The default block of weights.  A block holds bound / (8 N) replicates and the replicate kernel runs one workgroup a replicate, so a
-// small block leaves most of the device idle: at 2.6e6 rows, 512 MiB (24 replicates) took 2.8 s for the weights of 1000 replicates
-// and 8 GiB 0.24 s (profiles/posterior_probe.txt).  Only min(nsamples, bound / (8 N)) replicates are allocated.
-constexpr long long kDefaultWeightBytes = 8ll << 30;
 constexpr int kAcc = 4;                                   // accumulators a lane keeps in passes A and B
 
 __global__ __launch_bounds__(kThreads)
@@ -60,19 +59,6 @@ void exp_kernel(double* __restrict__ w, long long total)
 {
     for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < total; i += (long long)gridDim.x * kThreads)
         w[i] = exp(w[i]);
-}
-
-// the sum of v over the workgroup, in every thread: butterfly inside a wave, then the waves in order
-__device__ double block_sum(double v, double* sh)
-{
-    for (int off = 1; off < kWave; off <<= 1) v += __shfl_xor(v, off, kWave);
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    if (lane == 0) sh[wave] = v;
-    __syncthreads();
-    double r = sh[0];
-    for (int w = 1; w < kWaves; ++w) r += sh[w];
-    __syncthreads();
-    return r;
 }
 
 template <bool kMin>
@@ -216,122 +202,64 @@ int run_posterior(int32_t device, const double* logl, const double* birth, int64
                   int bootstrap, uint64_t seed, double* logz, double* info, double* mean, double* sd, double* quant,
                   int64_t block_bytes, rvll_posterior_timing* timing)
 {
-    const auto t_start = std::chrono::steady_clock::now();
     const long long per_rep = n * (long long)sizeof(double);
     const long long tables = n * (long long)ncols * (long long)(sizeof(double) + sizeof(int32_t));
-    const long long bound = block_bytes > 0 ? block_bytes : tables + kDefaultWeightBytes;
-    if (tables + per_rep > bound)
-        return rvll::report_error(RVLL_E_NOMEM, "the tables of %d columns (%lld bytes) and one replicate of the weights (%lld "
-                                  "bytes) are above the device block bound of %lld", (int)ncols, tables, per_rep, bound);
-    const long long s_blk = std::min<long long>(std::min<long long>(nsamples, kMaxGroups), (bound - tables) / per_rep);
-    int status = RVLL_OK;
-    int prev_device = -1;
-    double *d_logz = nullptr, *d_info = nullptr, *d_w = nullptr, *d_vin = nullptr, *d_vals = nullptr, *d_q = nullptr;
-    double *d_mean = nullptr, *d_sd = nullptr, *d_quant = nullptr;
+    char what[64];
+    snprintf(what, sizeof what, "the tables of %d columns", (int)ncols);
+    Replicates rep(device, logl, birth, n, run_start, n_runs, nsamples, expected, bootstrap, seed);
+    MRG_OK(rep.plan_blocks(block_bytes, tables + kDefaultWeightBytes, tables, per_rep, kMaxGroups, what, "the weights"));
+    double *d_vin = nullptr, *d_vals = nullptr, *d_q = nullptr, *d_mean = nullptr, *d_sd = nullptr, *d_quant = nullptr;
     int32_t* d_perm = nullptr;
-    MergeSetup su;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    double setup_ms = 0., weights_ms = 0., reduce_ms = 0.;
-    int launches = 0, blocks = 0;
-    const size_t shmem = bootstrap ? sizeof(int32_t) * (size_t)n_runs : 0;
     const size_t nc = (size_t)n * (size_t)ncols;
+    const size_t sc = (size_t)nsamples * (size_t)ncols;
 
-    MRG_TRY(su.query(n));
-    MRG_TRY(hipGetDevice(&prev_device));
-    if (device >= 0) MRG_TRY(hipSetDevice(device));
-    MRG_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-    for (auto& e : ev) MRG_TRY(hipEventCreate(&e));
-    // every device block before the first launch: running out of memory fails the call before any work
-    MRG_TRY(su.alloc(n, n_runs));
-    MRG_TRY(hipMalloc(&d_logz, sizeof(double) * (size_t)nsamples));
-    MRG_TRY(hipMalloc(&d_info, sizeof(double) * (size_t)nsamples));
-    MRG_TRY(hipMalloc(&d_mean, sizeof(double) * (size_t)nsamples * ncols));
-    MRG_TRY(hipMalloc(&d_sd, sizeof(double) * (size_t)nsamples * ncols));
-    MRG_TRY(hipMalloc(&d_quant, sizeof(double) * (size_t)nsamples * ncols * nq));
-    MRG_TRY(hipMalloc(&d_q, sizeof(double) * (size_t)nq));
-    MRG_TRY(hipMalloc(&d_vals, sizeof(double) * nc));
-    MRG_TRY(hipMalloc(&d_perm, sizeof(int32_t) * nc));
-    MRG_TRY(hipMalloc(&d_w, sizeof(double) * (size_t)(s_blk * n)));
-    MRG_TRY(hipMalloc(&d_vin, sizeof(double) * nc));       // the input's copy: freed once it is permuted
-    MRG_TRY(su.upload(logl, birth, run_start, n, n_runs, stream));
+    MRG_OK(rep.begin());
+    MergeSetup& su = rep.su;
+    const hipStream_t stream = rep.stream;
+    MRG_TRY(rep.alloc(d_mean, sc));
+    MRG_TRY(rep.alloc(d_sd, sc));
+    MRG_TRY(rep.alloc(d_quant, sc * nq));
+    MRG_TRY(rep.alloc(d_q, (size_t)nq));
+    MRG_TRY(rep.alloc(d_vals, nc));
+    MRG_TRY(rep.alloc(d_perm, nc));
+    MRG_TRY(rep.alloc(d_vin, nc));                         // the input's copy: freed once it is permuted
     MRG_TRY(hipMemcpyAsync(d_vin, values, sizeof(double) * nc, hipMemcpyHostToDevice, stream));
     MRG_TRY(hipMemcpyAsync(d_q, quantiles, sizeof(double) * (size_t)nq, hipMemcpyHostToDevice, stream));
 
-    MRG_TRY(hipEventRecord(ev[0], stream));
-    MRG_TRY(su.launch(n, n_runs, stream));
-    hipLaunchKernelGGL(permute_kernel, dim3(blocks_for(n, kThreads)), dim3(kThreads), 0, stream, d_vin, su.order, (long long)n,
-                       (int)ncols, d_vals);
-    MRG_TRY(hipGetLastError());
-    launches += 5;
-    for (int c = 0; c < ncols; ++c) {                     // su.kl / su.kb are free after the setup; su.idx holds 0 .. n - 1
-        hipLaunchKernelGGL(colkeys_kernel, dim3(blocks_for(n, kThreads)), dim3(kThreads), 0, stream, d_vals + (size_t)c * n,
-                           (long long)n, su.kl);
-        MRG_TRY(hipGetLastError());
-        MRG_TRY(rocprim::radix_sort_pairs(su.temp, su.temp_bytes, su.kl, su.kb, su.idx, d_perm + (size_t)c * n, (unsigned int)n, 0,
-                                          64, stream));
-        launches += 2;
-    }
-    MRG_TRY(hipEventRecord(ev[1], stream));
-    MRG_TRY(hipEventSynchronize(ev[1]));
-    {
-        float ms = 0.f;
-        MRG_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
-        setup_ms += ms;
-    }
-    MRG_TRY(hipFree(d_vin));
-    d_vin = nullptr;
-    for (long long s0 = 0; s0 < nsamples; s0 += s_blk) {
-        const long long sb = std::min<long long>(s_blk, nsamples - s0);
-        MRG_TRY(hipEventRecord(ev[0], stream));
-        hipLaunchKernelGGL(replicate_kernel, dim3((unsigned)sb), dim3(kThreads), shmem, stream, su.ev, su.L, su.rho, (long long)n,
-                           (int)n_runs, (int)s0, (u64)seed, expected, bootstrap, d_logz, d_info, d_w);
-        MRG_TRY(hipGetLastError());
-        MRG_TRY(hipEventRecord(ev[1], stream));
+    MRG_OK(rep.setup([&]() -> hipError_t {
+        hipLaunchKernelGGL(permute_kernel, dim3(blocks_for(n, kThreads)), dim3(kThreads), 0, stream, d_vin, su.order, (long long)n,
+                           (int)ncols, d_vals);
+        hipError_t e = hipGetLastError();
+        ++rep.launches;
+        for (int c = 0; c < ncols && e == hipSuccess; ++c) {   // su.kl / su.kb are free after the setup; su.idx holds 0 .. n - 1
+            hipLaunchKernelGGL(colkeys_kernel, dim3(blocks_for(n, kThreads)), dim3(kThreads), 0, stream, d_vals + (size_t)c * n,
+                               (long long)n, su.kl);
+            if ((e = hipGetLastError()) != hipSuccess) break;
+            e = su.sort(su.kl, su.kb, su.idx, d_perm + (size_t)c * n, n, stream);
+            rep.launches += 2;
+        }
+        return e;
+    }));
+    MRG_TRY(rep.free_now(d_vin));
+    MRG_OK(rep.run_blocks(nullptr, [&](long long s0, long long sb, double* d_w, hipStream_t) -> hipError_t {
         hipLaunchKernelGGL(exp_kernel, dim3(blocks_for(sb * n, kThreads)), dim3(kThreads), 0, stream, d_w, sb * (long long)n);
-        MRG_TRY(hipGetLastError());
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
         hipLaunchKernelGGL(summary_kernel, dim3((unsigned)(sb * ncols)), dim3(kThreads), 0, stream, d_w, d_vals, d_perm,
                            (long long)n, (int)ncols, d_q, (int)nq, (int)s0, d_mean, d_sd, d_quant);
-        MRG_TRY(hipGetLastError());
-        MRG_TRY(hipEventRecord(ev[2], stream));
-        launches += 3;
-        ++blocks;
-        MRG_TRY(hipEventSynchronize(ev[2]));
-        float ms = 0.f;
-        MRG_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
-        weights_ms += ms;
-        MRG_TRY(hipEventElapsedTime(&ms, ev[1], ev[2]));
-        reduce_ms += ms;
-    }
-    MRG_TRY(hipMemcpyAsync(logz, d_logz, sizeof(double) * (size_t)nsamples, hipMemcpyDeviceToHost, stream));
-    MRG_TRY(hipMemcpyAsync(info, d_info, sizeof(double) * (size_t)nsamples, hipMemcpyDeviceToHost, stream));
-    MRG_TRY(hipMemcpyAsync(mean, d_mean, sizeof(double) * (size_t)nsamples * ncols, hipMemcpyDeviceToHost, stream));
-    MRG_TRY(hipMemcpyAsync(sd, d_sd, sizeof(double) * (size_t)nsamples * ncols, hipMemcpyDeviceToHost, stream));
-    MRG_TRY(hipMemcpyAsync(quant, d_quant, sizeof(double) * (size_t)nsamples * ncols * nq, hipMemcpyDeviceToHost, stream));
-    MRG_TRY(hipStreamSynchronize(stream));
+        rep.launches += 2;
+        return hipGetLastError();
+    }, nullptr));
+    MRG_TRY(hipMemcpyAsync(mean, d_mean, sizeof(double) * sc, hipMemcpyDeviceToHost, stream));
+    MRG_TRY(hipMemcpyAsync(sd, d_sd, sizeof(double) * sc, hipMemcpyDeviceToHost, stream));
+    MRG_TRY(hipMemcpyAsync(quant, d_quant, sizeof(double) * sc * nq, hipMemcpyDeviceToHost, stream));
+    MRG_OK(rep.finish(logz, info));
+    rep.report(timing);
     if (timing) {
-        timing->kernel_ms = setup_ms + weights_ms + reduce_ms;
-        timing->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
-        timing->setup_ms = setup_ms;
-        timing->weights_ms = weights_ms;
-        timing->reduce_ms = reduce_ms;
-        timing->rows = n;
-        timing->elements = n * (long long)nsamples;
-        timing->launches = launches;
         timing->threads = kThreads;
-        timing->blocks = blocks;
         timing->reserved = 0;
     }
-
-done:
-    su.release();
-    for (void* p : {(void*)d_logz, (void*)d_info, (void*)d_w, (void*)d_vin, (void*)d_vals, (void*)d_q, (void*)d_mean, (void*)d_sd,
-                    (void*)d_quant, (void*)d_perm})
-        if (p) (void)hipFree(p);
-    for (auto& e : ev) if (e) (void)hipEventDestroy(e);
-    if (stream) (void)hipStreamDestroy(stream);
-    if (prev_device >= 0 && device >= 0) (void)hipSetDevice(prev_device);
-    return status;
+    return RVLL_OK;
 }
 
 }  // namespace
@@ -342,15 +270,8 @@ extern "C" int rvll_posterior_replicates(int32_t device, const double* logl, con
                                          uint64_t seed, double* logz, double* info, double* mean, double* sd, double* quant,
                                          int64_t block_bytes, rvll_posterior_timing* timing)
 {
-    const int rc = check_common(logl, birth, n_rows, run_start, n_runs);
-    if (rc != RVLL_OK) return rc;
-    if (nsamples < 1) return rvll::report_error(RVLL_E_INVALID, "nsamples must be >= 1");
-    if (mode != RVLL_SHRINK_RANDOM && mode != RVLL_SHRINK_EXPECTED)
-        return rvll::report_error(RVLL_E_INVALID, "mode %d is neither RVLL_SHRINK_RANDOM nor RVLL_SHRINK_EXPECTED", mode);
-    if (bootstrap != 0 && bootstrap != 1) return rvll::report_error(RVLL_E_INVALID, "bootstrap must be 0 or 1");
-    if (bootstrap && n_runs > kMaxBootRuns)
-        return rvll::report_error(RVLL_E_INVALID, "the run bootstrap takes at most %d runs", kMaxBootRuns);
-    if (block_bytes < 0) return rvll::report_error(RVLL_E_INVALID, "negative block_bytes");
+    MRG_OK(check_common(logl, birth, n_rows, run_start, n_runs));
+    MRG_OK(check_replicate_args(nsamples, mode, bootstrap, n_runs, block_bytes));
     if (n_cols < 1 || n_cols > kMaxCols) return rvll::report_error(RVLL_E_INVALID, "n_cols must be in [1, %d]", kMaxCols);
     if (n_q < 1 || n_q > kMaxQ) return rvll::report_error(RVLL_E_INVALID, "n_q must be in [1, %d]", kMaxQ);
     if (!values || !quantiles || !logz || !info || !mean || !sd || !quant)
@@ -358,10 +279,7 @@ extern "C" int rvll_posterior_replicates(int32_t device, const double* logl, con
     for (int32_t k = 0; k < n_q; ++k)
         if (!(quantiles[k] > 0.0 && quantiles[k] < 1.0))
             return rvll::report_error(RVLL_E_INVALID, "quantile level %d is outside (0, 1)", (int)k);
-    for (int64_t i = 0; i < n_rows * (int64_t)n_cols; ++i)
-        if (!std::isfinite(values[i]))
-            return rvll::report_error(RVLL_E_INVALID, "row %lld, column %lld: value is not finite", (long long)(i / n_cols),
-                                      (long long)(i % n_cols));
+    MRG_OK(check_finite_values(values, n_rows, n_cols));
     if (timing) *timing = rvll_posterior_timing{0., 0., 0., 0., 0., n_rows, 0, 0, kThreads, 0, 0};
     return run_posterior(device, logl, birth, n_rows, run_start, n_runs, values, n_cols, quantiles, n_q, nsamples,
                          mode == RVLL_SHRINK_EXPECTED ? 1 : 0, bootstrap, seed, logz, info, mean, sd, quant, block_bytes, timing);
