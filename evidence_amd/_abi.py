@@ -118,6 +118,13 @@ class MarginalTiming(C.Structure):
                 ("launches", C.c_int32), ("threads", C.c_int32), ("blocks", C.c_int32), ("groups", C.c_int32)]
 
 
+class DrawTiming(C.Structure):
+    _fields_ = [("kernel_ms", C.c_double), ("total_ms", C.c_double), ("setup_ms", C.c_double), ("weights_ms", C.c_double),
+                ("reduce_ms", C.c_double), ("scan_ms", C.c_double), ("pick_ms", C.c_double), ("rows", C.c_int64),
+                ("elements", C.c_int64), ("draws", C.c_int64), ("launches", C.c_int32), ("threads", C.c_int32),
+                ("blocks", C.c_int32), ("tiles", C.c_int32)]
+
+
 SHRINK_RANDOM, SHRINK_EXPECTED = 0, 1
 FIP_MAX_PLANETS = 8
 Handle = C.c_void_p
@@ -221,6 +228,11 @@ PROTOTYPES = {
                                            _ip, C.POINTER(C.c_int64), C.c_int32, _ip, C.c_int32, C.c_int32, C.c_int32,
                                            C.c_int32, C.c_uint64, _dp, _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _dp,
                                            _dp, _dp, C.c_int64, C.POINTER(MarginalTiming)]),
+    "rvll_draw_replicates": (C.c_int, [C.c_int32, _dp, _dp, C.c_int64, C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.c_int32,
+                                       C.c_int32, C.c_int32, C.c_uint64, _ip, _dp, _dp, C.POINTER(C.c_int64),
+                                       C.POINTER(C.c_int64), C.c_int64, C.POINTER(DrawTiming)]),
+    "rvll_kep_rv_bands": (C.c_int, [Handle, _dp, C.c_int64, C.c_int32, _dp, C.c_int32, C.c_uint32, _dp, C.c_int32, _dp, _dp, _ip,
+                                    C.c_int64, _dp]),
     "rvll_region_draw_runs": (C.c_int, [Handle, _dp, C.POINTER(C.c_int64), C.c_int64, _dp, _dp, _dp, C.POINTER(C.c_uint64), _ip,
                                         C.c_int32, C.c_int64, C.c_int64, C.c_int32, _dp, _dp, _dp, _ip, C.POINTER(C.c_int64),
                                         C.c_int64, _dp, _ip, _ip, _dp, C.POINTER(C.c_int64), _ip]),

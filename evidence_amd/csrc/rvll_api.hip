@@ -1633,6 +1633,73 @@ int rvll_kep_rv_batch(rvll_handle* h, const double* theta, int64_t B, const doub
     return status;
 }
 
+// ---- order statistics of groups of Keplerian curves (post-processing; rvll_bands.hip) ----------------------------------------
+int rvll_kep_rv_bands(rvll_handle* h, const double* theta, int64_t n_groups, int32_t n, const double* times, int32_t n_times,
+                      uint32_t include_mask, const double* levels, int32_t n_q, double* q, double* mean, int32_t* n_valid,
+                      int64_t chunk_bytes, double* phase_ms)
+{
+    int rc = use_device(h);
+    if (rc) return rc;
+    if (n_groups < 0 || n_times < 0 || chunk_bytes < 0) return fail(RVLL_E_INVALID, "negative size");
+    if (n < 1 || n > 4096) return fail(RVLL_E_INVALID, "n must be in [1, 4096]");
+    if (n_q < 1 || n_q > 16) return fail(RVLL_E_INVALID, "n_q must be in [1, 16]");
+    if (!levels) return fail(RVLL_E_INVALID, "null buffer");
+    for (int32_t k = 0; k < n_q; ++k)
+        if (!(levels[k] > 0.0 && levels[k] < 1.0)) return fail(RVLL_E_INVALID, "level %d is outside (0, 1)", (int)k);
+    if (phase_ms) phase_ms[0] = phase_ms[1] = 0.0;
+    if (n_groups == 0 || n_times == 0) return RVLL_OK;
+    if (!theta || !times || !q || !mean || !n_valid) return fail(RVLL_E_INVALID, "null buffer");
+    const long long group_bytes = (long long)sizeof(double) * n * n_times;
+    const long long bound = chunk_bytes > 0 ? chunk_bytes : 256ll << 20;
+    const long long gc = std::min<long long>(n_groups, std::max<long long>(1, bound / group_bytes));   // whole groups a chunk
+    double *d_times = nullptr, *d_levels = nullptr, *d_vals = nullptr, *d_q = nullptr, *d_mean = nullptr;
+    int32_t* d_nv = nullptr;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    int status = RVLL_OK;
+    hipError_t e = hipMalloc(&d_times, sizeof(double) * (size_t)n_times);
+    if (e == hipSuccess) e = hipMalloc(&d_levels, sizeof(double) * (size_t)n_q);
+    if (e == hipSuccess) e = hipMalloc(&d_vals, (size_t)(gc * group_bytes));
+    if (e == hipSuccess) e = hipMalloc(&d_q, sizeof(double) * (size_t)(gc * n_q * n_times));
+    if (e == hipSuccess) e = hipMalloc(&d_mean, sizeof(double) * (size_t)(gc * n_times));
+    if (e == hipSuccess) e = hipMalloc(&d_nv, sizeof(int32_t) * (size_t)(gc * n_times));
+    for (auto& x : ev)
+        if (e == hipSuccess) e = hipEventCreate(&x);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_times, times, sizeof(double) * (size_t)n_times, hipMemcpyHostToDevice, h->compute);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_levels, levels, sizeof(double) * (size_t)n_q, hipMemcpyHostToDevice, h->compute);
+    for (long long g0 = 0; g0 < n_groups && status == RVLL_OK && e == hipSuccess; g0 += gc) {
+        const long long gb = std::min<long long>(gc, n_groups - g0);
+        status = rvll_dev_upload_theta(h, theta + g0 * n * (long long)h->L.ndim, gb * n);
+        if (status != RVLL_OK) break;
+        rvll::LoglikeArgs a;
+        status = build_args(h, h->d_theta, h->d_logL2[0], h->d_flags2[0], gb * n, &a);
+        if (status != RVLL_OK) break;
+        e = hipEventRecord(ev[0], h->compute);
+        if (e == hipSuccess) e = rvll::launch_keprv(a, d_times, n_times, include_mask, d_vals, h->compute);
+        if (e == hipSuccess) e = hipEventRecord(ev[1], h->compute);
+        if (e == hipSuccess) e = rvll::launch_bands(d_vals, gb, n, n_times, d_levels, n_q, d_q, d_mean, d_nv, h->compute);
+        if (e == hipSuccess) e = hipEventRecord(ev[2], h->compute);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(q + g0 * n_q * n_times, d_q, sizeof(double) * (size_t)(gb * n_q * n_times), hipMemcpyDeviceToHost,
+                               h->compute);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(mean + g0 * n_times, d_mean, sizeof(double) * (size_t)(gb * n_times), hipMemcpyDeviceToHost, h->compute);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(n_valid + g0 * n_times, d_nv, sizeof(int32_t) * (size_t)(gb * n_times), hipMemcpyDeviceToHost,
+                               h->compute);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->compute);
+        float ms = 0.f;
+        if (e == hipSuccess && phase_ms && (e = hipEventElapsedTime(&ms, ev[0], ev[1])) == hipSuccess) phase_ms[0] += ms;
+        if (e == hipSuccess && phase_ms && (e = hipEventElapsedTime(&ms, ev[1], ev[2])) == hipSuccess) phase_ms[1] += ms;
+    }
+    if (status == RVLL_OK && e != hipSuccess)
+        status = fail(e == hipErrorOutOfMemory ? RVLL_E_NOMEM : RVLL_E_HIP, "kep_rv_bands: %s", hipGetErrorString(e));
+    (void)hipStreamSynchronize(h->compute);
+    for (auto& x : ev)
+        if (x) (void)hipEventDestroy(x);
+    dev_free(d_times); dev_free(d_levels); dev_free(d_vals); dev_free(d_q); dev_free(d_mean); dev_free(d_nv);
+    return status;
+}
+
 // ---- diagnostics ---------------------------------------------------------------------
 int rvll_debug_eval(rvll_handle* h, int32_t op, const double* x, const double* y, int64_t n, double* out)
 {

@@ -356,6 +356,10 @@ hipError_t launch_prior_table(int kind, const double* args, double* z, double* d
 
 hipError_t launch_keprv(const LoglikeArgs& a, const double* times, int Nt, unsigned include_mask, double* out,
                         hipStream_t stream);
+// rvll_bands.hip: per (group of n rows of vals [groups n, Nt], time) the count of values that are not NaN, nq order statistics and
+// the mean (rvll_kep_rv_bands; n <= 4096, 1 <= nq <= 16)
+hipError_t launch_bands(const double* vals, long long groups, int n, int Nt, const double* levels, int nq, double* q,
+                        double* mean, int32_t* n_valid, hipStream_t stream);
 hipError_t launch_debug_eval(int op, const double* x, const double* y, long long n, double* out, hipStream_t stream);
 hipError_t launch_fill_cube(double* cube, long long n, uint64_t seed, hipStream_t stream);
 

@@ -13,7 +13,8 @@
 // Per block of replicates (as many as fit the block bound next to the table):
 //     weights   replicate_kernel writes logw - lnZ into the replicate's slot
 //     fixed     every slot entry becomes m = rint(exp(logwt) 2^62) as int64 in place (0 for a row without weight); M = sum m
-//               per replicate by integer adds (shuffles, LDS, one 64-bit integer atomic a workgroup)
+//               per replicate by integer adds (shuffles, LDS, one 64-bit integer atomic a workgroup): launch_fixed of
+//               rvll_merge_setup.hip, which rvll_draws.hip shares
 //     hist      one 512-thread workgroup per (replicate, panel group, row chunk): an int64 histogram of the group's panels in
 //               LDS (a panel's bins and one entry for its outside rows; panels are packed into a group while 8192 entries, 64
 //               KiB, allow), accumulated with 64-bit integer LDS atomics and flushed with 64-bit integer global atomics into
@@ -45,7 +46,6 @@ constexpr unsigned kOutsideBin = 0xFFFFu;
 constexpr long long kMinChunkRows = 1024;                 // chunks shrink to this only while the launch is short of workgroups
 constexpr long long kTargetGroups = 4096;                 // workgroups a hist launch aims at
 constexpr long long kMaxBlockReps = 32768;                // grid y
-constexpr double kScale = 4611686018427387904.0;          // 2^62
 
 struct Panel {
     int32_t a, b;            // axes; b = -1: one-dimensional
@@ -77,35 +77,6 @@ void bin_kernel(const double* __restrict__ vin, const int32_t* __restrict__ orde
         unsigned j = kOutsideBin;
         if (lo >= 1 && x <= e[ne - 1]) j = (unsigned)(lo == ne ? ne - 2 : lo - 1);
         bins[t] = (uint16_t)j;
-    }
-}
-
-__device__ __forceinline__ long long wave_sum(long long v)
-{
-    for (int off = 1; off < kWave; off <<= 1) v += __shfl_xor(v, off, kWave);
-    return v;
-}
-
-__global__ __launch_bounds__(kThreads)
-void fixed_kernel(double* __restrict__ w, long long n, unsigned long long* __restrict__ msum)
-{
-    __shared__ long long sh[kWaves];
-    double* slot = w + (long long)blockIdx.y * n;
-    long long acc = 0;
-    for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < n; i += (long long)gridDim.x * kThreads) {
-        const double p = exp(slot[i]);
-        const long long mi = p > 0.0 ? __double2ll_rn(p * kScale) : 0;    // NaN (a replicate without weight) and 0 give 0
-        slot[i] = __longlong_as_double(mi);                               // the integer's bits: hist_kernel reads them as int64
-        acc += mi;
-    }
-    acc = wave_sum(acc);
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    if (lane == 0) sh[wave] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        long long t = sh[0];
-        for (int k = 1; k < kWaves; ++k) t += sh[k];
-        if (t != 0) atomicAdd(&msum[blockIdx.y], (unsigned long long)t);
     }
 }
 
@@ -335,9 +306,7 @@ int run_marginal(int32_t device, const double* logl, const double* birth, int64_
     }, [&](long long, long long sb, double* d_w, hipStream_t) -> hipError_t {
         const long long chunk = chunk_rows_for(n, ngroups, sb);
         const long long chunks = (n + chunk - 1) / chunk;
-        hipLaunchKernelGGL(fixed_kernel, dim3((unsigned)std::min<long long>(blocks_for(n, kThreads), 1024), (unsigned)sb),
-                           dim3(kThreads), 0, stream, d_w, (long long)n, d_msum);
-        hipError_t e = hipGetLastError();
+        hipError_t e = launch_fixed(d_w, (long long)n, sb, d_msum, stream);
         if (e != hipSuccess) return e;
         e = launch_hist<false>(wave_reduce, dim3((unsigned)(chunks * ngroups), (unsigned)sb), lds, stream,
                                reinterpret_cast<const long long*>(d_w), d_bins, (long long)n, d_panels, d_group_first, ngroups,

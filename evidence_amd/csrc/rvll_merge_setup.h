@@ -1,4 +1,5 @@
-// What the merged-run entry points share (rvll_merge.hip, rvll_posterior.hip, rvll_fip_merged.hip, rvll_marginal.hip): the setup
+// What the merged-run entry points share (rvll_merge.hip, rvll_posterior.hip, rvll_fip_merged.hip, rvll_marginal.hip,
+// rvll_draws.hip): the setup
 // of a merge by birth contours (keys, two radix sorts, placement and the event stream), the replicate kernel, the argument checks
 // and the driver of a call that reduces replicates of the merged run block by block.  rvll_merge_setup.hip defines them, once
 // for the library; rvll_merge.hip's header comment describes the kernels; DESIGN §4j.  This header declares them and holds the
@@ -37,6 +38,7 @@ constexpr long long kDefaultBlockBytes = 512ll << 20;     // rvll_merge_replicat
 // replicate, so a small block leaves most of the device idle: at 2.6e6 rows, 512 MiB (24 replicates) took 2.8 s for the weights of
 // 1000 replicates and 8 GiB 0.24 s (profiles/posterior_probe.txt).  Only min(nsamples, bound / (8 N)) replicates are allocated.
 constexpr long long kDefaultWeightBytes = 8ll << 30;
+constexpr unsigned long long kSeedMul = 0xD1B54A32D192ED03ull;   // replicate s has the seed seed + s * kSeedMul
 
 typedef unsigned long long u64;
 
@@ -68,6 +70,13 @@ __device__ __forceinline__ T wave_scan(T v, int lane)
     return v;
 }
 
+// the sum of v over the wave, in every lane
+__device__ __forceinline__ long long wave_sum(long long v)
+{
+    for (int off = 1; off < kWave; off <<= 1) v += __shfl_xor(v, off, kWave);
+    return v;
+}
+
 // the sum of v over the workgroup, in every thread: butterfly inside a wave, then the waves in order
 __device__ inline double block_sum(double v, double* sh)
 {
@@ -85,6 +94,10 @@ int check_common(const double* logl, const double* birth, int64_t n_rows, const 
 // what every replicate entry point asks of nsamples, mode, bootstrap and block_bytes
 int check_replicate_args(int32_t nsamples, int32_t mode, int32_t bootstrap, int32_t n_runs, int64_t block_bytes);
 int check_finite_values(const double* values, int64_t n_rows, int32_t n_cols);
+
+// The fixed point of the weights of `reps` replicates of n slots each: every entry exp(logwt) becomes m = rint(p 2^62)
+// as int64 in place (0 for a row without weight) and msum[replicate], zeroed by the caller, receives the integer sum of its m.
+hipError_t launch_fixed(double* w, long long n, long long reps, unsigned long long* msum, hipStream_t stream);
 
 struct Replicates;
 

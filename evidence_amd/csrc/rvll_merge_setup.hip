@@ -11,8 +11,8 @@ namespace {
 
 constexpr long long kMaxRows = (1ll << 30) - 1;           // 2N stream positions stay below 2^31
 constexpr int kMaxBootRuns = 8192;                        // LDS multiplicities: 32 KiB
-constexpr unsigned long long kSeedMul = 0xD1B54A32D192ED03ull;
 constexpr unsigned long long kBootXor = 0x5851F42D4C957F2Dull;
+constexpr double kScale = 4611686018427387904.0;          // 2^62
 
 // keys of every row, its index and its run (the last r with run_start[r] <= g)
 __global__ __launch_bounds__(kThreads)
@@ -233,7 +233,38 @@ __global__ __launch_bounds__(kThreads) void replicate_kernel(
         }
 }
 
+// every slot entry becomes m = rint(exp(logwt) 2^62) as int64 in place; msum[replicate] += the sum of its m
+__global__ __launch_bounds__(kThreads)
+void fixed_kernel(double* __restrict__ w, long long n, unsigned long long* __restrict__ msum)
+{
+    __shared__ long long sh[kWaves];
+    double* slot = w + (long long)blockIdx.y * n;
+    long long acc = 0;
+    for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < n; i += (long long)gridDim.x * kThreads) {
+        const double p = exp(slot[i]);
+        const long long mi = p > 0.0 ? __double2ll_rn(p * kScale) : 0;    // NaN (a replicate without weight) and 0 give 0
+        slot[i] = __longlong_as_double(mi);                               // the integer's bits: the reducers read them as int64
+        acc += mi;
+    }
+    acc = wave_sum(acc);
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    if (lane == 0) sh[wave] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        long long t = sh[0];
+        for (int k = 1; k < kWaves; ++k) t += sh[k];
+        if (t != 0) atomicAdd(&msum[blockIdx.y], (unsigned long long)t);
+    }
+}
+
 }  // namespace
+
+hipError_t launch_fixed(double* w, long long n, long long reps, unsigned long long* msum, hipStream_t stream)
+{
+    hipLaunchKernelGGL(fixed_kernel, dim3((unsigned)std::min<long long>(blocks_for(n, kThreads), 1024), (unsigned)reps),
+                       dim3(kThreads), 0, stream, w, n, msum);
+    return hipGetLastError();
+}
 
 int report_hip(hipError_t e, const char* expr, const char* file, int line)
 {

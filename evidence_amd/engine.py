@@ -232,6 +232,43 @@ class GpuRVModel:
             raise KeyError(f"planet{planet}_k1")
         return self._curves(X, time, 1 << (int(planet) - 1))
 
+    def kep_rv_bands(self, theta, time, levels, planet=None, exclude_planet=None, chunk_bytes=None, timing=None):
+        """Order statistics of groups of curves (predictive.bands_definition holds the definition; rvll_kep_rv_bands): theta
+        [G, n, ndim] is G groups of n parameter vectors (n <= 4096), levels up to 16 numbers in (0, 1).  The curves are
+        modelk_batch's for `planet`, else kep_rv_batch's with `exclude_planet`, bit for bit, and stay on the device.  Returns
+        (q [G, len(levels), T], mean [G, T], n_valid int32 [G, T]): per group and time the quantiles by the inverted CDF of
+        equal weights and the mean of the curves that are not NaN, and their number.  chunk_bytes bounds the device buffer of
+        curve values (default 256 MiB, at least one group); the results do not depend on it.  timing: a dict that receives
+        curves_ms and sort_ms."""
+        from .predictive import check_levels
+        theta = np.ascontiguousarray(theta, dtype=np.float64)
+        if theta.ndim != 3 or theta.shape[2] != self.ndim:
+            raise ValueError(f"expected an array of shape (groups, n, {self.ndim}), got {theta.shape}")
+        G, n = theta.shape[:2]
+        if not 1 <= n <= 4096:
+            raise ValueError("a group holds 1 to 4096 rows")
+        levels = check_levels(levels)
+        if planet is not None:
+            if not 1 <= int(planet) <= self.nplanets:
+                raise KeyError(f"planet{planet}_k1")
+            mask = 1 << (int(planet) - 1)
+        else:
+            if not (exclude_planet is None or type(exclude_planet) is int):
+                raise AssertionError(f"exclude_planet has to be an {int}, got {type(exclude_planet)}.")
+            mask = (1 << self.nplanets) - 1
+            if exclude_planet is not None and 1 <= exclude_planet <= self.nplanets:
+                mask &= ~(1 << (exclude_planet - 1))
+        time = np.ascontiguousarray(np.atleast_1d(time), dtype=np.float64)
+        T, Q = time.shape[0], levels.shape[0]
+        q, mean, nv = np.empty((G, Q, T)), np.empty((G, T)), np.empty((G, T), dtype=np.int32)
+        ms = np.zeros(2)
+        _abi.check(self._lib.rvll_kep_rv_bands(self._h, _abi.as_dp(theta), G, n, _abi.as_dp(time), T, int(mask), _abi.as_dp(levels),
+                                               Q, _abi.as_dp(q), _abi.as_dp(mean), _abi.as_ip(nv), int(chunk_bytes or 0),
+                                               _abi.as_dp(ms)))
+        if timing is not None:
+            timing.update(curves_ms=float(ms[0]), sort_ms=float(ms[1]))
+        return q, mean, nv
+
     # ---- prior transform --------------------------------------------------------------------
     def prior_transform_batch(self, cubes):
         cubes = self._theta2d(cubes)

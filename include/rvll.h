@@ -65,7 +65,8 @@ extern "C" {
                                        rvll_posterior_replicates (rvll_posterior_timing),
                                        rvll_fip_replicates (rvll_fip_merged_timing),
                                        rvll_marginal_replicates (rvll_marginal_timing),
-                                       rvll_region_draw_runs, rvll_region_tile_rows */
+                                       rvll_region_draw_runs, rvll_region_tile_rows,
+                                       rvll_draw_replicates (rvll_draw_timing), rvll_kep_rv_bands */
 
 /* ---- error codes ------------------------------------------------------ */
 #define RVLL_OK             0
@@ -571,6 +572,19 @@ int rvll_comm_destroy(rvll_handle* h);
 int rvll_kep_rv_batch(rvll_handle* h, const double* theta, int64_t B, const double* times,
                       int32_t n_times, uint32_t include_mask, double* out /*[B, n_times]*/);
 
+/* Order statistics of groups of those curves (evidence_amd/predictive.py is the definition).  theta holds n_groups
+ * groups of n rows; the curves of every row are rvll_kep_rv_batch's, bit for bit (the same kernel writes them into a device
+ * buffer).  Per group g and time j, over the n curve values of the group at that time: n_valid[g][j] = how many are not NaN;
+ * with those sorted ascending, q[g][k][j] = sorted[max(0, ceil(levels[k] * n_valid) - 1)] (the product in double: the inverted
+ * CDF of equal weights) and mean[g][j] = their sum taken from left to right in sorted order, over n_valid; NaN where n_valid
+ * is 0.  The work goes in chunks of whole groups whose curve values take at most chunk_bytes (0: 256 MiB; at least one group);
+ * the results do not depend on it.  phase_ms (may be NULL) receives the HIP-event time of the curve kernel and of the sort.
+ * RVLL_E_INVALID: n outside [1, 4096], n_q outside [1, 16], a level outside (0, 1), a negative size, null buffers.          */
+int rvll_kep_rv_bands(rvll_handle* h, const double* theta /*[n_groups * n, ndim]*/, int64_t n_groups, int32_t n,
+                      const double* times, int32_t n_times, uint32_t include_mask, const double* levels /*[n_q]*/, int32_t n_q,
+                      double* q /*[n_groups, n_q, n_times]*/, double* mean /*[n_groups, n_times]*/,
+                      int32_t* n_valid /*[n_groups, n_times]*/, int64_t chunk_bytes, double* phase_ms /*NULL or [2]*/);
+
 /* ---- FIP periodogram accumulation (post-processing; independent of any model handle) ------------ */
 /* Replaces the accumulation loop of evidence/fip_criterion.py:305-339.  The caller flattens the posterior
  * samples of all planet models of one run into rows, in the reference's loop order (kmod = 1.., then sample
@@ -799,6 +813,41 @@ int rvll_marginal_replicates(int32_t device, const double* logl /*[n_rows]*/, co
                              double* stats /*[4 * nbins]*/, double* mass /*NULL or [nsamples * nbins]*/,
                              double* outside /*NULL or [nsamples * n_panels]*/, int64_t block_bytes,
                              rvll_marginal_timing* timing);
+
+/* ---- equal-weight draws of the merged run's replicates (post-processing; independent of any model handle) --------- */
+/* Per replicate s of rvll_merge_replicates (same seeds, multiplicities and merged order) ndraws rows drawn by systematic
+ * resampling with one uniform (evidence_amd/draws.py is the definition).  With m_i = rint(exp(logwt_i) 2^62) as int64
+ * (0 for a row without weight; the integers of rvll_marginal_replicates), C the inclusive running sum of m in merged order,
+ * M its last entry, U the 53-bit integer behind uniform01 of (seed_s ^ 0xA0761D6478BD642F, 0), Q = M / ndraws (integer) and
+ * O = (U Q) >> 53:  tau_k = k Q + O, and draw k is the first merged row with C > tau_k.  rows[s * ndraws + k] is that row's
+ * input row, ascending in merged order over k; a row is drawn floor or ceil of ndraws p_i times, a row with m = 0 never; a
+ * replicate with M < ndraws (a bootstrap of empty runs) has -1 throughout.  logz[s], info[s] as rvll_merge_replicates gives
+ * them.  fixed [nsamples * n_rows] (m in merged order) and msum [nsamples] (M) may each be NULL.  block_bytes bounds the device
+ * block of weights (8 * n_rows bytes a replicate); 0 stands for 8 GiB, of which only nsamples replicates are allocated;
+ * RVLL_E_NOMEM before any work when one replicate does not fit.  Every decision is an integer comparison: the results do not
+ * depend on the batching or on the other replicates.  RVLL_E_INVALID: everything rvll_merge_replicates refuses, ndraws outside
+ * [1, 2^20], null required buffers.  timing may be NULL.  device < 0 uses the current device. */
+typedef struct rvll_draw_timing {
+    double  kernel_ms;       /* HIP-event time of all device work: setup_ms + weights_ms + reduce_ms                       */
+    double  total_ms;        /* the whole call: checks, allocation, uploads, kernels, downloads                            */
+    double  setup_ms;        /* the merge's setup                                                                           */
+    double  weights_ms;      /* the replicate kernels (what rvll_merge_replicates spends on the same input)                 */
+    double  reduce_ms;       /* scan_ms + pick_ms, and the download of `fixed` when it is asked for                         */
+    double  scan_ms;         /* fixed point and the three launches of the running sum                                       */
+    double  pick_ms;         /* the searches                                                                                */
+    int64_t rows;            /* n_rows                                                                                      */
+    int64_t elements;        /* (row, replicate) pairs: n_rows * nsamples                                                   */
+    int64_t draws;           /* ndraws * nsamples                                                                           */
+    int32_t launches;        /* 4 for the setup, then 6 a block of replicates (a rocPRIM sort counted as one)               */
+    int32_t threads;         /* per workgroup                                                                               */
+    int32_t blocks;          /* blocks of replicates the call was split into                                                */
+    int32_t tiles;           /* tiles of 1024 rows of the running sum                                                       */
+} rvll_draw_timing;
+int rvll_draw_replicates(int32_t device, const double* logl /*[n_rows]*/, const double* birth /*[n_rows]*/, int64_t n_rows,
+                         const int64_t* run_start /*[n_runs + 1]*/, int32_t n_runs, int32_t ndraws, int32_t nsamples,
+                         int32_t mode, int32_t bootstrap, uint64_t seed, int32_t* rows /*[nsamples * ndraws]*/,
+                         double* logz /*[nsamples]*/, double* info /*[nsamples]*/, int64_t* fixed /*NULL or [nsamples * n_rows]*/,
+                         int64_t* msum /*NULL or [nsamples]*/, int64_t block_bytes, rvll_draw_timing* timing);
 
 /* ---- MLFriends region sampling (evidence_amd/region.py holds the definition) -----------------------------------
  * kdraw draws from the constrained prior of each of R runs by uniform rejection sampling from the union of the balls of
