@@ -31,14 +31,15 @@ def _assert_same(got, ref, what):
     assert got[2].tobytes() == ref[2].tobytes(), (what, got[2], ref[2])
 
 
-def _cases(rng, ndim):
-    """(name, runs, wrapped): blobs, a blob across the wrap, uniform rows, a ragged batch with runs of 0, 1 and 2 rows."""
+def _cases(rng, ndim, wrap_dim=0):
+    """(name, runs, wrapped): blobs, a blob across the wrap of dimension wrap_dim (the one wrapped dimension), uniform rows, a
+    ragged batch with runs of 0, 1 and 2 rows."""
     def blobs(centres, n, sig):
         return np.concatenate([np.clip(rng.normal(c, sig, (n, ndim)), 0.0, np.nextafter(1.0, 0.0)) for c in centres])
     wrap_blob = rng.normal(0.0, 0.02, (120, ndim)) + 0.5
-    wrap_blob[:, 0] = (wrap_blob[:, 0] - 0.5) % 1.0
+    wrap_blob[:, wrap_dim] = (wrap_blob[:, wrap_dim] - 0.5) % 1.0
     wr = np.zeros(ndim, dtype=bool)
-    wr[0] = True
+    wr[wrap_dim] = True
     return [("blobs", [blobs([0.2, 0.5, 0.8], 90, 0.02)], None),
             ("wrapped", [wrap_blob], wr),
             ("not wrapped", [wrap_blob], None),
@@ -47,11 +48,16 @@ def _cases(rng, ndim):
                         rng.random((333, ndim)), blobs([0.25, 0.75], 65, 0.01)], wr)]
 
 
-@pytest.mark.parametrize("ndim", [1, 7, 19])
+@pytest.mark.parametrize("ndim", [1, 7, 19, 8, 9, 16, 17, 32, 33, 64])
 def test_device_clustering_is_the_numpy_definition(gpu_required, ndim):
+    """1, 7 and 19 dimensions with dimension 0 wrapped; then both sides of every edge of the kernels' register templates (rows
+    of 8, 16, 32 and 64 doubles: 8 | 9, 16 | 17, 32 | 33, and 64 itself) with the last dimension wrapped: bit 32 of the 64-bit
+    mask at 33 dimensions, bit 63 at 64.  The runs of 400 and 333 rows cross the LDS tile (16384 / 8 ndim rows) at every size;
+    at 33 and 64 dimensions the tile (62 and 32 rows) is shorter than the 64-row workgroup that loads it."""
     rng = np.random.default_rng(100 + ndim)
+    wrap_dim = 0 if ndim in (1, 7, 19) else ndim - 1
     with _offsets_model(ndim) as m:
-        for name, runs, wr in _cases(rng, ndim):
+        for name, runs, wr in _cases(rng, ndim, wrap_dim):
             cube = np.concatenate(runs)
             run_start = np.concatenate([[0], np.cumsum([len(r) for r in runs])]).astype(np.int64)
             scale = rng.uniform(0.5, 4.0, (len(runs), ndim))

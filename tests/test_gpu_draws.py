@@ -1,6 +1,7 @@
 """Equal-weight draws on the device (rvll_draw_replicates; draws.draw_arrays with device=0) against the numpy definition of
 evidence_amd/draws.py, on the 3212 ragged rows of the marginal tests (over three 1024-row tiles of the running sum; ties, plateaus
-and off-contour rows) for both shrinkage modes with and without the run bootstrap and 1, 64 and 1000 draws.
+and off-contour rows) for both shrinkage modes with and without the run bootstrap and 1, 64 and 1000 draws; and on 528 000 rows
+whose mass covers the merged order (_wide of tests/test_gpu_merge.py: 516 tiles, three steps of the scan of the tile sums).
 
 Exact.  With the device's own integers m (the optional output `fixed`) the definition's pick must give the device's rows bit for
 bit: every decision is an integer comparison.  ln Z and H are rvll_merge_replicates' bits.
@@ -19,6 +20,7 @@ import pytest
 from evidence_amd import RvllError, _abi, draws, marginals, merge
 from evidence_amd.shrinkage import replicate_seeds
 from test_gpu_marginals import _check, _reference
+from test_gpu_merge import _wide
 from test_marginals_host import _case, _small
 from test_merge_host import _arrays, _ragged, _synthetic
 
@@ -112,6 +114,76 @@ def test_bits_do_not_depend_on_the_batching_or_on_the_other_replicates(gpu_requi
     for a, b, c, d in zip(one, again, few, single):
         assert np.array_equal(a, b) and np.array_equal(a, c) and np.array_equal(a, d)
     assert all(np.array_equal(a[0], b[0]) for a, b in zip(one, first))
+
+
+WIDE_S = 6
+WIDE_SEED = 2      # (the third scan step holds 8e-4 of the mass, under one draw in 1000: a seed whose draws reach it in every replicate)
+_WIDE = {}
+
+
+def _wide_definition(mode, bootstrap):
+    """(logl, birth, run_start, order, m [WIDE_S, N]) of the definition on _wide(n_runs=24): 528 000 rows, 516 tiles — three
+    256-tile steps of the tile scan, the last one of 4 tiles, and the smallest round size past the 1024 blocks at which the
+    fixed-point kernel's grid is clamped.  Computed once, shared, never changed."""
+    key = (mode, bootstrap)
+    if key not in _WIDE:
+        if "input" not in _WIDE:
+            _WIDE["input"] = _wide(n_runs=24)
+        logl, birth, run_start = _WIDE["input"]
+        _, _, logwt = merge.replicates_arrays(logl, birth, run_start, WIDE_S, seed=WIDE_SEED, mode=mode, bootstrap=bootstrap,
+                                              return_logwt=True)
+        out = (merge._layout(logl, birth, run_start)["order"].astype(np.int64), draws.fixed_point(logwt))
+        for v in out:
+            v.setflags(write=False)
+        _WIDE[key] = (logl, birth, run_start) + out
+    return _WIDE[key]
+
+
+@pytest.mark.parametrize("mode, bootstrap", [("random", True), ("expected", False)])
+def test_draws_of_516_tiles_land_throughout_the_merged_order_and_are_the_definitions(gpu_required, mode, bootstrap):
+    """The first test at 516 tiles, on a fixture whose mass covers the merged order (tests/test_merge_host.py).  The tile scan's
+    carry and the parity of its two LDS buffers decide every draw past tile 255: with the definition alone, the 1000 draws of
+    every replicate land in at least 400 distinct tiles and in all three 256-tile steps (measured: 470 - 474 tiles), so a scan
+    that is wrong from its second step on moves more than half of the draws."""
+    logl, birth, run_start, order, m_def = _wide_definition(mode, bootstrap)
+    N = logl.size
+    assert N == 528_000 and -(-N // 1024) == 516
+    seeds = replicate_seeds(WIDE_SEED, WIDE_S)
+    for s in range(WIDE_S):
+        tiles = np.unique(draws.pick(m_def[s], seeds[s], 1000) // 1024)
+        print("replicate", s, "distinct tiles", tiles.size, "steps", sorted(set((tiles // 256).tolist())))
+        assert tiles.size >= 400 and set((tiles // 256).tolist()) == {0, 1, 2}
+    c_def = np.cumsum(m_def, axis=1, dtype=np.int64)
+    bound = 1e-10 * c_def.astype(np.float64) + np.arange(1, N + 1)
+    compared = fragile = 0
+    for n in (1, 64, 1000):
+        rows, logz, info, fixed, msum = draws.device_integers(logl, birth, run_start, n, WIDE_S, seed=WIDE_SEED, mode=mode,
+                                                              bootstrap=bootstrap)
+        assert np.array_equal(msum, fixed.sum(axis=1, dtype=np.int64)) and fixed.min() >= 0
+        assert np.array_equal(rows, _own(order, fixed, seeds, n)), n
+        err = np.abs(np.cumsum(fixed, axis=1, dtype=np.int64) - c_def)
+        print("n", n, "max |C err| / bound", float((err / bound).max()))
+        assert np.all(err <= bound)
+        want = _own(order, m_def, seeds, n)
+        for s in range(WIDE_S):
+            frag = _fragile(c_def[s], seeds[s], n)
+            assert np.array_equal(rows[s][~frag], want[s][~frag]), (n, s)
+            compared += n
+            fragile += int(frag.sum())
+    print("fragile draws", fragile, "of", compared)
+    assert compared == 6390 and fragile * 1000 <= compared
+
+
+def test_bits_of_516_tiles_do_not_depend_on_the_batching(gpu_required):
+    logl, birth, run_start = _wide_definition("random", True)[:3]
+    kw = dict(seed=WIDE_SEED, device=0)
+    timing = {}
+    one = draws.draw_arrays(logl, birth, run_start, 1000, WIDE_S, timing=timing, **kw)
+    assert timing["blocks"] == 1 and timing["tiles"] == 516 and timing["rows"] == logl.size
+    few = draws.draw_arrays(logl, birth, run_start, 1000, WIDE_S, block_bytes=8 * logl.size * 2 + 8, timing=timing, **kw)
+    assert timing["blocks"] == 3
+    assert all(np.array_equal(a, b) for a, b in zip(one, few))
+    assert one[0].min() >= 0 and np.unique(one[0][0]).size > 400
 
 
 @pytest.mark.parametrize("nlive, ndead", [(1, 0), (24, 1000), (25, 1000)])

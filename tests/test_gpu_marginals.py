@@ -20,7 +20,7 @@ import pytest
 
 from evidence_amd import RvllError, _abi, marginals, merge, run_nested_ensemble
 from evidence_amd.callbacks import wrapped_params
-from test_gpu_merge import _51peg, _big, _close
+from test_gpu_merge import _51peg, _big, _close, _wide
 from test_marginals_host import _case, _small, _with_empty_runs
 from test_merge_host import _arrays, _ragged
 from test_posterior_host import _columns
@@ -190,6 +190,57 @@ def test_two_million_rows_match_the_definition_on_the_first_replicates(gpu_requi
     assert all(np.all(np.isfinite(v)) for v in dev.values()) and np.all(dev["mass"] >= 0) and np.all(dev["outside"] >= 0)
     start = dev["panel_start"]
     total = np.add.reduceat(dev["mass"], start[:-1], axis=1) + dev["outside"]
+    assert np.all(np.abs(total - 1.0) <= 1e-9), float(np.abs(total - 1.0).max())
+    assert np.all(dev["min"] <= dev["max"]) and np.all(dev["std"] >= 0)
+
+
+def _wide_case():
+    """_wide with the posterior tests' six columns (column 4 follows log-L) and the axes and panels of the test above."""
+    logl, birth, run_start = _wide()
+    n = logl.size
+    rng = np.random.default_rng(1)
+    values = np.stack([rng.normal(0.0, 3.0, n), np.round(rng.normal(2.0, 0.5, n), 1), 4.23 + 1e-5 * rng.normal(size=n),
+                       np.exp(rng.uniform(0.0, 7.0, n)), logl + rng.normal(0.0, 0.1, n),
+                       rng.integers(0, 5, n).astype(float)], axis=1)
+    lo, hi = values.min(axis=0), values.max(axis=0)
+    span = hi - lo
+    axes = [(c, np.linspace(lo[c] + 0.02 * span[c], hi[c] - 0.02 * span[c], 201)) for c in range(6)]
+    axes += [(c, np.linspace(lo[c], hi[c], 41)) for c in range(6)]
+    panels = list(range(6)) + [(6 + a, 6 + b) for a in range(6) for b in range(a + 1, 6)]
+    return values, logl, birth, run_start, axes, panels
+
+
+def test_two_million_rows_of_spread_mass_match_the_definition(gpu_required):
+    """The histograms of _wide, whose mass covers the merged order (tests/test_merge_host.py): every bin's mass is a sum over
+    rows of every tile, 8e-4 of it from rows past 2^21 (the second grid-stride pass), so a bin kernel or a replicate carry that
+    loses rows is outside the bound here where on _big it would lose nothing that has weight.
+
+    The case has not degenerated: in the definition, more than half of the bins of every 1-D panel hold mass.  A bin holds
+    mass only if a value of its column falls into it, and columns 1 and 5 take 48 and 3 values inside their 200 bins, so the
+    count is held against min(bins, distinct values inside the panel): the bins themselves for the other four columns."""
+    values, logl, birth, run_start, axes, panels = _wide_case()
+    n = logl.size
+    assert n > 2 ** 21 + 8192 and len(panels) == 21
+    kw = dict(seed=3, mode="random", bootstrap=True)
+    timing = {}
+    dev = marginals.marginals_arrays(values, logl, birth, run_start, axes, panels, nsamples=4, device=0, return_replicates=True,
+                                     timing=timing, **kw)
+    print("timing", timing)
+    assert timing["elements"] == 4 * n and timing["rows"] == n and timing["bins"] == 6 * 200 + 15 * 1600
+    ref = marginals.marginals_arrays(values, logl, birth, run_start, axes, panels, nsamples=2, return_replicates=True, **kw)
+    start = ref["panel_start"]
+    for c in range(6):
+        edges = axes[c][1]
+        col = values[:, c]
+        attainable = min(200, np.unique(col[(col >= edges[0]) & (col < edges[-1])]).size)
+        held = (ref["mass"][:, start[c]:start[c + 1]] > 0).sum(axis=1)
+        print("panel", c, "bins with mass", held, "attainable", attainable)
+        assert np.all(held > 0.5 * attainable), (c, held, attainable)
+    _check(dev, ref, 2, stats=False)
+    assert dev["outside_count"][:6].min() > 0 and np.all(dev["outside_count"][6:] == 0)
+    assert all(np.all(np.isfinite(v)) for v in dev.values()) and np.all(dev["mass"] >= 0) and np.all(dev["outside"] >= 0)
+    total = np.add.reduceat(dev["mass"], start[:-1], axis=1) + dev["outside"]
+    print("max |mass + outside - 1|", float(np.abs(total - 1.0).max()))
     assert np.all(np.abs(total - 1.0) <= 1e-9), float(np.abs(total - 1.0).max())
     assert np.all(dev["min"] <= dev["max"]) and np.all(dev["std"] >= 0)
 

@@ -127,6 +127,22 @@ def _big(n_runs=96, rows=22_000, seed=0):
     return logl, birth, run_start
 
 
+def _wide(n_runs=96, rows=22_000, seed=0):
+    """_big's recipe with a flat likelihood: log-L is N(0, 0.5) and births lie Exp(0.4) below, so the posterior mass is spread
+    over the whole merged order (every row has a non-zero 62-bit weight in expected mode, no 1024-row tile holds more than 1 %;
+    tests/test_merge_host.py asserts it) where _big's sits on its last rows.  A sum over rows that loses any part of the merged
+    order is then off by far more than the 1e-10 bounds of the reducers' tests."""
+    rng = np.random.default_rng(seed)
+    n = n_runs * rows
+    logl = np.round(rng.normal(0.0, 0.5, n), 6)
+    birth = logl - rng.exponential(0.4, n)
+    birth[rng.random(n) < 0.02] = -np.inf
+    off = rng.random(n) < 1e-4
+    birth[off] = logl[off] + rng.integers(0, 2, off.sum())
+    run_start = np.arange(0, n + 1, rows, dtype=np.int64)
+    return logl, birth, run_start
+
+
 def test_two_million_rows_match_the_definition_on_the_first_replicates(gpu_required):
     logl, birth, run_start = _big()
     assert logl.size > 2_000_000
@@ -141,6 +157,39 @@ def test_two_million_rows_match_the_definition_on_the_first_replicates(gpu_requi
         timing = {}
         d = merge.replicates_arrays(logl, birth, run_start, 64, seed=3, mode=mode, bootstrap=bootstrap, device=0, timing=timing)
         r = merge.replicates_arrays(logl, birth, run_start, 2, seed=3, mode=mode, bootstrap=bootstrap)
+        _close(d[0][:2], r[0])
+        _close(d[1][:2], r[1])
+        assert timing["elements"] == 64 * logl.size and timing["launches"] == 5
+
+
+def _rel(got, want):
+    """The largest error in _close's measure, for the record."""
+    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
+    fin = np.isfinite(want)
+    return float((np.abs(got[fin] - want[fin]) / np.maximum(1.0, np.abs(want[fin]))).max())
+
+
+def test_two_million_rows_of_spread_mass_match_the_definition_row_by_row(gpu_required):
+    """_wide: rows of every weight throughout the merged order, so ln Z and H are sums to which the rows from 2^21 on (the
+    second grid-stride pass of the 8192-block launches) contribute 8e-4 and no tile more than 0.3 %."""
+    logl, birth, run_start = _wide()
+    assert logl.size > 2 ** 21 + 8192
+    want = merge.merge_arrays(logl, birth, run_start)
+    got = merge.merge_arrays(logl, birth, run_start, device=0)
+    assert np.array_equal(got["order"], want["order"]) and np.array_equal(got["nlive_row"], want["nlive_row"])
+    assert got["off_contour"] == want["off_contour"] > 0
+    print("max |logwt|", float(np.abs(want["logwt"][np.isfinite(want["logwt"])]).max()), " logz err / 1e-12",
+          _rel(got["logz"], want["logz"]) / 1e-12, " information err / 1e-12", _rel(got["information"], want["information"]) / 1e-12,
+          " logwt err / 1e-12", _rel(got["logwt"], want["logwt"]) / 1e-12)
+    _close(got["logz"], want["logz"])
+    _close(got["information"], want["information"])
+    _close(got["logwt"], want["logwt"])
+    for mode, bootstrap in (("random", True), ("random", False), ("expected", True)):
+        timing = {}
+        d = merge.replicates_arrays(logl, birth, run_start, 64, seed=3, mode=mode, bootstrap=bootstrap, device=0, timing=timing)
+        r = merge.replicates_arrays(logl, birth, run_start, 2, seed=3, mode=mode, bootstrap=bootstrap)
+        print(mode, bootstrap, "logz err / 1e-12", _rel(d[0][:2], r[0]) / 1e-12, " information err / 1e-12",
+              _rel(d[1][:2], r[1]) / 1e-12)
         _close(d[0][:2], r[0])
         _close(d[1][:2], r[1])
         assert timing["elements"] == 64 * logl.size and timing["launches"] == 5

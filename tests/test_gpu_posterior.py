@@ -17,7 +17,7 @@ import pytest
 
 from evidence_amd import RvllError, _abi, merge, posterior, run_nested_ensemble
 from evidence_amd.callbacks import wrapped_params
-from test_gpu_merge import _51peg, _big, _close
+from test_gpu_merge import _51peg, _big, _close, _wide
 from test_merge_host import _arrays, _ragged
 from test_posterior_host import _columns
 
@@ -107,6 +107,28 @@ def test_two_million_rows_match_the_definition_on_the_first_replicates(gpu_requi
     timing = {}
     dev = posterior.summarize_arrays(values, logl, birth, run_start, nsamples=64, device=0, timing=timing, **kw)
     assert timing["elements"] == 64 * n and timing["rows"] == n
+    print("timing", timing)
+    single, total = _check(dev, values, logl, birth, run_start, 2, **kw)
+    assert total == 2 * 3 * 6 and single >= 0.99 * total
+    assert all(np.all(np.isfinite(dev[k])) for k in dev) and np.all(dev["std"] >= 0)
+    assert np.all(np.diff(dev["quantiles"], axis=1) >= 0)
+
+
+def test_two_million_rows_of_spread_mass_match_the_definition(gpu_required):
+    """The same columns on _wide, whose mass covers the merged order (tests/test_merge_host.py): the means, deviations and
+    quantiles are then sums to which every tile contributes, the rows from 2^21 on (the second grid-stride pass) 8e-4 of them,
+    against bounds of 1e-10.  Column 4 follows log-L, and with it the merged order."""
+    logl, birth, run_start = _wide()
+    n = logl.size
+    assert n > 2 ** 21 + 8192
+    rng = np.random.default_rng(1)
+    values = np.stack([rng.normal(0.0, 3.0, n), np.round(rng.normal(2.0, 0.5, n), 1), 4.23 + 1e-5 * rng.normal(size=n),
+                       np.exp(rng.uniform(0.0, 7.0, n)), logl + rng.normal(0.0, 0.1, n),
+                       rng.integers(0, 5, n).astype(float)], axis=1)
+    kw = dict(seed=3, mode="random", bootstrap=True)
+    timing = {}
+    dev = posterior.summarize_arrays(values, logl, birth, run_start, nsamples=8, device=0, timing=timing, **kw)
+    assert timing["elements"] == 8 * n and timing["rows"] == n
     print("timing", timing)
     single, total = _check(dev, values, logl, birth, run_start, 2, **kw)
     assert total == 2 * 3 * 6 and single >= 0.99 * total

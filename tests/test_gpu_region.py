@@ -174,6 +174,133 @@ def test_results_do_not_depend_on_the_batching(gpu_required):
             _check_decisions(m, part[5][r], [x[r] for x in part[:5]], u, sc, r2, ls, sd, wr, 10 ** 4)
 
 
+HIGH_KDRAW = 64
+HIGH_CAP = 4800
+
+
+def _high_wrapped(ndim):
+    wr = np.zeros(ndim, dtype=bool)
+    wr[ndim - 1] = True                      # bit 32 of the mask at 33 dimensions, bit 63 at 64
+    if ndim > 35:
+        wr[35] = True                        # a second bit of the high word, not the last (64 dimensions only: 33 has no such)
+    return wr
+
+
+def _high_runs(evaluate, ndim, sizes, wr, seed):
+    """_runs for a model of ndim offsets.  The cloud's centre lies at 0.5 +- 0.01, but for coordinates 0 and 1 (not wrapped),
+    which lie at 0.02 and 0.985: candidates cross both walls.  The contour of the draw is the midpoint of the two middle log-L
+    values among the kept ones of the definition's first 512 candidates (drawn with lstar = +inf, so that none is taken): about
+    half of the kept candidates are accepted at any ndim, and the contour lies on none of them."""
+    rng = np.random.default_rng(seed)
+    centre = 0.5 + rng.uniform(-0.01, 0.01, ndim)
+    centre[0], centre[1] = 0.02, 0.985
+    runs = []
+    for r, n in enumerate(sizes):
+        cloud = centre + 0.03 * rng.standard_normal((2 * n + 64, ndim))
+        cloud[:, wr] %= 1.0
+        cloud = np.clip(cloud, 0.0, np.nextafter(1.0, 0.0))
+        logl = evaluate(cloud)[1]
+        floor = float(np.quantile(logl, 0.3))
+        u = cloud[logl > floor][:n]
+        assert len(u) == n
+        u = u[np.argsort(logl[logl > floor][:n], kind="stable")]
+        scale = nested._cluster_scale(u)
+        radius2 = clustering.cluster_one(u, scale, wr, 30, 40 + r)[2]
+        assert not region.blocked(scale, radius2, wr)
+        sd = 900 + 13 * r + seed
+        pre = region.draw_runs(u, [0, n], scale[None], [radius2], [np.inf], [sd], HIGH_KDRAW, evaluate, wrapped=wr,
+                               max_candidates=512, trace=True, block=512)[5][0]
+        kept = np.sort(pre["logl"][(pre["flags"] & region.KEPT) != 0])
+        assert kept.size >= 2 and kept[kept.size // 2 - 1] < kept[kept.size // 2]
+        lstar = 0.5 * (kept[kept.size // 2 - 1] + kept[kept.size // 2])
+        runs.append((u, scale, radius2, float(lstar), sd))
+    return runs
+
+
+@pytest.mark.parametrize("ndim", [8, 9, 16, 17, 32, 33, 64])
+def test_every_dimension_template_matches_the_definition(gpu_required, ndim):
+    """Both sides of every edge of the propose kernel's register templates (8, 16, 32 and 64 coordinates: 8 | 9, 16 | 17,
+    32 | 33, and 64 itself), on a model of ndim instrument offsets: the last dimension wrapped, and dimension 35 too where there
+    is one (bits of the mask's high word); runs of 40 survivors and of one more than the LDS tile holds.  With the definition
+    alone: candidates leave the cube, every run gets its 64 draws, under 1 % of the candidates are fragile, and up to 17
+    dimensions some candidate lies in more than one ball (beyond, the balls of so thin a cloud hardly overlap)."""
+    from test_gpu_clustering import _offsets_model
+    with _offsets_model(ndim) as m:
+        tile = m.region_tile_rows()
+        assert tile == 5120 // ndim
+        wr = _high_wrapped(ndim)
+        runs = _high_runs(m.prior_loglike_batch, ndim, [40, tile + 1], wr, ndim)
+        surv, run_start, scale, radius2, lstar, seeds = _args(runs)
+        kw = dict(wrapped=wr, max_candidates=HIGH_CAP, trace=True)
+        ref = region.draw_runs(surv, run_start, scale, radius2, lstar, seeds, HIGH_KDRAW, m.prior_loglike_batch, block=SMALL_BLOCK,
+                               **kw)
+        frag = [_fragile(ref[5][r], u, sc, r2, ls, sd, wr) for r, (u, sc, r2, ls, sd) in enumerate(runs)]
+        flags = np.concatenate([t["flags"] for t in ref[5]])
+        ncand, nfrag = flags.size, int(sum(np.count_nonzero(f) for f in frag))
+        counts = {name: int(np.count_nonzero(flags & bit)) for name, bit in (("outside", region.OUTSIDE), ("lost", region.LOST),
+                                                                              ("kept", region.KEPT), ("accepted", region.ACCEPTED))}
+        nmax = max(int(t["n"].max()) for t in ref[5])
+        print(f"D = {ndim}: {ncand} candidates, {counts}, largest n {nmax}, {nfrag} fragile, nfound {ref[3]}, ncalls {ref[4]}")
+        assert counts["outside"] > 0 and counts["kept"] > 0 and np.all(ref[3] == HIGH_KDRAW)
+        assert nfrag < 0.01 * ncand
+        assert ndim > 17 or nmax > 1
+        small = m.region_draw_runs(surv, run_start, scale, radius2, lstar, seeds, HIGH_KDRAW, block=SMALL_BLOCK, **kw)
+        large = m.region_draw_runs(surv, run_start, scale, radius2, lstar, seeds, HIGH_KDRAW, block=LARGE_BLOCK, **kw)
+        assert _same(small, large)
+        worst = 0.0
+        for r, (u, sc, r2, ls, sd) in enumerate(runs):
+            t, tr = small[5][r], ref[5][r]
+            k = min(len(t["c"]), len(tr["c"]))
+            assert k > 0 and len(t["c"]) % SMALL_BLOCK == 0 and np.array_equal(t["c"][:k], tr["c"][:k])
+            ok = ~frag[r][:k]
+            err = t["cube"][:k][ok] - tr["cube"][:k][ok]
+            err[:, wr] -= np.rint(err[:, wr])
+            worst = max(worst, float(np.abs(err).max()))
+            for out in (small, large):
+                _check_decisions(m, out[5][r], [x[r] for x in out[:5]], u, sc, r2, ls, sd, wr, HIGH_KDRAW)
+            if not frag[r].any() and len(t["c"]) == len(tr["c"]):
+                assert np.array_equal(t["flags"], tr["flags"]) and np.array_equal(t["n"], tr["n"])
+                assert small[3][r] == ref[3][r] and small[4][r] == ref[4][r]
+            kk = len(t["c"])
+            assert kk <= len(large[5][r]["c"])
+            for key in ("cube", "flags", "n", "logl"):
+                assert t[key].tobytes() == large[5][r][key][:kk].tobytes(), (r, key)
+        print(f"D = {ndim}: max |device - definition| = {worst:.3e}")
+        assert worst <= 1e-13
+
+
+def test_the_offsets_carry_and_every_select_pass(gpu_required):
+    """65 runs of 40 survivors with a block of 1024 candidates: 260 workgroups, which the offsets kernel scans 256 at a time,
+    so the four workgroups of run 64 start at the carry of the first step; and select takes four passes of 256 over a block
+    (sixteen over the default block of 4096), its counts of accepted and kept candidates carried from pass to pass.  The runs
+    that evaluate more than 256 candidates with the small block take draws past select's first pass."""
+    with _model() as m:
+        wr = _one_wrapped(m)
+        runs = _runs(m, [40] * 65, wr, 4)
+        surv, run_start, scale, radius2, lstar, seeds = _args(runs)
+        kw = dict(wrapped=wr, max_candidates=8192, trace=True)
+        small = m.region_draw_runs(surv, run_start, scale, radius2, lstar, seeds, HIGH_KDRAW, block=SMALL_BLOCK, **kw)
+        wide = m.region_draw_runs(surv, run_start, scale, radius2, lstar, seeds, HIGH_KDRAW, block=1024, return_rounds=True, **kw)
+        evaluated = np.array([len(t["c"]) for t in small[5]])
+        print("candidates a run evaluated with the small block: min", evaluated.min(), "median", int(np.median(evaluated)), "max",
+              evaluated.max(), " nfound", small[3].min(), small[3].max(), " rounds of the block of 1024:", wide[6])
+        assert np.all(small[3] == HIGH_KDRAW) and np.count_nonzero(evaluated > 256) >= 33 and evaluated[64] > 256
+        assert _same(small, wide)
+        for r, (u, sc, r2, ls, sd) in enumerate(runs):
+            assert len(wide[5][r]["c"]) % 1024 == 0 and len(wide[5][r]["c"]) >= evaluated[r]
+            _check_decisions(m, wide[5][r], [x[r] for x in wide[:5]], u, sc, r2, ls, sd, wr, HIGH_KDRAW)
+        rows = slice(run_start[64], run_start[65])
+        alone = m.region_draw_runs(surv[rows], [0, 40], scale[64:65], radius2[64:65], lstar[64:65], seeds[64:65], HIGH_KDRAW,
+                                   block=1024, **kw)
+        assert _same(alone, [x[64:65] for x in wide[:5]])
+        four = slice(0, run_start[4])
+        default = m.region_draw_runs(surv[four], run_start[:5], scale[:4], radius2[:4], lstar[:4], seeds[:4], HIGH_KDRAW, **kw)
+        assert all(len(t["c"]) == 4096 for t in default[5])
+        assert _same(default, [x[:4] for x in small[:5]])
+        for r, (u, sc, r2, ls, sd) in enumerate(runs[:4]):
+            _check_decisions(m, default[5][r], [x[r] for x in default[:5]], u, sc, r2, ls, sd, wr, HIGH_KDRAW)
+
+
 def test_blocked_and_empty_runs_and_argument_errors(gpu_required):
     from evidence_amd import _abi
     with _model() as m:

@@ -196,6 +196,34 @@ def test_merged_gaussian_evidence_is_right_within_its_error():
     assert abs(merged.logz - TRUTH) < 4 * single
 
 
+@pytest.mark.parametrize("n_runs", [24, 96])
+@pytest.mark.parametrize("mode, bootstrap", [("expected", False), ("random", True)])
+def test_the_wide_fixture_spreads_its_mass_over_the_merged_order(mode, bootstrap, n_runs):
+    """The device tests that weigh every row (the _wide tests of tests/test_gpu_*.py) rest on this: in the definition's 62-bit
+    fixed-point weights of _wide, at least 95 % of the 1024-row tiles of the merged order hold 0.1 / ntiles of the mass or more,
+    and no tile of the 2 112 000-row default (2063 tiles) holds over 1 %.  Conditions on the fixture, not measurements: the
+    worst of the replicates here has 2058 of 2063 tiles above the floor and a largest tile of 0.29 %.
+
+    A tile's share goes as 1 / ntiles, so the ceiling is 1 % · 2063 / ntiles: 20.6 mean tiles at either size.  At 24 runs
+    (528 000 rows, 516 tiles: the draws' fixture) 515 tiles are above the floor and the largest holds 1.02 - 1.04 %, 5.3 - 5.4 mean
+    tiles (5.6 - 5.9 at 96 runs); a flat 1 % is 5.2 mean tiles there and does not hold."""
+    from evidence_amd import draws
+    from test_gpu_merge import _wide
+    logl, birth, run_start = _wide(n_runs=n_runs)
+    assert logl.size == n_runs * 22_000
+    _, _, logwt = merge.replicates_arrays(logl, birth, run_start, nsamples=2, seed=3, mode=mode, bootstrap=bootstrap,
+                                          return_logwt=True)
+    ntiles = -(-logl.size // 1024)
+    for s in range(2):
+        m = draws.fixed_point(logwt[s])
+        share = np.add.reduceat(m, np.arange(0, m.size, 1024)).astype(np.float64) / float(m.sum(dtype=np.int64))
+        assert share.size == ntiles
+        print(mode, bootstrap, s, "rows with mass", int(np.count_nonzero(m)), "of", m.size, " tiles above the floor",
+              int(np.count_nonzero(share >= 0.1 / ntiles)), "of", ntiles, " largest tile", float(share.max()))
+        assert np.count_nonzero(share >= 0.1 / ntiles) >= 0.95 * ntiles
+        assert share.max() <= 0.01 * 2063 / ntiles
+
+
 def test_refusals():
     logl, birth, run_start = _arrays(_ragged(4))
     with pytest.raises(ValueError, match="birth"):
