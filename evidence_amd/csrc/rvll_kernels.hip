@@ -409,6 +409,27 @@ void debug_eval_kernel(int op, const double* x, const double* y, long long n, do
         case 17: { double v = a; for (int k = 0; k < 1000; ++k) { sincos_dd_table(DD{v, 1e-20}, s, c); v = 0.7 * s + 1e-3 * c; } r = v; break; }
         case 18: { double v = a; for (int k = 0; k < 1000; ++k) { sincos_dd_kernel(DD{v, 1e-20}, s, c); v = 0.7 * s + 1e-3 * c; } r = v; break; }
         case 19: { double v = a; for (int k = 0; k < 1000; ++k) { sincos_any(v, s, c); v = v * 1.0000001 + s * 1e-3; } r = v; break; }
+        // the primitives beyond sincos_f64's reach and the fp32 layer of the reduced-precision modes (tests/test_gpu_math.py);
+        // floats travel as doubles: cast in, widened out
+        case 22: sincos_any(a, s, c); r = s; break;
+        case 23: sincos_any(a, s, c); r = c; break;
+        case 24: case 25: {                              // reduce_huge: r, and q (mod 4) as a double; its domain is |x| >= 2^-10, finite
+            r = NAN;
+            if (fabs(a) >= 0x1p-10 && fabs(a) < __builtin_inf()) { double rr; uint32_t q; reduce_huge(a, rr, q); r = op == 24 ? rr : (double)(q & 3u); }
+            break; }
+        case 26: case 27: { float sf, cf; sincos_f32((float)a, sf, cf); r = (double)(op == 26 ? sf : cf); break; }
+        case 28: case 29: case 30: case 31: {            // the packed pair on (x, y): s.x, s.y, c.x, c.y
+            f32x2 sf, cf;
+            sincos_f32x2(f32x2{(float)a, (float)b}, sf, cf);
+            r = (double)(op == 28 ? sf.x : op == 29 ? sf.y : op == 30 ? cf.x : cf.y);
+            break; }
+        case 32: r = (double)reduce_2pi_to_f32(a); break;
+        case 33: r = (double)div_f32((float)a, (float)b); break;
+        case 34: case 35: {                              // the packed quotient of (x, 3 x) by (y, 2 - y): .x, .y
+            const float nf = (float)a, df = (float)b;
+            const f32x2 qf = div_f32x2(f32x2{nf, 3.0f * nf}, f32x2{df, 2.0f - df});
+            r = (double)(op == 34 ? qf.x : qf.y);
+            break; }
         default: r = NAN; break;
         }
         out[i] = r;

@@ -192,8 +192,9 @@ static const uint64_t kTwoOverPiBits[21] = {
     0xef2f118b5a0a6d1full, 0x6d367ecf27cb09b7ull, 0x4f463f669e5fea2dull, 0x7527bac7ebe5f17bull,
     0x3d0739f78a5292eaull, 0x6bfb5fb11f8d5d08ull, 0x56033046fc7b6babull, 0xf0cfbc209af4361dull};
 
-constexpr double kSincosFastMax = 1125899906842624.0;   // 2^50: below, sincos_f64's own reduction (exact first step, second
-                                                        // constant good to 2^-60 up to there); from here on, reduce_huge
+constexpr double kSincosFastMax = 1125899906842624.0;   // 2^50: below, sincos_f64's own reduction (exact first step; measured
+                                                        // <= 1.2 * 2^-53 up to 2^49, up to 4.7 * 2^-53 in [2^49, 2^50), where the
+                                                        // rounding of 2/pi moves k: see above sincos_any); from here on, reduce_huge
 constexpr int    kSafeSteps = 8;                        // a Newton iterate cannot pass 2^50 before its 8th step (rvll_tile.h)
 constexpr double kExcursionM = 281474976710656.0;       // 2^48
 constexpr double kLongSolveEcc = 0.9;                   // a planet at or above it may hold a wandering solve: its point goes first
@@ -246,7 +247,12 @@ RVLL_HD void reduce_huge(double x, double& r, uint32_t& q)
     r = neg ? -rr : rr;
 }
 
-// sin and cos of any finite x (inf / nan: nan, like libm): the fast reduction below 2^50, the long one beyond
+// sin and cos of any finite x (inf / nan: nan, like libm): the fast reduction below 2^50, the long one beyond.
+// Below 2^50 these are sincos_f64's very bits (the shortcut loop and this routine share a tile on that), so its error is this
+// routine's there: against mpmath <= 1.2 * 2^-53 in every band up to 2^49, and up to 4.7 * 2^-53 in [2^49, 2^50) — the double
+// that holds 2/pi is off by 3.9e-17, which moves x * 2/pi by up to 0.044 there, k is then the wrong neighbour, |r| reaches
+// 0.85 and the minimax kernels are past their interval.  The long route is good to 1.2 * 2^-53 everywhere.  No solve's result
+// hangs on that band: an iterate that gets there wanders, and a wandering solve is redone with sincos_cr.
 RVLL_HD void sincos_any(double x, double& s_out, double& c_out, const SincosConsts& k)
 {
     if (__builtin_fabs(x) < kSincosFastMax) { sincos_f64(x, s_out, c_out, k); return; }
@@ -644,13 +650,15 @@ RVLL_HD void quadrant_f32(float sr, float cr, uint32_t uq, float& s_out, float& 
 // ---- fp32 pieces of the reduced-precision modes (RVLL_PREC_MIXED / RVLL_PREC_FP32) ----------
 // sin and cos of a float in roughly [-8, 8] (a mean anomaly already reduced to [-pi, pi] in fp64,
 // plus Newton steps): one Cody-Waite step to [-pi/4, pi/4], degree-7/8 minimax kernels
-// (coefficients: Sun/FreeBSD k_sinf.c, k_cosf.c), ~1 ulp(float).
+// (coefficients: Sun/FreeBSD k_sinf.c, k_cosf.c).  pi/2 is split as float(pi/2) and its complement, both exact floats
+// (FreeBSD's 25-bit pio2_1 is made for double arithmetic: as a float it is a tie, and the pair then misses pi/2 by an ulp of 1
+// per quadrant passed).  Measured over [-8, 8]: sin 1.05, cos 1.24 * 2^-24 absolute (tests/test_gpu_math.py).
 RVLL_HD void sincos_f32(float x, float& s_out, float& c_out)
 {
     const float fk = __builtin_rintf(x * 6.36619772367581382433e-01f);
     const int q = (int)fk;
-    float r = __builtin_fmaf(-fk, 1.5707963109016418e+00f, x);       // pi/2 high part (24 bits)
-    r = __builtin_fmaf(-fk, 1.5893254773528196e-08f, r);              // pi/2 - high
+    float r = __builtin_fmaf(-fk, 1.5707963705062866e+00f, x);       // float(pi/2)
+    r = __builtin_fmaf(-fk, -4.371138828673793e-08f, r);              // pi/2 - float(pi/2)
     const float z = r * r;
     float ps = __builtin_fmaf(z, 2.7183114939898219064e-06f, -1.9839334836096632576e-04f);
     ps = __builtin_fmaf(z, ps, 8.3333293858894631756e-03f);
@@ -663,7 +671,9 @@ RVLL_HD void sincos_f32(float x, float& s_out, float& c_out)
     quadrant_f32(sr, cr, (uint32_t)q, s_out, c_out);
 }
 
-// x reduced to [-pi, pi] in fp64 (two-constant Cody-Waite on 2*pi), returned as float.
+// x reduced to [-pi, pi] in fp64 (two-constant Cody-Waite on 2*pi), returned as float.  INV_TWOPI is off by 9.84e-18: next to
+// a half-integer of x / (2 pi) the other neighbour is taken, and r, x modulo 2 pi all the same, lies beyond pi by up to
+// 2 pi |x| 9.84e-18 (0.017 at the 2^48 the tile admits); sincos_f32 takes [-8, 8].
 RVLL_HD float reduce_2pi_to_f32(double x)
 {
     constexpr double INV_TWOPI = 1.59154943091895335769e-01;
@@ -703,8 +713,8 @@ RVLL_HD void sincos_f32x2(f32x2 x, f32x2& s_out, f32x2& c_out)
     const f32x2 t = x * splat2(6.36619772367581382433e-01f);
     const f32x2 fk = {__builtin_rintf(t.x), __builtin_rintf(t.y)};
     const int q0 = (int)fk.x, q1 = (int)fk.y;
-    f32x2 r = fma2(-fk, splat2(1.5707963109016418e+00f), x);
-    r = fma2(-fk, splat2(1.5893254773528196e-08f), r);
+    f32x2 r = fma2(-fk, splat2(1.5707963705062866e+00f), x);
+    r = fma2(-fk, splat2(-4.371138828673793e-08f), r);
     const f32x2 z = r * r;
     f32x2 ps = fma2(z, splat2(2.7183114939898219064e-06f), splat2(-1.9839334836096632576e-04f));
     ps = fma2(z, ps, splat2(8.3333293858894631756e-03f));

@@ -269,6 +269,12 @@ struct ItemCtx {
     int* pflags;          // per-point flag bits (RVLL_FLAG_WANDERED is set from the solver's second loop)
 };
 
+// A root of Kepler's equation lies within e < 1 of M: E - M = e sin E.  A float iterate that stops moving anywhere else has not
+// settled: thrown out to 1e5 .. 1e12 at the eccentricity clamp, beyond what sincos_f32's one-step reduction takes, it meets
+// polynomial values of 1e20 and more in f' = 1 - e cos E, its step f / f' vanishes, and |dE| <= tol holds at a nonsense E
+// (5e-4 of the solves at e = 0.99 with M uniform; tests/test_gpu_math.py).  NaN-safe like every stop test of these loops: a
+// non-finite iterate is astray.  Both the solve that has not settled and the one that is astray are done in double.
+__device__ __forceinline__ bool f32_astray(float E, float Mf, float tolf) { return !(fabsf(E - Mf) <= 1.0f + tolf); }
 
 // One (point, epoch) item: returns res^2 / (2 var) (the ln sqrt(var) of rvmodel:80 is summed per point by tile_logdet).
 // FAILCHECK: honour the itmax marks of earlier solves (nu = 0 from the first failing epoch of that planet on).  The
@@ -418,11 +424,11 @@ __device__ __forceinline__ double eval_item(const LoglikeArgs& a, const ItemCtx&
                     dE = En - E;
                     E = En;
                     ++steps;
-                } while (fabsf(dE) > tolf && steps < a.itmax && steps < kF32Steps);
-                if (fabsf(dE) > tolf && steps < a.itmax) {
-                    // not settled after kF32Steps: at the eccentricity clamp the iteration wanders far outside what a
-                    // float (or its one-step reduction) can follow — such a solve is done in double from the start,
-                    // as the parity mode does it (rare: cfg3's priors, 0.01 % of the waves)
+                } while (!(fabsf(dE) <= tolf) && steps < a.itmax && steps < kF32Steps);     // (NaN-safe: a non-finite step is "not settled")
+                if ((!(fabsf(dE) <= tolf) || f32_astray(E, Mf, tolf)) && steps < a.itmax) {
+                    // not settled after kF32Steps, or "settled" where no root can be (f32_astray): at the eccentricity clamp
+                    // the iteration wanders far outside what a float (or its one-step reduction) can follow — such a solve
+                    // is done in double from the start, as the parity mode does it (rare: cfg3's priors, 0.01 % of the waves)
                     double Ed = M, sd, cd, dd;
                     const SincosConsts kc = sincos_consts();
                     steps = 0;
@@ -575,13 +581,14 @@ __device__ __forceinline__ void eval_item_pair(const LoglikeArgs& a, const ItemC
             dE = En - E;
             E = En;
             ++steps;
-            more = __builtin_amdgcn_ballot_w64(fabsf(dE.x) > tolf.x || fabsf(dE.y) > tolf.y) != 0;
+            more = __builtin_amdgcn_ballot_w64(!(fabsf(dE.x) <= tolf.x) || !(fabsf(dE.y) <= tolf.y)) != 0;
         };
         do newton(); while (more && steps < kSafeSteps);
         const f32x2 dE8 = dE;                 // every item settled: within tol; else the step at kSafeSteps (0.01 % of the waves)
         if (__builtin_expect(more, 0)) { do newton(); while (more && steps < kF32Steps); }
-        const bool lateA = fabsf(dE8.x) > tolf.x, lateB = fabsf(dE8.y) > tolf.y;      // more than kSafeSteps steps: WANDERED
-        const bool movA = fabsf(dE.x) > tolf.x, movB = fabsf(dE.y) > tolf.y;
+        // (every test NaN-safe: a non-finite step counts as moving, and the item is solved in double)
+        const bool lateA = !(fabsf(dE8.x) <= tolf.x), lateB = !(fabsf(dE8.y) <= tolf.y);      // more than kSafeSteps steps: WANDERED
+        const bool movA = !(fabsf(dE.x) <= tolf.x) || f32_astray(E.x, Mf.x, tolf.x), movB = !(fabsf(dE.y) <= tolf.y) || f32_astray(E.y, Mf.y, tolf.y);
         // the model term of both from the packed iterate: (s, c) are at the iterate before the last step, and that step is within
         // tol for every item that goes on from here — rotated by it (h^3 / 6 <= 2e-10 dropped) instead of a third reduction
         if (a.tol <= 1e-3) {

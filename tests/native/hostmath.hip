@@ -27,6 +27,31 @@ HM void hm_sincos_long(const double* x, long n, double* s, double* c) {
         s[i] = ((q & 2u) ? -a : a) * (x[i] < 0 ? -1. : 1.);
         c[i] = ((q + 1u) & 2u) ? -b : b;
     } }
+// reduce_huge by itself (|x| >= 2^-10, finite; nan elsewhere): r, and q mod 4 as a double
+HM void hm_reduce_huge(const double* x, long n, double* r, double* q) {
+    for (long i = 0; i < n; ++i) {
+        r[i] = q[i] = __builtin_nan("");
+        if (!(__builtin_fabs(x[i]) >= 0x1p-10 && __builtin_fabs(x[i]) < __builtin_inf())) continue;
+        uint32_t qq; rvll::reduce_huge(x[i], r[i], qq); q[i] = (double)(qq & 3u);
+    } }
+// the fp32 layer of the reduced-precision modes; floats travel as doubles: cast in, widened out
+HM void hm_sincos_f32(const double* x, long n, double* s, double* c) {
+    for (long i = 0; i < n; ++i) { float sf, cf; rvll::sincos_f32((float)x[i], sf, cf); s[i] = sf; c[i] = cf; } }
+HM void hm_sincos_f32x2(const double* x, const double* y, long n, double* sx, double* sy, double* cx, double* cy) {
+    for (long i = 0; i < n; ++i) {
+        rvll::f32x2 sf, cf;
+        rvll::sincos_f32x2(rvll::f32x2{(float)x[i], (float)y[i]}, sf, cf);
+        sx[i] = sf.x; sy[i] = sf.y; cx[i] = cf.x; cy[i] = cf.y;
+    } }
+HM void hm_reduce_2pi_to_f32(const double* x, long n, double* out) { for (long i = 0; i < n; ++i) out[i] = rvll::reduce_2pi_to_f32(x[i]); }
+HM void hm_div_f32(const double* a, const double* b, long n, double* out) { for (long i = 0; i < n; ++i) out[i] = rvll::div_f32((float)a[i], (float)b[i]); }
+// the packed quotient of (a, 3 a) by (b, 2 - b), as debug_eval 34 / 35 form it
+HM void hm_div_f32x2(const double* a, const double* b, long n, double* qx, double* qy) {
+    for (long i = 0; i < n; ++i) {
+        const float nf = (float)a[i], df = (float)b[i];
+        const rvll::f32x2 q = rvll::div_f32x2(rvll::f32x2{nf, 3.0f * nf}, rvll::f32x2{df, 2.0f - df});
+        qx[i] = q.x; qy[i] = q.y;
+    } }
 HM void hm_ndtri(const double* p, long n, double* out) { for (long i = 0; i < n; ++i) out[i] = rvll::ndtri_f64(p[i]); }
 HM void hm_ndtri_cephes(const double* p, long n, double* out) { for (long i = 0; i < n; ++i) out[i] = rvll::ndtri_cephes(p[i]); }
 HM void hm_beta_ppf(const double* q, long n, double a, double b, double lbeta, double* out) { for (long i = 0; i < n; ++i) out[i] = rvll::beta_ppf(q[i], a, b, lbeta); }

@@ -18,11 +18,13 @@ def _run(w, theta, precision):
 
 # (max, median) of the relative log-L error against the fp64 path, per config and mode: at most 5x what was measured on
 # the MI355X for these very samples (profiles/DESIGN_history_r1_r3.md §4 table; max 1.2e-7 / 1.4e-7 / 9.2e-8 for cfg2 / 3 / 5, medians 2.0e-10 ..
-# 3.5e-8), so a regression by an order of magnitude fails
+# 3.5e-8), so a regression by an order of magnitude fails.  With sincos_f32's pi/2 split exact in float the maxima of cfg2 and
+# cfg5 fell (1.20e-7 / 1.20e-7 -> 1.03e-7 / 9.93e-8 and 9.63e-8 / 9.99e-8 -> 6.57e-8 / 6.38e-8) and their bounds with them, by the
+# same rule; cfg3's single worst sample moved the other way (1.49e-7 / 1.75e-7 -> 1.72e-7 / 1.85e-7): its bounds stay
 BOUNDS = {
-    (2, "mixed"): (6e-7, 1.0e-9), (2, "fp32"): (6e-7, 1.8e-7),
+    (2, "mixed"): (5.2e-7, 1.0e-9), (2, "fp32"): (5.0e-7, 1.8e-7),
     (3, "mixed"): (7e-7, 1.6e-8), (3, "fp32"): (7.5e-7, 1.7e-7),
-    (5, "mixed"): (4.6e-7, 1.2e-8), (5, "fp32"): (4.6e-7, 5.5e-8),
+    (5, "mixed"): (3.3e-7, 1.2e-8), (5, "fp32"): (3.2e-7, 5.5e-8),
 }
 
 

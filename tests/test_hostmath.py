@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import golden
+import math_cases as mc
 import prior_cases as pc
 
 HERE = Path(__file__).resolve().parent
@@ -142,27 +143,21 @@ def test_sincos_of_any_finite_double(hm):
     """sincos_any (rvll_math.h): the short reduction up to 2^50, the long (Payne - Hanek) one beyond, against glibc, which
     reduces every argument exactly: <= 1.5 ulp of 1 over random arguments up to 1e300, at exact powers of two, around the
     switch at 2^50, and at the doubles closest to multiples of pi/2 (where a short reduction loses everything) with their
-    RELATIVE accuracy kept; the long reduction by itself is also checked from 1 upwards, where the short one is valid too."""
-    rng = np.random.default_rng(12)
-    x = np.concatenate([
-        rng.uniform(-1, 1, 20000) * 10.0 ** rng.uniform(0, 300, 20000),
-        rng.uniform(-1, 1, 20000) * 2.0 ** rng.uniform(28, 56, 20000),
-        2.0 ** np.arange(0, 1024), -(2.0 ** np.arange(0, 1024)),
-        2.0 ** 50 + np.arange(-64, 65) * 0.25,
-        np.array([6381956970095103.0 * 2.0 ** 797, 5319372648326541416707072.0, 1e22, 2.343e22, -1.03e18]),
-        rng.integers(1, 2 ** 22, 5000) * np.pi,                      # the doubles next to multiples of pi: sin ~ 1e-10
-        rng.integers(1, 2 ** 22, 5000) * np.pi + np.pi / 2,          # ... and cos
-    ])
-    rs = np.array([math.sin(v) for v in x])
-    rc = np.array([math.cos(v) for v in x])
+    RELATIVE accuracy kept; the long reduction by itself is also checked from 1 upwards, where the short one is valid too.
+    [2^49, 2^50), the top of the short reduction, is weighed with 2e4 arguments of its own: the rounding of the 2/pi constant
+    costs the short route up to 4.2 * 2^-53 there (math_cases.HOST_TOP_BAND), and those arguments are held to that figure."""
+    x, band = mc.any_vector()
+    rs, rc = mc.any_reference()
+    assert band.sum() >= 20000 and np.all((np.abs(x[band]) >= 2.0 ** 49) & (np.abs(x[band]) < 2.0 ** 50))
     ulp = 2.0 ** -52
+    short = mc.any_bound()                                  # 1.5 ulp, and the measured figure of [2^49, 2^50) on the band's vector
     for fn, sel in (("hm_sincos_any", np.ones(x.size, bool)), ("hm_sincos_long", np.abs(x) >= 1.0)):
         xs = np.ascontiguousarray(x[sel])
-        s, c = np.empty_like(xs), np.empty_like(xs)
-        getattr(hm, fn)(xs.ctypes.data_as(dp), C.c_long(xs.size), s.ctypes.data_as(dp), c.ctypes.data_as(dp))
+        s, c = mc.host_call(hm, fn, [xs], 2)
+        bound = short[sel] if fn == "hm_sincos_any" else 1.5 * ulp      # the long reduction needs no allowance in the band
         es, ec = np.abs(s - rs[sel]), np.abs(c - rc[sel])
-        assert es.max() <= 1.5 * ulp, (fn, float(es.max() / ulp), float(xs[es.argmax()]))
-        assert ec.max() <= 1.5 * ulp, (fn, float(ec.max() / ulp), float(xs[ec.argmax()]))
+        assert np.all(es <= bound), (fn, float(np.max(es / bound)), float(xs[np.argmax(es / bound)]))
+        assert np.all(ec <= bound), (fn, float(np.max(ec / bound)), float(xs[np.argmax(ec / bound)]))
         if fn == "hm_sincos_long":                          # the long reduction keeps small results RELATIVELY accurate
             tiny = np.abs(rs[sel]) < 1e-6                   # (the short one is absolute: 2^-60 per quadrant passed)
             assert tiny.sum() > 100
@@ -214,3 +209,81 @@ def test_sincos_cr_is_correctly_rounded(hm):
     assert np.array_equal(s, want_s) and np.array_equal(c, want_c)
     glibc_off = np.mean((np.sin(x) != want_s) | (np.cos(x) != want_c))
     assert glibc_off < 0.02                                 # glibc itself: correctly rounded nearly always (it is what the oracle calls)
+
+
+# ---- sincos_f64 by band, the fp32 layer of the reduced-precision modes (the device side: tests/test_gpu_math.py) ----------------
+@pytest.mark.parametrize("band", mc.BANDS, ids=lambda b: f"2^{b[0]}-2^{b[1]}")
+def test_sincos_f64_by_band(hm, band):
+    """sincos_f64 from 2^14 up to its switch at 2^50, log-uniform arguments and the doubles next to multiples of pi/2, against
+    long-double libm: 1.5 * 2^-53 below 2^48; above, the measured figure of math_cases.HOST_TOP_BAND plus the reference's rounding."""
+    x = mc.band_vector(*band)
+    s, c = mc.host_call(hm, "hm_sincos", [x], 2)
+    rs, rc = mc.band_reference(*band)
+    es = float(np.max(np.abs(s.astype(np.longdouble) - rs))) / mc.ULP53
+    ec = float(np.max(np.abs(c.astype(np.longdouble) - rc))) / mc.ULP53
+    print(f"host sincos_f64 2^{band[0]}..2^{band[1]}: sin {es:.3f} cos {ec:.3f} (2^-53), n = {x.size}")
+    assert es <= mc.band_bound(band) and ec <= mc.band_bound(band), (band, es, ec)
+
+
+@pytest.mark.parametrize("band", sorted(mc.HOST_TOP_BAND), ids=lambda b: f"2^{b[0]}-2^{b[1]}")
+def test_sincos_f64_top_bands_against_mpmath(hm, band):
+    """Where math_cases.HOST_TOP_BAND comes from: the host build against mpmath (no rounding of the reference) on the band's own
+    vector.  The device test's bound is this figure plus half an ulp, so it must not drift from what it was recorded as."""
+    x = mc.band_vector(*band)
+    s, c = mc.host_call(hm, "hm_sincos", [x], 2)
+    es, ec = mc.err_vs_mpmath(x, s, c)
+    worst = max(es, ec) / mc.ULP53
+    print(f"host sincos_f64 2^{band[0]}..2^{band[1]} against mpmath: sin {es / mc.ULP53:.4f} cos {ec / mc.ULP53:.4f} (2^-53)")
+    assert mc.HOST_TOP_BAND[band] - 0.01 <= worst <= mc.HOST_TOP_BAND[band], (band, worst)
+
+
+def test_sincos_f32_accuracy(hm):
+    """sincos_f32 on 2e6 floats in [-8, 8] and every float within 4 ulps of k pi/2, |k| <= 5, against float64 libm:
+    1.5 * 2^-24 absolute (with the pi/2 split that is exact in float the emulation gives <= 1.24; the split this routine had
+    before, FreeBSD's 25-bit pio2_1, is a tie as a float and cost one ulp per quadrant passed: 4.6 / 5.2 on this vector)."""
+    x = mc.f32_vector()
+    s, c = mc.host_call(hm, "hm_sincos_f32", [x], 2)
+    rs, rc = mc.f32_reference()
+    es, ec = np.max(np.abs(s - rs)) / mc.ULP24, np.max(np.abs(c - rc)) / mc.ULP24
+    print(f"host sincos_f32: sin {es:.3f} cos {ec:.3f} (2^-24)")
+    assert es <= mc.SINCOS_F32_BOUND and ec <= mc.SINCOS_F32_BOUND, (float(es), float(ec))
+
+
+def test_sincos_f32x2_components_are_the_scalar_routine(hm):
+    x = mc.f32_vector()
+    y = np.ascontiguousarray(x[::-1])
+    s, c = mc.host_call(hm, "hm_sincos_f32", [x], 2)
+    sx, sy, cx, cy = mc.host_call(hm, "hm_sincos_f32x2", [x, y], 4)
+    assert np.array_equal(sx, s) and np.array_equal(cx, c) and np.array_equal(sy, s[::-1]) and np.array_equal(cy, c[::-1])
+
+
+def test_reduce_2pi_to_f32(hm):
+    """reduce_2pi_to_f32 against the reduction in mpmath rounded to float: |x| <= 2e4 dense and log-uniform to 2^48."""
+    x = mc.reduce_vector()
+    r, = mc.host_call(hm, "hm_reduce_2pi_to_f32", [x], 1)
+    over, at, rmax = mc.check_reduce_2pi(x, r)
+    assert rmax <= mc.R2PI_MAX, rmax
+    assert over <= 0, (over, at)
+
+
+def test_reduce_2pi_to_f32_where_the_constant_decides(hm):
+    """Next to half-integers of x / (2 pi) at large |x| the routine's 1 / (2 pi) picks the wrong neighbour: r is x modulo 2 pi all
+    the same, and beyond pi by no more than the constant's error allows (math_cases.reduce_edge_range)."""
+    x = mc.reduce_edge_vector()
+    r, = mc.host_call(hm, "hm_reduce_2pi_to_f32", [x], 1)
+    over, at, _ = mc.check_reduce_2pi(x, r)
+    assert over <= 0, (over, at)
+    assert np.all(np.abs(r) <= mc.reduce_edge_range(x)), float(np.max(np.abs(r)))
+    print(f"host reduce_2pi_to_f32 at the edge: max |r| = {np.abs(r).max():.6f}, {np.mean(np.abs(r) > mc.R2PI_MAX):.3f} beyond float(pi)")
+
+
+def test_div_f32_and_div_f32x2(hm):
+    """Within one float ulp of IEEE float division (the host build divides; the device: rcp to 1 ulp and one residual step)."""
+    n, d = mc.div_vector()
+    n0, n1, d0, d1 = mc.div_pair_operands()
+    q, = mc.host_call(hm, "hm_div_f32", [n, d], 1)
+    qx, qy = mc.host_call(hm, "hm_div_f32x2", [n, d], 2)
+    for got, nn, dd in ((q, n0, d0), (qx, n0, d0), (qy, n1, d1)):
+        off, share = mc.div_ulps_off(got, nn, dd)
+        assert off <= 1.0, off
+        assert share == 0.0          # the host build IS the IEEE division
