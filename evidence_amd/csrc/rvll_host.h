@@ -2,7 +2,9 @@
 // pointer, the error macro, and the helpers of rvll_api.hip the other units call.  Internal; not part of the ABI.
 //   rvll_api.hip        the ABI core: create / destroy, priors, resident and host-buffer batch calls, scalar-call server,
 //                       streamed host batches, curves, self tests
-//   rvll_walk_host.hip  the sampler's proposal step: the device walk in its forms, the resident live set (rvll_live_*)
+//   rvll_walk_host.hip  the sampler's proposal step: the device walk in its forms (rvll_slice_walk*)
+//   rvll_live_host.hip  the resident live set and ensemble (rvll_live_*, rvll_live_runs_*): the stages of a resident step
+//   rvll_step_groups.h  the walker groups of a resident ensemble step: index arithmetic without a HIP call
 //   rvll_comm.hip       multi-GPU: RCCL communicators, lanes, all-gathers
 //   rvll_cluster_host.hip  MLFriends clustering of many row sets (rvll_cluster_runs)
 //   rvll_region.hip     MLFriends region sampling (rvll_region_draw_runs): kernels and host side
@@ -37,6 +39,13 @@ int report_error(int code, const char* fmt, ...);
             return ::rvll::report_error(e_ == hipErrorOutOfMemory ? RVLL_E_NOMEM : RVLL_E_HIP, \
                         "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_),      \
                         __FILE__, __LINE__);                                        \
+    } while (0)
+
+// a host-unit call that has reported its own error: pass its code on
+#define RVLL_TRY(expr)                                                              \
+    do {                                                                            \
+        const int rc_ = (expr);                                                     \
+        if (rc_) return rc_;                                                        \
     } while (0)
 
 namespace rvll {
@@ -289,6 +298,30 @@ inline unsigned long long wrapped_mask(const int32_t* wrapped, int D)
     return m;
 }
 constexpr size_t kDownloadStagedMin = 32u << 20, kDeadStagedMin = 8u << 20;
+
+// rvll_walk_host.hip: what the resident live set (rvll_live_host.hip) needs of the walk
+// Run mode of a walk (rvll_slice_walk_runs): the walkers of several independent runs in one walk.  Every row's run is in
+// d_walk_run and its index inside the run in d_walk_wid (the random-number counter index the one-run walk of that run gives
+// it); per run lstar, seed and whitening factor are in d_run_lstar / d_run_seed / d_run_chol.  Every launch of the walk counts
+// the calls of each row in d_walk_cost (the single-kernel forms' per-row cost, the rounds step's per-walker count), and the
+// host adds them up per row: the calls of a run are then those its own walk would report, whichever forms the rows took.
+// With a per-run step-count table (rvll_slice_walk_runs_steps; nsteps != null, d_run_nsteps uploaded) the nsteps of the walk
+// is the largest count and a row stops after its run's own: the single-kernel forms read the table (WalkArgs::run_nsteps),
+// the rounds form, whose direction table has nsteps rows per walker, is not taken.
+struct RunWalk {
+    const int32_t* run;                // [K] host copy of d_walk_run
+    const int32_t* rid;                // [K] host copy of d_walk_wid
+    std::vector<long long> row_calls;  // [K] out: likelihood calls every row consumed
+    const int32_t* nsteps = nullptr;   // [R] or null: host copy of d_run_nsteps
+};
+int walk_reserve(rvll_handle* h, int64_t K);                 // device buffers of the walk for K rows (grown on demand)
+int runs_reserve(rvll_handle* h, int64_t K, int64_t R);      // ... in run mode, and the tables of R runs
+int walk_check_args(rvll_handle* h, int64_t K, int32_t nsteps, int32_t max_rounds, int64_t walker_base, const int32_t* wrapped);
+int walk_upload_frame(rvll_handle* h, const double* chol, const int32_t* wrapped);   // chol may be null (run mode); synchronises
+// the walk of the K rows in the walk's buffers (rw: run mode, else null); synchronises the compute stream
+int walk_core(rvll_handle* h, int64_t K, double lstar, int32_t nsteps, int32_t max_rounds, uint64_t seed, int64_t walker_base,
+              int64_t* ncalls, RunWalk* rw);
+int steps_range(const char* who, const int32_t* nsteps, int32_t n, int32_t* most, bool* uniform);
 
 }  // namespace host
 }  // namespace rvll

@@ -1,6 +1,6 @@
 // rvll_walk_host.hip — host side of the sampler's proposal step: the device-resident slice-sampling walk
-// in its forms (rvll_slice_walk) and the live set of nested sampling kept in HBM (rvll_live_*).  Entry points of include/rvll.h;
-// the kernels are in rvll_walk.hip, rvll_rounds.hip and rvll_live.hip.
+// in its forms (rvll_slice_walk*).  Entry points of include/rvll.h; the kernels are in rvll_walk.hip and rvll_rounds.hip.  The
+// live set of nested sampling kept in HBM (rvll_live_*) is rvll_live_host.hip, which walks through walk_core (rvll_host.h).
 #include <chrono>
 #include <thread>
 #include "rvll_host.h"
@@ -13,55 +13,6 @@ namespace {
 // the bound of the stepout walk's basis scratch (walk_core), in doubles: 512 MiB
 constexpr size_t kStepoutBasisMax = (size_t)1 << 26;
 
-// device buffers of the walk for K rows (grown on demand)
-int walk_reserve(rvll_handle* h, int64_t K)
-{
-    const size_t D = (size_t)h->L.ndim;
-    int rc = rvll_dev_reserve(h, K + rvll::kMaxPointsPerBlock);   // scratch rows (one tile per workgroup): d_theta, log-L / flags of lane 0
-    if (rc) return rc;
-    rc = sync_other_lanes(h);
-    if (rc) return rc;
-    if (K > h->walk_cap || !h->d_walk_chol) {
-        HIP_TRY(hipStreamSynchronize(h->compute));
-        dev_free(h->d_walk_u); dev_free(h->d_walk_theta); dev_free(h->d_walk_logl);
-        dev_free(h->d_walk_steps); dev_free(h->d_walk_wid); dev_free(h->d_walk_start);
-        dev_free(h->d_walk_cost); dev_free(h->d_walk_order); dev_free(h->d_walk_wflag);
-        h->walk_cap = 0;
-        const size_t cap = (size_t)std::max<long long>(K, 1024);
-        HIP_TRY(hipMalloc(&h->d_walk_u, sizeof(double) * D * cap));
-        HIP_TRY(hipMalloc(&h->d_walk_theta, sizeof(double) * D * cap));
-        HIP_TRY(hipMalloc(&h->d_walk_logl, sizeof(double) * cap));
-        HIP_TRY(hipMalloc(&h->d_walk_steps, sizeof(int32_t) * cap));
-        HIP_TRY(hipMalloc(&h->d_walk_wid, sizeof(int32_t) * cap));
-        HIP_TRY(hipMalloc(&h->d_walk_start, sizeof(int32_t) * cap));
-        HIP_TRY(hipMalloc(&h->d_walk_cost, sizeof(int32_t) * cap));
-        HIP_TRY(hipMalloc(&h->d_walk_order, sizeof(int32_t) * cap));
-        HIP_TRY(hipMalloc(&h->d_walk_wflag, sizeof(int32_t) * cap));
-        if (!h->d_walk_chol) {
-            HIP_TRY(hipMalloc(&h->d_walk_chol, sizeof(double) * D * D));
-            HIP_TRY(hipMalloc(&h->d_walk_wrapped, sizeof(int32_t) * D));
-            HIP_TRY(hipMalloc(&h->d_walk_ncalls, kWalkWords * sizeof(unsigned long long)));   // calls used, tile slots evaluated, diagnostic bins
-        }
-        h->walk_cap = (long long)cap;
-    }
-    return RVLL_OK;
-}
-
-// Run mode of a walk (rvll_slice_walk_runs): the walkers of several independent runs in one walk.  Every row's run is in
-// d_walk_run and its index inside the run in d_walk_wid (the random-number counter index the one-run walk of that run gives
-// it); per run lstar, seed and whitening factor are in d_run_lstar / d_run_seed / d_run_chol.  Every launch of the walk counts
-// the calls of each row in d_walk_cost (the single-kernel forms' per-row cost, the rounds step's per-walker count), and the
-// host adds them up per row: the calls of a run are then those its own walk would report, whichever forms the rows took.
-// With a per-run step-count table (rvll_slice_walk_runs_steps; nsteps != null, d_run_nsteps uploaded) the nsteps of the walk
-// is the largest count and a row stops after its run's own: the single-kernel forms read the table (WalkArgs::run_nsteps),
-// the rounds form, whose direction table has nsteps rows per walker, is not taken.
-struct RunWalk {
-    const int32_t* run;                // [K] host copy of d_walk_run
-    const int32_t* rid;                // [K] host copy of d_walk_wid
-    std::vector<long long> row_calls;  // [K] out: likelihood calls every row consumed
-    const int32_t* nsteps = nullptr;   // [R] or null: host copy of d_run_nsteps
-};
-
 // run mode: d_walk_cost [n] down and added to rw->row_calls (at rows[j], or at j when rows is null); synchronises the stream
 int run_calls_add(rvll_handle* h, RunWalk* rw, int64_t n, const int32_t* rows)
 {
@@ -69,87 +20,6 @@ int run_calls_add(rvll_handle* h, RunWalk* rw, int64_t n, const int32_t* rows)
     HIP_TRY(hipMemcpyAsync(c.data(), h->d_walk_cost, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, h->compute));
     HIP_TRY(hipStreamSynchronize(h->compute));
     for (int64_t j = 0; j < n; ++j) rw->row_calls[(size_t)(rows ? rows[j] : j)] += c[(size_t)j];
-    return RVLL_OK;
-}
-
-// the walk's buffers for K rows in run mode, and the tables of R runs (grown on demand)
-int runs_reserve(rvll_handle* h, int64_t K, int64_t R)
-{
-    const size_t D = (size_t)h->L.ndim;
-    int rc = walk_reserve(h, K);
-    if (rc) return rc;
-    hipStream_t st = h->compute;
-    if (K > h->runs_rows_cap) {
-        HIP_TRY(hipStreamSynchronize(st));
-        dev_free(h->d_walk_run);
-        h->runs_rows_cap = 0;
-        HIP_TRY(hipMalloc(&h->d_walk_run, sizeof(int32_t) * (size_t)h->walk_cap));
-        h->runs_rows_cap = h->walk_cap;
-    }
-    if (R > h->runs_cap) {
-        HIP_TRY(hipStreamSynchronize(st));
-        dev_free(h->d_run_lstar); dev_free(h->d_run_seed); dev_free(h->d_run_chol); dev_free(h->d_run_nsteps);
-        h->runs_cap = 0;
-        const size_t cap = (size_t)std::max<int64_t>(R, 64);
-        HIP_TRY(hipMalloc(&h->d_run_nsteps, sizeof(int32_t) * cap));
-        HIP_TRY(hipMalloc(&h->d_run_lstar, sizeof(double) * cap));
-        HIP_TRY(hipMalloc(&h->d_run_seed, sizeof(unsigned long long) * cap));
-        HIP_TRY(hipMalloc(&h->d_run_chol, sizeof(double) * D * D * cap));
-        h->runs_cap = (long long)cap;
-    }
-    return RVLL_OK;
-}
-
-// The whitening factor of the resident live set: the lower Cholesky - Banachiewicz factor of cov + 1e-14 on the diagonal (as
-// evidence_amd/nested.py adds), factor [D, D] zero above the diagonal.  Host arithmetic (19 x 19 at most in practice), shared by
-// rvll_live_step and rvll_live_runs_step so that the two cannot drift apart.  False: not positive definite.
-bool whitening_factor(const double* cov, size_t D, double* factor)
-{
-    std::fill(factor, factor + D * D, 0.);
-    for (size_t j = 0; j < D; ++j) {
-        for (size_t l = 0; l <= j; ++l) {
-            double sum = cov[j * D + l] + (j == l ? 1e-14 : 0.);
-            for (size_t m = 0; m < l; ++m) sum -= factor[j * D + m] * factor[l * D + m];
-            if (j == l) {
-                if (!(sum > 0.)) return false;
-                factor[j * D + j] = std::sqrt(sum);
-            } else {
-                factor[j * D + l] = sum / factor[l * D + l];
-            }
-        }
-    }
-    return true;
-}
-
-// room in the dead store for `add` more rows (grown to at least dead_n + 4 grow rows, the rows kept)
-int dead_reserve(rvll_handle* h, long long add, long long grow, const char* who)
-{
-    if (h->dead_n + add <= h->dead_cap) return RVLL_OK;
-    const size_t D = (size_t)h->L.ndim;
-    hipStream_t st = h->compute;
-    const long long cap = std::max<long long>(2 * h->dead_cap, h->dead_n + 4 * grow);
-    double *nt = nullptr, *nl = nullptr, *nb = nullptr;
-    HIP_TRY(hipMalloc(&nt, sizeof(double) * D * (size_t)cap));
-    {
-        hipError_t e = hipMalloc(&nl, sizeof(double) * (size_t)cap);
-        if (e == hipSuccess) e = hipMalloc(&nb, sizeof(double) * (size_t)cap);
-        if (e != hipSuccess) {
-            (void)hipFree(nt); if (nl) (void)hipFree(nl);
-            return report_error(e == hipErrorOutOfMemory ? RVLL_E_NOMEM : RVLL_E_HIP, "%s: dead store: %s", who, hipGetErrorString(e));
-        }
-    }
-    if (h->dead_n) {
-        hipError_t e = hipMemcpyAsync(nt, h->d_dead_theta, sizeof(double) * D * (size_t)h->dead_n, hipMemcpyDeviceToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(nl, h->d_dead_logl, sizeof(double) * (size_t)h->dead_n, hipMemcpyDeviceToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(nb, h->d_dead_birth, sizeof(double) * (size_t)h->dead_n, hipMemcpyDeviceToDevice, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) {
-            (void)hipFree(nt); (void)hipFree(nl); (void)hipFree(nb);
-            return report_error(RVLL_E_HIP, "%s: dead store: %s", who, hipGetErrorString(e));
-        }
-    }
-    dev_free(h->d_dead_theta); dev_free(h->d_dead_logl); dev_free(h->d_dead_birth);
-    h->d_dead_theta = nt; h->d_dead_logl = nl; h->d_dead_birth = nb; h->dead_cap = cap;
     return RVLL_OK;
 }
 
@@ -520,6 +390,70 @@ int walk_rounds(rvll_handle* h, int64_t K, double lstar, int32_t nsteps, int32_t
     h->walk_rounds_used = (int)std::min<long long>(rounds, 0x7fffffff);
     if (calls) *calls = total;
     if (slots) *slots = evaluated;
+    return RVLL_OK;
+}
+
+}  // namespace
+
+namespace rvll {
+namespace host {
+
+// device buffers of the walk for K rows (grown on demand)
+int walk_reserve(rvll_handle* h, int64_t K)
+{
+    const size_t D = (size_t)h->L.ndim;
+    RVLL_TRY(rvll_dev_reserve(h, K + rvll::kMaxPointsPerBlock));   // scratch rows (one tile per workgroup): d_theta, log-L / flags of lane 0
+    RVLL_TRY(sync_other_lanes(h));
+    if (K > h->walk_cap || !h->d_walk_chol) {
+        HIP_TRY(hipStreamSynchronize(h->compute));
+        dev_free(h->d_walk_u); dev_free(h->d_walk_theta); dev_free(h->d_walk_logl);
+        dev_free(h->d_walk_steps); dev_free(h->d_walk_wid); dev_free(h->d_walk_start);
+        dev_free(h->d_walk_cost); dev_free(h->d_walk_order); dev_free(h->d_walk_wflag);
+        h->walk_cap = 0;
+        const size_t cap = (size_t)std::max<long long>(K, 1024);
+        HIP_TRY(hipMalloc(&h->d_walk_u, sizeof(double) * D * cap));
+        HIP_TRY(hipMalloc(&h->d_walk_theta, sizeof(double) * D * cap));
+        HIP_TRY(hipMalloc(&h->d_walk_logl, sizeof(double) * cap));
+        HIP_TRY(hipMalloc(&h->d_walk_steps, sizeof(int32_t) * cap));
+        HIP_TRY(hipMalloc(&h->d_walk_wid, sizeof(int32_t) * cap));
+        HIP_TRY(hipMalloc(&h->d_walk_start, sizeof(int32_t) * cap));
+        HIP_TRY(hipMalloc(&h->d_walk_cost, sizeof(int32_t) * cap));
+        HIP_TRY(hipMalloc(&h->d_walk_order, sizeof(int32_t) * cap));
+        HIP_TRY(hipMalloc(&h->d_walk_wflag, sizeof(int32_t) * cap));
+        if (!h->d_walk_chol) {
+            HIP_TRY(hipMalloc(&h->d_walk_chol, sizeof(double) * D * D));
+            HIP_TRY(hipMalloc(&h->d_walk_wrapped, sizeof(int32_t) * D));
+            HIP_TRY(hipMalloc(&h->d_walk_ncalls, kWalkWords * sizeof(unsigned long long)));   // calls used, tile slots evaluated, diagnostic bins
+        }
+        h->walk_cap = (long long)cap;
+    }
+    return RVLL_OK;
+}
+
+// the walk's buffers for K rows in run mode, and the tables of R runs (grown on demand)
+int runs_reserve(rvll_handle* h, int64_t K, int64_t R)
+{
+    const size_t D = (size_t)h->L.ndim;
+    RVLL_TRY(walk_reserve(h, K));
+    hipStream_t st = h->compute;
+    if (K > h->runs_rows_cap) {
+        HIP_TRY(hipStreamSynchronize(st));
+        dev_free(h->d_walk_run);
+        h->runs_rows_cap = 0;
+        HIP_TRY(hipMalloc(&h->d_walk_run, sizeof(int32_t) * (size_t)h->walk_cap));
+        h->runs_rows_cap = h->walk_cap;
+    }
+    if (R > h->runs_cap) {
+        HIP_TRY(hipStreamSynchronize(st));
+        dev_free(h->d_run_lstar); dev_free(h->d_run_seed); dev_free(h->d_run_chol); dev_free(h->d_run_nsteps);
+        h->runs_cap = 0;
+        const size_t cap = (size_t)std::max<int64_t>(R, 64);
+        HIP_TRY(hipMalloc(&h->d_run_nsteps, sizeof(int32_t) * cap));
+        HIP_TRY(hipMalloc(&h->d_run_lstar, sizeof(double) * cap));
+        HIP_TRY(hipMalloc(&h->d_run_seed, sizeof(unsigned long long) * cap));
+        HIP_TRY(hipMalloc(&h->d_run_chol, sizeof(double) * D * D * cap));
+        h->runs_cap = (long long)cap;
+    }
     return RVLL_OK;
 }
 
@@ -914,41 +848,91 @@ int walk_upload_frame(rvll_handle* h, const double* chol, const int32_t* wrapped
     return RVLL_OK;
 }
 
-// N unit-cube rows -> prior transform -> log-L into the resident live buffers d_live_u / _theta / _logl (grown on demand), births
-// -inf;
-// logl_out [N] may be NULL.  Shared by the one-run live set and the ensemble; the caller keeps the state.
-int live_load(rvll_handle* h, const double* cube, int64_t N, double* logl_out)
+// a per-run step table nsteps [n] (rvll_slice_walk_runs_steps, rvll_live_runs_step_steps): every count in range; *most its largest,
+// *uniform whether all are equal (then the walk is the scalar one of `most` moves, every form open to it)
+int steps_range(const char* who, const int32_t* nsteps, int32_t n, int32_t* most, bool* uniform)
 {
-    const size_t D = (size_t)std::max(1, h->L.ndim);
-    int rc = rvll_dev_upload_cube(h, cube, N);
-    if (rc) return rc;
-    rc = rvll_dev_prior_loglike(h, N);
-    if (rc) return rc;
-    rc = rvll_dev_sync(h);
-    if (rc) return rc;
-    rc = use_device(h);                                  // (elements the table-only prior stage handed over are redone here)
-    if (rc) return rc;
-    if (N > h->live_cap) {
-        dev_free(h->d_live_u); dev_free(h->d_live_theta); dev_free(h->d_live_logl); dev_free(h->d_live_birth); dev_free(h->d_live_idx);
-        dev_free(h->d_sort_keys); dev_free(h->d_sort_rows);
-        h->live_cap = 0;
-        HIP_TRY(hipMalloc(&h->d_live_u, sizeof(double) * D * (size_t)N));
-        HIP_TRY(hipMalloc(&h->d_live_theta, sizeof(double) * D * (size_t)N));
-        HIP_TRY(hipMalloc(&h->d_live_logl, sizeof(double) * (size_t)N));
-        HIP_TRY(hipMalloc(&h->d_live_birth, sizeof(double) * (size_t)N));
-        HIP_TRY(hipMalloc(&h->d_live_idx, sizeof(int32_t) * 2 * (size_t)N));
-        HIP_TRY(hipMalloc(&h->d_sort_keys, sizeof(unsigned long long) * 2 * (size_t)N));
-        HIP_TRY(hipMalloc(&h->d_sort_rows, sizeof(int32_t) * (size_t)N));
-        h->live_cap = N;
+    if (n > 0 && !nsteps) return report_error(RVLL_E_INVALID, "%s: null step table", who);
+    int32_t hi = 0, lo = n > 0 ? nsteps[0] : 0;
+    for (int32_t r = 0; r < n; ++r) {
+        if (nsteps[r] < 0 || nsteps[r] >= (1 << 18))
+            return report_error(RVLL_E_INVALID, "%s: nsteps[%d] = %d out of range", who, (int)r, (int)nsteps[r]);
+        hi = std::max(hi, nsteps[r]);
+        lo = std::min(lo, nsteps[r]);
     }
-    if (!h->d_live_mom) HIP_TRY(hipMalloc(&h->d_live_mom, sizeof(double) * (rvll::moments_scratch_doubles((int)D) + D + D * D)));
+    *most = hi;
+    *uniform = lo == hi;
+    return RVLL_OK;
+}
+
+}  // namespace host
+}  // namespace rvll
+
+namespace {
+
+// the walkers' rows (unit cube, theta, log-L: K of each) from host buffers into the walk's, behind one another on the compute stream
+int walk_rows_upload(rvll_handle* h, const double* cube, const double* theta, const double* logl, int64_t K)
+{
+    const size_t D = (size_t)h->L.ndim;
     hipStream_t st = h->compute;
-    HIP_TRY(hipMemcpyAsync(h->d_live_u, h->d_cube, sizeof(double) * D * (size_t)N, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipMemcpyAsync(h->d_live_theta, h->d_theta, sizeof(double) * D * (size_t)N, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipMemcpyAsync(h->d_live_logl, h->d_logL2[h->logl_last], sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(rvll::launch_fill(h->d_live_birth, N, -INFINITY, st));       // drawn from the whole prior: born at -inf
-    if (logl_out) HIP_TRY(hipMemcpyAsync(logl_out, h->d_live_logl, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h->d_walk_u, cube, sizeof(double) * D * (size_t)K, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(h->d_walk_theta, theta, sizeof(double) * D * (size_t)K, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(h->d_walk_logl, logl, sizeof(double) * (size_t)K, hipMemcpyHostToDevice, st));
+    return RVLL_OK;
+}
+
+// ... and back to the host buffers; synchronises the stream
+int walk_rows_download(rvll_handle* h, double* cube, double* theta, double* logl, int64_t K)
+{
+    const size_t D = (size_t)h->L.ndim;
+    hipStream_t st = h->compute;
+    HIP_TRY(hipMemcpyAsync(cube, h->d_walk_u, sizeof(double) * D * (size_t)K, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(theta, h->d_walk_theta, sizeof(double) * D * (size_t)K, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(logl, h->d_walk_logl, sizeof(double) * (size_t)K, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
+    return RVLL_OK;
+}
+
+// rvll_slice_walk_runs (steps = null: every run makes nsteps moves) and rvll_slice_walk_runs_steps (steps [R]: run r makes
+// steps[r]; nsteps is their largest)
+int slice_walk_runs_impl(rvll_handle* h, double* cube, double* theta, double* logl, const int64_t* run_start, int32_t R,
+                         const double* lstar, const double* chol, const uint64_t* seed, const int32_t* wrapped,
+                         const int32_t* steps, int32_t nsteps, int32_t max_rounds, int64_t* ncalls)
+{
+    RVLL_TRY(use_device(h));
+    if (R < 0 || (R > 0 && !run_start)) return report_error(RVLL_E_INVALID, "rvll_slice_walk_runs: bad run table");
+    if (ncalls) for (int32_t r = 0; r < R; ++r) ncalls[r] = 0;
+    if (R > 0 && run_start[0] != 0) return report_error(RVLL_E_INVALID, "rvll_slice_walk_runs: run_start[0] must be 0");
+    for (int32_t r = 0; r < R; ++r)
+        if (run_start[r + 1] < run_start[r]) return report_error(RVLL_E_INVALID, "rvll_slice_walk_runs: run_start decreases at run %d", (int)r);
+    const int64_t K = R > 0 ? run_start[R] : 0;
+    RVLL_TRY(walk_check_args(h, K, nsteps, max_rounds, 0, wrapped));
+    if (K == 0 || nsteps == 0) return RVLL_OK;
+    if (!cube || !theta || !logl || !lstar || !chol || !seed) return report_error(RVLL_E_INVALID, "null buffer");
+    {
+        const char* e = getenv("RVLL_WALK_ROWS");
+        if (e && atoi(e) >= 1) return report_error(RVLL_E_UNSUPPORTED, "rvll_slice_walk_runs: the rows form (RVLL_WALK_ROWS) has no run mode");
+    }
+    const size_t D = (size_t)h->L.ndim;
+    RVLL_TRY(runs_reserve(h, K, R));
+    hipStream_t st = h->compute;
+    std::vector<int32_t> run((size_t)K), rid((size_t)K);
+    for (int32_t r = 0; r < R; ++r)
+        for (int64_t i = run_start[r]; i < run_start[r + 1]; ++i) { run[(size_t)i] = r; rid[(size_t)i] = (int32_t)(i - run_start[r]); }
+    RVLL_TRY(walk_rows_upload(h, cube, theta, logl, K));
+    HIP_TRY(hipMemcpyAsync(h->d_walk_run, run.data(), sizeof(int32_t) * (size_t)K, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(h->d_walk_wid, rid.data(), sizeof(int32_t) * (size_t)K, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(h->d_run_lstar, lstar, sizeof(double) * (size_t)R, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(h->d_run_seed, seed, sizeof(uint64_t) * (size_t)R, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(h->d_run_chol, chol, sizeof(double) * D * D * (size_t)R, hipMemcpyHostToDevice, st));
+    if (steps) HIP_TRY(hipMemcpyAsync(h->d_run_nsteps, steps, sizeof(int32_t) * (size_t)R, hipMemcpyHostToDevice, st));
+    RVLL_TRY(walk_upload_frame(h, nullptr, wrapped));       // (synchronises: the host tables above may go out of scope after it)
+    RunWalk rw{run.data(), rid.data(), std::vector<long long>((size_t)K, 0), steps};
+    RVLL_TRY(walk_core(h, K, 0., nsteps, max_rounds, 0, 0, nullptr, &rw));
+    RVLL_TRY(walk_rows_download(h, cube, theta, logl, K));
+    if (ncalls)
+        for (int32_t r = 0; r < R; ++r)
+            for (int64_t i = run_start[r]; i < run_start[r + 1]; ++i) ncalls[r] += rw.row_calls[(size_t)i];
     return RVLL_OK;
 }
 
@@ -960,91 +944,17 @@ int rvll_slice_walk(rvll_handle* h, double* cube, double* theta, double* logl, i
                     const double* chol, const int32_t* wrapped, int32_t nsteps, int32_t max_rounds,
                     uint64_t seed, int64_t walker_base, int64_t* ncalls)
 {
-    int rc = use_device(h);
-    if (rc) return rc;
+    RVLL_TRY(use_device(h));
     if (ncalls) *ncalls = 0;
-    rc = walk_check_args(h, K, nsteps, max_rounds, walker_base, wrapped);
-    if (rc) return rc;
+    RVLL_TRY(walk_check_args(h, K, nsteps, max_rounds, walker_base, wrapped));
     if (K == 0 || nsteps == 0) return RVLL_OK;
     if (!cube || !theta || !logl || !chol) return report_error(RVLL_E_INVALID, "null buffer");
-    const size_t D = (size_t)h->L.ndim;
-    rc = walk_reserve(h, K);
-    if (rc) return rc;
-    hipStream_t st = h->compute;
-    HIP_TRY(hipMemcpyAsync(h->d_walk_u, cube, sizeof(double) * D * (size_t)K, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(h->d_walk_theta, theta, sizeof(double) * D * (size_t)K, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(h->d_walk_logl, logl, sizeof(double) * (size_t)K, hipMemcpyHostToDevice, st));
-    rc = walk_upload_frame(h, chol, wrapped);
-    if (rc) return rc;
-    rc = walk_core(h, K, lstar, nsteps, max_rounds, seed, walker_base, ncalls);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(cube, h->d_walk_u, sizeof(double) * D * (size_t)K, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(theta, h->d_walk_theta, sizeof(double) * D * (size_t)K, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(logl, h->d_walk_logl, sizeof(double) * (size_t)K, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return RVLL_OK;
+    RVLL_TRY(walk_reserve(h, K));
+    RVLL_TRY(walk_rows_upload(h, cube, theta, logl, K));
+    RVLL_TRY(walk_upload_frame(h, chol, wrapped));
+    RVLL_TRY(walk_core(h, K, lstar, nsteps, max_rounds, seed, walker_base, ncalls));
+    return walk_rows_download(h, cube, theta, logl, K);
 }
-
-}  // extern "C"
-
-namespace {
-
-// rvll_slice_walk_runs (steps = null: every run makes nsteps moves) and rvll_slice_walk_runs_steps (steps [R]: run r makes
-// steps[r]; nsteps is their largest)
-int slice_walk_runs_impl(rvll_handle* h, double* cube, double* theta, double* logl, const int64_t* run_start, int32_t R,
-                         const double* lstar, const double* chol, const uint64_t* seed, const int32_t* wrapped,
-                         const int32_t* steps, int32_t nsteps, int32_t max_rounds, int64_t* ncalls)
-{
-    int rc = use_device(h);
-    if (rc) return rc;
-    if (R < 0 || (R > 0 && !run_start)) return report_error(RVLL_E_INVALID, "rvll_slice_walk_runs: bad run table");
-    if (ncalls) for (int32_t r = 0; r < R; ++r) ncalls[r] = 0;
-    if (R > 0 && run_start[0] != 0) return report_error(RVLL_E_INVALID, "rvll_slice_walk_runs: run_start[0] must be 0");
-    for (int32_t r = 0; r < R; ++r)
-        if (run_start[r + 1] < run_start[r]) return report_error(RVLL_E_INVALID, "rvll_slice_walk_runs: run_start decreases at run %d", (int)r);
-    const int64_t K = R > 0 ? run_start[R] : 0;
-    rc = walk_check_args(h, K, nsteps, max_rounds, 0, wrapped);
-    if (rc) return rc;
-    if (K == 0 || nsteps == 0) return RVLL_OK;
-    if (!cube || !theta || !logl || !lstar || !chol || !seed) return report_error(RVLL_E_INVALID, "null buffer");
-    {
-        const char* e = getenv("RVLL_WALK_ROWS");
-        if (e && atoi(e) >= 1) return report_error(RVLL_E_UNSUPPORTED, "rvll_slice_walk_runs: the rows form (RVLL_WALK_ROWS) has no run mode");
-    }
-    const size_t D = (size_t)h->L.ndim;
-    rc = runs_reserve(h, K, R);
-    if (rc) return rc;
-    hipStream_t st = h->compute;
-    std::vector<int32_t> run((size_t)K), rid((size_t)K);
-    for (int32_t r = 0; r < R; ++r)
-        for (int64_t i = run_start[r]; i < run_start[r + 1]; ++i) { run[(size_t)i] = r; rid[(size_t)i] = (int32_t)(i - run_start[r]); }
-    HIP_TRY(hipMemcpyAsync(h->d_walk_u, cube, sizeof(double) * D * (size_t)K, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(h->d_walk_theta, theta, sizeof(double) * D * (size_t)K, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(h->d_walk_logl, logl, sizeof(double) * (size_t)K, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(h->d_walk_run, run.data(), sizeof(int32_t) * (size_t)K, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(h->d_walk_wid, rid.data(), sizeof(int32_t) * (size_t)K, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(h->d_run_lstar, lstar, sizeof(double) * (size_t)R, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(h->d_run_seed, seed, sizeof(uint64_t) * (size_t)R, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(h->d_run_chol, chol, sizeof(double) * D * D * (size_t)R, hipMemcpyHostToDevice, st));
-    if (steps) HIP_TRY(hipMemcpyAsync(h->d_run_nsteps, steps, sizeof(int32_t) * (size_t)R, hipMemcpyHostToDevice, st));
-    rc = walk_upload_frame(h, nullptr, wrapped);       // (synchronises: the host tables above may go out of scope after it)
-    if (rc) return rc;
-    RunWalk rw{run.data(), rid.data(), std::vector<long long>((size_t)K, 0), steps};
-    rc = walk_core(h, K, 0., nsteps, max_rounds, 0, 0, nullptr, &rw);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(cube, h->d_walk_u, sizeof(double) * D * (size_t)K, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(theta, h->d_walk_theta, sizeof(double) * D * (size_t)K, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(logl, h->d_walk_logl, sizeof(double) * (size_t)K, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (ncalls)
-        for (int32_t r = 0; r < R; ++r)
-            for (int64_t i = run_start[r]; i < run_start[r + 1]; ++i) ncalls[r] += rw.row_calls[(size_t)i];
-    return RVLL_OK;
-}
-
-}  // namespace
-
-extern "C" {
 
 int rvll_slice_walk_runs(rvll_handle* h, double* cube, double* theta, double* logl, const int64_t* run_start, int32_t R,
                          const double* lstar, const double* chol, const uint64_t* seed, const int32_t* wrapped,
@@ -1057,873 +967,12 @@ int rvll_slice_walk_runs_steps(rvll_handle* h, double* cube, double* theta, doub
                                const double* lstar, const double* chol, const uint64_t* seed, const int32_t* wrapped,
                                const int32_t* nsteps, int32_t max_rounds, int64_t* ncalls)
 {
-    if (R > 0 && !nsteps) return report_error(RVLL_E_INVALID, "rvll_slice_walk_runs_steps: null step table");
-    int32_t most = 0, least = R > 0 ? nsteps[0] : 0;
-    for (int32_t r = 0; r < R; ++r) {
-        if (nsteps[r] < 0 || nsteps[r] >= (1 << 18))
-            return report_error(RVLL_E_INVALID, "rvll_slice_walk_runs_steps: nsteps[%d] = %d out of range", (int)r, (int)nsteps[r]);
-        most = std::max(most, nsteps[r]);
-        least = std::min(least, nsteps[r]);
-    }
+    int32_t most = 0;
+    bool uniform = true;
+    RVLL_TRY(steps_range("rvll_slice_walk_runs_steps", nsteps, R, &most, &uniform));
     // a uniform table is the scalar walk (every form open to it); otherwise the rows stop at their run's count
-    return slice_walk_runs_impl(h, cube, theta, logl, run_start, R, lstar, chol, seed, wrapped, least == most ? nullptr : nsteps,
-                                most, max_rounds, ncalls);
-}
-
-// ---- nested sampling with the live points resident on the device -------------------------------------------
-int rvll_live_init(rvll_handle* h, const double* cube, int64_t N, double* logl_out)
-{
-    int rc = use_device(h);
-    if (rc) return rc;
-    if (!h->have_priors) return report_error(RVLL_E_NOPRIORS, "rvll_set_priors has not been called");
-    if (N < 1 || N >= (1LL << 31) || !cube) return report_error(RVLL_E_INVALID, "rvll_live_init: bad arguments");
-    // a new run starts here: whatever fails below, no earlier run's live set is left looking valid (rvll_live_step and
-    // rvll_live_get refuse live_n = 0) — live_n is set again as the last thing, on success
-    h->live_n = 0;
-    h->dead_n = 0;
-    h->sorted_kdead = -1;
-    h->runs_R = 0;                                       // (and no ensemble's either)
-    h->cl_A = 0;
-    rc = live_load(h, cube, N, logl_out);
-    if (rc) return rc;
-    h->live_n = N;
-    h->dead_n = 0;
-    return RVLL_OK;
-}
-
-int rvll_live_step(rvll_handle* h, const int32_t* order, int64_t kdead, const int32_t* start, double lstar,
-                   const double* chol, const int32_t* wrapped, int32_t nsteps, int32_t max_rounds, uint64_t seed,
-                   int64_t walker_base, int64_t* ncalls, double* logl_new, double* chol_out)
-{
-    int rc = use_device(h);
-    if (rc) return rc;
-    if (ncalls) *ncalls = 0;
-    const int64_t N = h->live_n;
-    if (N < 1) return report_error(RVLL_E_INVALID, "rvll_live_init has not been called");
-    if (!start || !logl_new || kdead < 1 || kdead >= N) return report_error(RVLL_E_INVALID, "rvll_live_step: bad arguments");
-    rc = walk_check_args(h, kdead, nsteps, max_rounds, walker_base, wrapped);
-    if (rc) return rc;
-    const bool dev_order = order == nullptr;             // the order rvll_live_sort left on the device; start[] are ranks among the survivors
-    if (dev_order) {
-        if (h->sorted_kdead != kdead) return report_error(RVLL_E_INVALID, "rvll_live_step: order is NULL but no rvll_live_sort(kdead = %lld) precedes", (long long)kdead);
-        if (!(lstar == h->sorted_lstar)) return report_error(RVLL_E_INVALID, "rvll_live_step: lstar is not the one rvll_live_sort returned");
-        for (int64_t i = 0; i < kdead; ++i)
-            if (start[i] < 0 || start[i] >= N - kdead) return report_error(RVLL_E_INVALID, "rvll_live_step: start[%lld] is not a rank among the survivors", (long long)i);
-        h->sorted_kdead = -1;                            // (used up, whatever happens below: the step changes the rows)
-    }
-    for (int64_t i = 0; !dev_order && i < N; ++i)
-        if (order[i] < 0 || order[i] >= N) return report_error(RVLL_E_INVALID, "rvll_live_step: order[%lld] out of range", (long long)i);
-    if (!dev_order) {
-        // the dying rows are scattered into in parallel and appended to the dead store: a row listed twice would race and be counted twice
-        std::vector<uint64_t> seen(((size_t)N + 63) / 64, 0);
-        for (int64_t i = 0; i < kdead; ++i) {
-            uint64_t& word = seen[(size_t)order[i] >> 6];
-            const uint64_t bit = 1ull << (order[i] & 63);
-            if (word & bit) return report_error(RVLL_E_INVALID, "rvll_live_step: row %d is listed twice among the dying rows", (int)order[i]);
-            word |= bit;
-        }
-    }
-    for (int64_t i = 0; !dev_order && i < kdead; ++i)
-        if (start[i] < 0 || start[i] >= N) return report_error(RVLL_E_INVALID, "rvll_live_step: start[%lld] out of range", (long long)i);
-    const size_t D = (size_t)h->L.ndim;
-    const int Di = h->L.ndim;
-    rc = walk_reserve(h, kdead);
-    if (rc) return rc;
-    hipStream_t st = h->compute;
-    int32_t* d_order = h->d_live_idx;
-    int32_t* d_start = h->d_live_idx + h->live_cap;
-    if (dev_order) {
-        // d_order holds the device's own order; the ranks go up through the sort's row scratch and become rows on the device
-        HIP_TRY(hipMemcpyAsync(h->d_sort_rows, start, sizeof(int32_t) * (size_t)kdead, hipMemcpyHostToDevice, st));
-        HIP_TRY(rvll::launch_compose_index(d_order, kdead, h->d_sort_rows, kdead, d_start, st));
-    } else {
-        h->sorted_kdead = -1;
-        HIP_TRY(hipMemcpyAsync(d_order, order, sizeof(int32_t) * (size_t)N, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_start, start, sizeof(int32_t) * (size_t)kdead, hipMemcpyHostToDevice, st));
-    }
-    // the points that die (rows order[0 .. kdead)) go to the dead store before their rows are overwritten
-    rc = dead_reserve(h, kdead, kdead, "rvll_live_step");
-    if (rc) return rc;
-    HIP_TRY(rvll::launch_gather_rows(h->d_live_theta, d_order, kdead, Di, h->d_dead_theta + (size_t)h->dead_n * D, st));
-    HIP_TRY(rvll::launch_gather_rows(h->d_live_logl, d_order, kdead, 1, h->d_dead_logl + h->dead_n, st));
-    // (dead_n moves on when the step has succeeded, at the bottom: a step that fails below — a covariance that is not positive
-    // definite, a walk that fails — leaves the dead store as it was, so a retry does not append the same rows twice)
-    // whitening: the caller's factor, or the covariance of the surviving rows order[kdead .. N) summed on the device (in a
-    // fixed order) and factored here (19 x 19: host arithmetic; + 1e-14 on the diagonal as evidence_amd/nested.py adds)
-    std::vector<double> factor(D * D, 0.);
-    if (chol) {
-        memcpy(factor.data(), chol, sizeof(double) * D * D);
-    } else {
-        double* scratch = h->d_live_mom;
-        double* d_mean = scratch + rvll::moments_scratch_doubles(Di);
-        double* d_cov = d_mean + D;
-        HIP_TRY(rvll::launch_moments(h->d_live_u, d_order + kdead, N - kdead, Di, scratch, d_mean, d_cov, st));
-        std::vector<double> cov(D * D);
-        HIP_TRY(hipMemcpyAsync(cov.data(), d_cov, sizeof(double) * D * D, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (!whitening_factor(cov.data(), D, factor.data()))
-            return report_error(RVLL_E_INVALID, "rvll_live_step: the live points' covariance is not positive definite");
-    }
-    if (chol_out) memcpy(chol_out, factor.data(), sizeof(double) * D * D);
-    // the walkers start from rows start[0 .. kdead)
-    HIP_TRY(rvll::launch_gather_rows(h->d_live_u, d_start, kdead, Di, h->d_walk_u, st));
-    HIP_TRY(rvll::launch_gather_rows(h->d_live_theta, d_start, kdead, Di, h->d_walk_theta, st));
-    HIP_TRY(rvll::launch_gather_rows(h->d_live_logl, d_start, kdead, 1, h->d_walk_logl, st));
-    rc = walk_upload_frame(h, factor.data(), wrapped);
-    if (rc) return rc;
-    rc = walk_core(h, kdead, lstar, nsteps, max_rounds, seed, walker_base, ncalls);
-    if (rc) return rc;
-    // ... and their end points replace the dead rows, born at lstar (the dying rows' births go to the dead store first)
-    HIP_TRY(rvll::launch_births_step(d_order, kdead, kdead, nullptr, lstar, h->d_live_birth, h->d_dead_birth + h->dead_n, st));
-    HIP_TRY(rvll::launch_scatter_rows(h->d_walk_u, d_order, kdead, Di, h->d_live_u, st));
-    HIP_TRY(rvll::launch_scatter_rows(h->d_walk_theta, d_order, kdead, Di, h->d_live_theta, st));
-    HIP_TRY(rvll::launch_scatter_rows(h->d_walk_logl, d_order, kdead, 1, h->d_live_logl, st));
-    HIP_TRY(hipMemcpyAsync(logl_new, h->d_walk_logl, sizeof(double) * (size_t)kdead, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    h->dead_n += kdead;
-    return RVLL_OK;
-}
-
-int rvll_live_sort(rvll_handle* h, int64_t kdead, double* dead_logl, double* lstar, double* max_logl)
-{
-    int rc = use_device(h);
-    if (rc) return rc;
-    const int64_t N = h->live_n;
-    if (N < 1) return report_error(RVLL_E_INVALID, "rvll_live_init has not been called");
-    if (kdead < 1 || kdead >= N || !dead_logl || !lstar || !max_logl) return report_error(RVLL_E_INVALID, "rvll_live_sort: bad arguments");
-    h->sorted_kdead = -1;
-    hipStream_t st = h->compute;
-    const size_t need = rvll::sort_temp_bytes(N);
-    if (need > h->sort_temp_bytes) {
-        HIP_TRY(hipStreamSynchronize(st));
-        dev_free(h->d_sort_temp);
-        h->sort_temp_bytes = 0;
-        HIP_TRY(hipMalloc(&h->d_sort_temp, need));
-        h->sort_temp_bytes = need;
-    }
-    int32_t* d_order = h->d_live_idx;
-    HIP_TRY(rvll::launch_sort_logl(h->d_live_logl, N, h->d_sort_keys, h->d_sort_keys + h->live_cap, h->d_sort_rows, d_order,
-                                   h->d_sort_temp, h->sort_temp_bytes, st));
-    // the log-L of the kdead lowest, in order, and of the highest: gathered into the walk's log-L scratch, one download
-    rc = walk_reserve(h, kdead + 1);
-    if (rc) return rc;
-    HIP_TRY(rvll::launch_gather_rows(h->d_live_logl, d_order, kdead, 1, h->d_walk_logl, st));
-    HIP_TRY(rvll::launch_gather_rows(h->d_live_logl, d_order + (N - 1), 1, 1, h->d_walk_logl + kdead, st));
-    std::vector<double> got((size_t)kdead + 1);
-    HIP_TRY(hipMemcpyAsync(got.data(), h->d_walk_logl, sizeof(double) * ((size_t)kdead + 1), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    memcpy(dead_logl, got.data(), sizeof(double) * (size_t)kdead);
-    *lstar = got[(size_t)kdead - 1];
-    *max_logl = got[(size_t)kdead];
-    h->sorted_kdead = kdead;
-    h->sorted_lstar = *lstar;
-    return RVLL_OK;
-}
-
-int rvll_live_get(rvll_handle* h, double* cube, double* theta, double* logl)
-{
-    int rc = use_device(h);
-    if (rc) return rc;
-    if (h->live_n < 1) return report_error(RVLL_E_INVALID, "rvll_live_init has not been called");
-    const size_t D = (size_t)h->L.ndim, N = (size_t)h->live_n;
-    hipStream_t st = h->compute;
-    const bool staged = sizeof(double) * D * N >= kDownloadStagedMin;
-    if (cube && staged) { rc = download_rows(h, cube, h->d_live_u, sizeof(double) * D * N); if (rc) return rc; }
-    else if (cube) HIP_TRY(hipMemcpyAsync(cube, h->d_live_u, sizeof(double) * D * N, hipMemcpyDeviceToHost, st));
-    if (theta && staged) { rc = download_rows(h, theta, h->d_live_theta, sizeof(double) * D * N); if (rc) return rc; }
-    else if (theta) HIP_TRY(hipMemcpyAsync(theta, h->d_live_theta, sizeof(double) * D * N, hipMemcpyDeviceToHost, st));
-    if (logl) HIP_TRY(hipMemcpyAsync(logl, h->d_live_logl, sizeof(double) * N, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return RVLL_OK;
-}
-
-int rvll_live_dead(rvll_handle* h, int64_t* n_dead, double* theta, double* logl)
-{
-    int rc = use_device(h);
-    if (rc) return rc;
-    if (!n_dead) return report_error(RVLL_E_INVALID, "n_dead is null");
-    if (h->runs_R > 0) return report_error(RVLL_E_INVALID, "rvll_live_dead: the resident rows are an ensemble's (rvll_live_runs_dead)");
-    const int64_t have = h->dead_n, want = (theta || logl) ? std::min<int64_t>(*n_dead, have) : 0;
-    *n_dead = have;
-    const size_t D = (size_t)h->L.ndim;
-    hipStream_t st = h->compute;
-    if (want > 0 && theta && sizeof(double) * D * (size_t)want >= kDeadStagedMin) {
-        rc = download_rows(h, theta, h->d_dead_theta, sizeof(double) * D * (size_t)want);
-        if (rc) return rc;
-    } else if (want > 0 && theta) {
-        HIP_TRY(hipMemcpyAsync(theta, h->d_dead_theta, sizeof(double) * D * (size_t)want, hipMemcpyDeviceToHost, st));
-    }
-    if (want > 0 && logl) HIP_TRY(hipMemcpyAsync(logl, h->d_dead_logl, sizeof(double) * (size_t)want, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return RVLL_OK;
-}
-
-// ---- the resident ensemble: R independent live sets in one handle (rvll_live_runs_*) ----------------------------------------
-int rvll_live_runs_init(rvll_handle* h, const double* cube, int32_t R, int64_t n, double* logl_out)
-{
-    int rc = use_device(h);
-    if (rc) return rc;
-    if (!h->have_priors) return report_error(RVLL_E_NOPRIORS, "rvll_set_priors has not been called");
-    if (R < 1 || n < 2 || (int64_t)R * n >= (1LL << 31) || !cube) return report_error(RVLL_E_INVALID, "rvll_live_runs_init: bad arguments");
-    // a new ensemble starts here: no earlier live set — one run's or an ensemble's — is left looking valid, whatever fails below
-    h->live_n = 0;
-    h->dead_n = 0;
-    h->sorted_kdead = -1;
-    h->runs_R = 0;
-    h->runs_sorted.clear();
-    h->runs_sorted_kdead = -1;
-    h->cl_A = 0;
-    const int64_t N = (int64_t)R * n;
-    rc = live_load(h, cube, N, logl_out);
-    if (rc) return rc;
-    const int Di = h->L.ndim;
-    const size_t D = (size_t)Di;
-    const long long idx_need = 4 * N + 2 * (long long)R + 1;
-    if (idx_need > h->runs_idx_cap) {
-        dev_free(h->d_runs_idx);
-        h->runs_idx_cap = 0;
-        HIP_TRY(hipMalloc(&h->d_runs_idx, sizeof(int32_t) * (size_t)idx_need));
-        h->runs_idx_cap = idx_need;
-    }
-    if (R > h->runs_mom_cap) {
-        dev_free(h->d_runs_mom);
-        h->runs_mom_cap = 0;
-        HIP_TRY(hipMalloc(&h->d_runs_mom, sizeof(double) * (rvll::moments_runs_scratch_doubles(Di) + D + D * D) * (size_t)R));
-        h->runs_mom_cap = R;
-    }
-    h->runs_dead.assign((size_t)R, {});
-    h->runs_n = n;
-    h->runs_R = R;
-    return RVLL_OK;
-}
-
-namespace {
-// the listed runs of a rvll_live_runs_sort / _step: distinct, ascending, below R
-int runs_check(rvll_handle* h, const int32_t* runs, int32_t A, int64_t kdead, const char* who)
-{
-    if (h->runs_R < 1) return report_error(RVLL_E_INVALID, "%s: rvll_live_runs_init has not been called", who);
-    if (!runs || A < 1 || A > h->runs_R) return report_error(RVLL_E_INVALID, "%s: bad run list", who);
-    if (kdead < 1 || kdead >= h->runs_n) return report_error(RVLL_E_INVALID, "%s: kdead must be in [1, n)", who);
-    for (int32_t a = 0; a < A; ++a)
-        if (runs[a] < 0 || runs[a] >= h->runs_R || (a > 0 && runs[a] <= runs[a - 1]))
-            return report_error(RVLL_E_INVALID, "%s: runs must be distinct, ascending and below R (runs[%d] = %d)", who, (int)a, (int)runs[a]);
-    return RVLL_OK;
-}
-}  // namespace
-
-int rvll_live_runs_sort(rvll_handle* h, const int32_t* runs, int32_t A, int64_t kdead, double* dead_logl, double* lstar,
-                        double* max_logl)
-{
-    int rc = use_device(h);
-    if (rc) return rc;
-    rc = runs_check(h, runs, A, kdead, "rvll_live_runs_sort");
-    if (rc) return rc;
-    if (!dead_logl || !lstar || !max_logl) return report_error(RVLL_E_INVALID, "rvll_live_runs_sort: bad arguments");
-    h->runs_sorted.clear();
-    h->runs_sorted_kdead = -1;
-    const long long n = h->runs_n, R = h->runs_R;
-    hipStream_t st = h->compute;
-    const size_t need = rvll::runs_sort_temp_bytes(A, n);
-    if (need > h->sort_temp_bytes) {
-        HIP_TRY(hipStreamSynchronize(st));
-        dev_free(h->d_sort_temp);
-        h->sort_temp_bytes = 0;
-        HIP_TRY(hipMalloc(&h->d_sort_temp, need));
-        h->sort_temp_bytes = need;
-    }
-    int32_t* d_order = h->d_runs_idx;                    // [A n]: the listed runs' orders, packed
-    int32_t* d_runs = h->d_runs_idx + 4 * R * n;         // [A], then the segments [A + 1]
-    int32_t* d_seg = d_runs + R;
-    rc = walk_reserve(h, (int64_t)A * (kdead + 1));      // (the walk's log-L scratch takes the rows that come down)
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(d_runs, runs, sizeof(int32_t) * (size_t)A, hipMemcpyHostToDevice, st));
-    HIP_TRY(rvll::launch_runs_sort(h->d_live_logl, d_runs, A, n, h->d_sort_keys, h->d_sort_keys + h->live_cap, h->d_sort_rows, d_seg,
-                                   d_order, h->d_sort_temp, h->sort_temp_bytes, st));
-    HIP_TRY(rvll::launch_runs_sorted_logl(h->d_live_logl, d_order, A, n, kdead, h->d_walk_logl, st));
-    std::vector<double> got((size_t)A * (size_t)(kdead + 1));
-    HIP_TRY(hipMemcpyAsync(got.data(), h->d_walk_logl, sizeof(double) * got.size(), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    std::vector<double> ls((size_t)A);
-    for (int32_t a = 0; a < A; ++a) {
-        const double* g = got.data() + (size_t)a * (size_t)(kdead + 1);
-        memcpy(dead_logl + (size_t)a * (size_t)kdead, g, sizeof(double) * (size_t)kdead);
-        ls[(size_t)a] = lstar[a] = g[kdead - 1];
-        max_logl[a] = g[kdead];
-    }
-    h->runs_sorted.assign(runs, runs + A);
-    h->runs_sorted_kdead = kdead;
-    h->runs_sorted_lstar = ls;
-    return RVLL_OK;
-}
-
-// rvll_live_runs_step, and rvll_live_runs_step_steps unclustered: steps [A] or null (every run nsteps; else nsteps is their
-// largest), move_out / pair_out [A kdead] or null (the step-count adaptation's distances)
-static int live_runs_step_impl(rvll_handle* h, const int32_t* runs, int32_t A, int64_t kdead, const int32_t* ranks, const double* lstar,
-                               const int32_t* wrapped, int32_t nsteps, const int32_t* steps, int32_t max_rounds, const uint64_t* seeds,
-                               int64_t* ncalls, double* logl_new, double* chol_out, double* move_out, double* pair_out)
-{
-    int rc = use_device(h);
-    if (rc) return rc;
-    if (ncalls && A > 0) for (int32_t a = 0; a < A; ++a) ncalls[a] = 0;
-    rc = runs_check(h, runs, A, kdead, "rvll_live_runs_step");
-    if (rc) return rc;
-    if (!ranks || !lstar || !seeds || !logl_new) return report_error(RVLL_E_INVALID, "rvll_live_runs_step: bad arguments");
-    const long long n = h->runs_n, R = h->runs_R;
-    const int64_t K = (int64_t)A * kdead;
-    rc = walk_check_args(h, K, nsteps, max_rounds, 0, wrapped);
-    if (rc) return rc;
-    if (h->runs_sorted_kdead != kdead || h->runs_sorted.size() != (size_t)A || !std::equal(runs, runs + A, h->runs_sorted.begin()))
-        return report_error(RVLL_E_INVALID, "rvll_live_runs_step: no rvll_live_runs_sort of these runs with kdead = %lld precedes", (long long)kdead);
-    for (int32_t a = 0; a < A; ++a)
-        if (!(lstar[a] == h->runs_sorted_lstar[(size_t)a]))
-            return report_error(RVLL_E_INVALID, "rvll_live_runs_step: lstar[%d] is not the one rvll_live_runs_sort returned", (int)a);
-    for (int64_t i = 0; i < K; ++i)
-        if (ranks[i] < 0 || ranks[i] >= n - kdead)
-            return report_error(RVLL_E_INVALID, "rvll_live_runs_step: ranks[%lld] is not a rank among the survivors", (long long)i);
-    h->runs_sorted.clear();                              // (used up, whatever happens below: the step changes the rows)
-    h->runs_sorted_kdead = -1;
-    const int Di = h->L.ndim;
-    const size_t D = (size_t)Di;
-    if (h->dead_n + K >= (1LL << 31)) return report_error(RVLL_E_NOMEM, "rvll_live_runs_step: the dead store is full (2^31 rows)");
-    rc = runs_reserve(h, K, A);
-    if (rc) return rc;
-    rc = dead_reserve(h, K, K, "rvll_live_runs_step");
-    if (rc) return rc;
-    hipStream_t st = h->compute;
-    int32_t* d_order = h->d_runs_idx;                    // [A n] from the sort
-    int32_t* d_rank = d_order + R * n;                   // [A kdead] each
-    int32_t* d_dying = d_rank + R * n;
-    int32_t* d_start = d_dying + R * n;
-    HIP_TRY(hipMemcpyAsync(d_rank, ranks, sizeof(int32_t) * (size_t)K, hipMemcpyHostToDevice, st));
-    HIP_TRY(rvll::launch_runs_compose(d_order, A, n, kdead, d_rank, d_dying, d_start, h->d_walk_run, h->d_walk_wid, st));
-    // the dying rows, run a's at a kdead of this step's block, go to the dead store before their rows are overwritten (dead_n
-    // and the runs' pieces move on only when the step has succeeded, at the bottom: a failed step leaves every run as it was)
-    HIP_TRY(rvll::launch_gather_rows(h->d_live_theta, d_dying, K, Di, h->d_dead_theta + (size_t)h->dead_n * D, st));
-    HIP_TRY(rvll::launch_gather_rows(h->d_live_logl, d_dying, K, 1, h->d_dead_logl + h->dead_n, st));
-    // whitening: every run's survivors (ranks kdead .. n) in one set of moments launches, A covariances down in one copy
-    double* d_part = h->d_runs_mom;
-    double* d_mean = d_part + rvll::moments_runs_scratch_doubles(Di) * (size_t)A;
-    double* d_cov = d_mean + D * (size_t)A;
-    HIP_TRY(rvll::launch_moments_runs(h->d_live_u, d_order + kdead, n, A, n - kdead, Di, d_part, d_mean, d_cov, st));
-    std::vector<double> cov(D * D * (size_t)A), factor(D * D * (size_t)A);
-    HIP_TRY(hipMemcpyAsync(cov.data(), d_cov, sizeof(double) * cov.size(), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    for (int32_t a = 0; a < A; ++a)
-        if (!whitening_factor(cov.data() + D * D * (size_t)a, D, factor.data() + D * D * (size_t)a))
-            return report_error(RVLL_E_INVALID, "rvll_live_runs_step: the live points' covariance of run %d is not positive definite", (int)runs[a]);
-    if (chol_out) memcpy(chol_out, factor.data(), sizeof(double) * factor.size());
-    // the walkers (walker i of listed run a is row a kdead + i of the walk) start from their rows ...
-    HIP_TRY(rvll::launch_gather_rows(h->d_live_u, d_start, K, Di, h->d_walk_u, st));
-    HIP_TRY(rvll::launch_gather_rows(h->d_live_theta, d_start, K, Di, h->d_walk_theta, st));
-    HIP_TRY(rvll::launch_gather_rows(h->d_live_logl, d_start, K, 1, h->d_walk_logl, st));
-    HIP_TRY(hipMemcpyAsync(h->d_run_lstar, lstar, sizeof(double) * (size_t)A, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(h->d_run_seed, seeds, sizeof(uint64_t) * (size_t)A, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(h->d_run_chol, factor.data(), sizeof(double) * factor.size(), hipMemcpyHostToDevice, st));
-    rc = walk_upload_frame(h, nullptr, wrapped);         // (synchronises: `factor` may go out of scope after it)
-    if (rc) return rc;
-    std::vector<int32_t> run((size_t)K), rid((size_t)K);
-    for (int64_t e = 0; e < K; ++e) { run[(size_t)e] = (int32_t)(e / kdead); rid[(size_t)e] = (int32_t)(e % kdead); }
-    const bool dist = move_out || pair_out;
-    double* d_wstart = nullptr;
-    int32_t* d_wgroup = nullptr;
-    if (dist) {                                          // the walkers' start rows and groups (walk_core may reuse d_walk_run)
-        rc = adapt_in_reserve(h, 8 * (size_t)K * D + 4 * (size_t)K + 16);
-        if (rc) return rc;
-        d_wstart = static_cast<double*>(h->d_adapt_in);
-        d_wgroup = reinterpret_cast<int32_t*>(d_wstart + (size_t)K * D);
-        HIP_TRY(hipMemcpyAsync(d_wstart, h->d_walk_u, 8 * (size_t)K * D, hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_wgroup, run.data(), 4 * (size_t)K, hipMemcpyHostToDevice, st));
-    }
-    if (steps) HIP_TRY(hipMemcpyAsync(h->d_run_nsteps, steps, sizeof(int32_t) * (size_t)A, hipMemcpyHostToDevice, st));
-    RunWalk rw{run.data(), rid.data(), std::vector<long long>((size_t)K, 0), steps};
-    rc = walk_core(h, K, 0., nsteps, max_rounds, 0, 0, nullptr, &rw);
-    if (rc) return rc;
-    // the distances (group = the run: its survivors, ranks kdead .. n of its sort order, and its factor), behind the walk
-    std::vector<int64_t> gofs, gcnt;
-    std::vector<int32_t> tables;
-    std::vector<double> hmove, hpair;
-    if (dist) {
-        gofs.resize((size_t)A); gcnt.assign((size_t)A, n - kdead);
-        for (int32_t a = 0; a < A; ++a) gofs[(size_t)a] = (int64_t)a * n + kdead;
-        double *d_pair = nullptr, *d_move = nullptr;
-        rc = walk_distances_core(h, h->d_live_u, d_order, gofs, gcnt, h->d_run_chol, wrapped_mask(wrapped, Di), d_wstart, h->d_walk_u,
-                                 d_wgroup, K, &d_pair, &d_move, tables);
-        if (rc) return rc;
-        hmove.resize((size_t)K); hpair.resize((size_t)A);
-        HIP_TRY(hipMemcpyAsync(hmove.data(), d_move, 8 * (size_t)K, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(hpair.data(), d_pair, 8 * (size_t)A, hipMemcpyDeviceToHost, st));
-    }
-    // ... and their end points replace the dying rows, born at their run's lstar: the highest dying log-L, slot a kdead + kdead - 1
-    // of the step's block in the dead store (the dying rows' births go to the dead store first)
-    double* dead_birth = h->d_dead_birth + h->dead_n;
-    HIP_TRY(rvll::launch_births_step(d_dying, K, kdead, h->d_dead_logl + h->dead_n + (kdead - 1), 0., h->d_live_birth, dead_birth, st));
-    HIP_TRY(rvll::launch_scatter_rows(h->d_walk_u, d_dying, K, Di, h->d_live_u, st));
-    HIP_TRY(rvll::launch_scatter_rows(h->d_walk_theta, d_dying, K, Di, h->d_live_theta, st));
-    HIP_TRY(rvll::launch_scatter_rows(h->d_walk_logl, d_dying, K, 1, h->d_live_logl, st));
-    HIP_TRY(hipMemcpyAsync(logl_new, h->d_walk_logl, sizeof(double) * (size_t)K, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (ncalls)
-        for (int64_t e = 0; e < K; ++e) ncalls[e / kdead] += rw.row_calls[(size_t)e];
-    if (dist)
-        for (int64_t e = 0; e < K; ++e) {
-            if (move_out) move_out[e] = hmove[(size_t)e];
-            if (pair_out) pair_out[e] = hpair[(size_t)(e / kdead)];
-        }
-    for (int32_t a = 0; a < A; ++a) h->runs_dead[(size_t)runs[a]].emplace_back(h->dead_n + (long long)a * kdead, (long long)kdead);
-    h->dead_n += K;
-    return RVLL_OK;
-}
-
-int rvll_live_runs_step(rvll_handle* h, const int32_t* runs, int32_t A, int64_t kdead, const int32_t* ranks, const double* lstar,
-                        const int32_t* wrapped, int32_t nsteps, int32_t max_rounds, const uint64_t* seeds, int64_t* ncalls,
-                        double* logl_new, double* chol_out)
-{
-    return live_runs_step_impl(h, runs, A, kdead, ranks, lstar, wrapped, nsteps, nullptr, max_rounds, seeds, ncalls, logl_new, chol_out,
-                               nullptr, nullptr);
-}
-
-// The clustered step ("Clustering inside the resident ensemble").  Host synchronisations before the walk: the global
-// covariances (as rvll_live_runs_step), the labels and cluster counts, and — only when some run has more than one cluster with at
-// least 2 ndim rows — the per-cluster covariances; then those of the walk and the final download, as rvll_live_runs_step.
-// rvll_live_runs_step_clustered, and rvll_live_runs_step_steps clustered (steps, move_out, pair_out as live_runs_step_impl; the
-// distances' groups are the walk's (run, cluster) groups)
-static int live_runs_step_clustered_impl(rvll_handle* h, const int32_t* runs, int32_t A, int64_t kdead, const int32_t* ranks,
-                                         const double* lstar, const int32_t* wrapped, int32_t nsteps, const int32_t* steps,
-                                         int32_t max_rounds, const uint64_t* seeds, int32_t nboot, const uint64_t* boot_seeds,
-                                         int64_t* ncalls, double* logl_new, int32_t* nclusters, double* move_out, double* pair_out)
-{
-    const char* who = "rvll_live_runs_step_clustered";
-    int rc = use_device(h);
-    if (rc) return rc;
-    if (ncalls && A > 0) for (int32_t a = 0; a < A; ++a) ncalls[a] = 0;
-    rc = runs_check(h, runs, A, kdead, who);
-    if (rc) return rc;
-    if (!ranks || !lstar || !seeds || !logl_new || !boot_seeds || !nclusters) return report_error(RVLL_E_INVALID, "%s: bad arguments", who);
-    if (nboot < 0 || nboot > rvll::kClusterMaxBoot)
-        return report_error(RVLL_E_INVALID, "%s: nboot = %d is outside [0, %d]", who, (int)nboot, rvll::kClusterMaxBoot);
-    const int Di = h->L.ndim;
-    if (Di < 1 || Di > rvll::kClusterMaxDims)
-        return report_error(RVLL_E_UNSUPPORTED, "%s: %d parameters (the clustering takes 1 .. %d)", who, Di, rvll::kClusterMaxDims);
-    const long long n = h->runs_n, R = h->runs_R, m = n - kdead;
-    const int64_t K = (int64_t)A * kdead, M = (int64_t)A * m;
-    rc = walk_check_args(h, K, nsteps, max_rounds, 0, wrapped);
-    if (rc) return rc;
-    if (h->runs_sorted_kdead != kdead || h->runs_sorted.size() != (size_t)A || !std::equal(runs, runs + A, h->runs_sorted.begin()))
-        return report_error(RVLL_E_INVALID, "%s: no rvll_live_runs_sort of these runs with kdead = %lld precedes", who, (long long)kdead);
-    for (int32_t a = 0; a < A; ++a)
-        if (!(lstar[a] == h->runs_sorted_lstar[(size_t)a]))
-            return report_error(RVLL_E_INVALID, "%s: lstar[%d] is not the one rvll_live_runs_sort returned", who, (int)a);
-    for (int64_t i = 0; i < K; ++i)
-        if (ranks[i] < 0 || ranks[i] >= m)
-            return report_error(RVLL_E_INVALID, "%s: ranks[%lld] is not a rank among the survivors", who, (long long)i);
-    h->runs_sorted.clear();                              // (used up, whatever happens below: the step changes the rows)
-    h->runs_sorted_kdead = -1;
-    const size_t D = (size_t)Di;
-    if (h->dead_n + K >= (1LL << 31)) return report_error(RVLL_E_NOMEM, "%s: the dead store is full (2^31 rows)", who);
-    rc = runs_reserve(h, K, K);                          // (group tables for up to A kdead groups: one walker each)
-    if (rc) return rc;
-    rc = dead_reserve(h, K, K, who);
-    if (rc) return rc;
-    // the clustering's blocks: rows a m .. a m + m - 1 are listed run a's survivors in rank order; the workgroup table depends on
-    // (A, m) alone
-    std::vector<int64_t> cstart((size_t)A + 1);
-    for (int32_t a = 0; a <= A; ++a) cstart[(size_t)a] = (int64_t)a * m;
-    const std::vector<int32_t> blocks = cluster_blocks(cstart.data(), A);
-    const ClusterLayout L = cluster_layout(M, A, Di, blocks.size());
-    rc = cluster_reserve(h, L, who);
-    if (rc) return rc;
-    hipStream_t st = h->compute;
-    const size_t need = rvll::label_sort_temp_bytes(A, M);
-    if (need > h->sort_temp_bytes) {
-        HIP_TRY(hipStreamSynchronize(st));
-        dev_free(h->d_sort_temp);
-        h->sort_temp_bytes = 0;
-        HIP_TRY(hipMalloc(&h->d_sort_temp, need));
-        h->sort_temp_bytes = need;
-    }
-    int32_t* d_order = h->d_runs_idx;                    // [A n] from the sort
-    int32_t* d_rank = d_order + R * n;                   // [A kdead] each: ranks, then the walkers in group order
-    int32_t* d_dying = d_rank + R * n;
-    int32_t* d_start = d_dying + R * n;
-    int32_t* d_seg = d_start + R * n + R;                // [A + 1]: the sort's segments, now the label sort's (a m)
-    // the sort keys' block as ints [4 live_cap]: labels in (label, rank) order | their slots | the walkers' start rows | their
-    // dying rows, in group order (live_cap >= R n >= A m, A kdead)
-    int32_t* kscr = reinterpret_cast<int32_t*>(h->d_sort_keys);
-    const long long lc = h->live_cap;
-    int32_t *d_lab_sorted = kscr, *d_slot_sorted = kscr + lc, *d_gstart = kscr + 2 * lc, *d_gdying = kscr + 3 * lc;
-    HIP_TRY(hipMemcpyAsync(d_rank, ranks, sizeof(int32_t) * (size_t)K, hipMemcpyHostToDevice, st));
-    HIP_TRY(rvll::launch_runs_compose(d_order, A, n, kdead, d_rank, d_dying, d_start, h->d_walk_run, h->d_walk_wid, st));
-    // the dying rows go to the dead store before their rows are overwritten; committed at the bottom, as rvll_live_runs_step
-    HIP_TRY(rvll::launch_gather_rows(h->d_live_theta, d_dying, K, Di, h->d_dead_theta + (size_t)h->dead_n * D, st));
-    HIP_TRY(rvll::launch_gather_rows(h->d_live_logl, d_dying, K, 1, h->d_dead_logl + h->dead_n, st));
-    // 1. the global moments, exactly as rvll_live_runs_step; the survivors packed for the clustering meanwhile
-    double* d_part = h->d_runs_mom;
-    double* d_mean = d_part + rvll::moments_runs_scratch_doubles(Di) * (size_t)A;
-    double* d_cov = d_mean + D * (size_t)A;
-    HIP_TRY(rvll::launch_moments_runs(h->d_live_u, d_order + kdead, n, A, m, Di, d_part, d_mean, d_cov, st));
-    char* din = static_cast<char*>(h->d_cl_in);
-    double* d_surv = reinterpret_cast<double*>(din + L.o_cube);
-    HIP_TRY(rvll::launch_runs_survivors(h->d_live_u, d_order, A, n, kdead, Di, d_surv, h->d_sort_rows, d_seg, st));
-    std::vector<double> cov(D * D * (size_t)A), gfac(D * D * (size_t)A);
-    HIP_TRY(hipMemcpyAsync(cov.data(), d_cov, sizeof(double) * cov.size(), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));                   // sync 1
-    const auto t1 = std::chrono::steady_clock::now();
-    for (int32_t a = 0; a < A; ++a)
-        if (!whitening_factor(cov.data() + D * D * (size_t)a, D, gfac.data() + D * D * (size_t)a))
-            return report_error(RVLL_E_INVALID, "%s: the live points' covariance of run %d is not positive definite", who, (int)runs[a]);
-    // 2. the metric (evidence_amd/nested.py's _cluster_scale of the device covariance), the bootstrap seeds and the block table go
-    // up behind the packed survivors; clustering, then every run's (label, rank) order
-    std::vector<double> scale(D * (size_t)A);
-    for (int32_t a = 0; a < A; ++a)
-        for (size_t d = 0; d < D; ++d) scale[(size_t)a * D + d] = 1.0 / std::sqrt(cov[(size_t)a * D * D + d * D + d] + 1e-14);
-    std::vector<char> in(L.in_bytes - L.o_scale);
-    memcpy(in.data(), scale.data(), sizeof(double) * scale.size());
-    memcpy(in.data() + (L.o_start - L.o_scale), cstart.data(), sizeof(int64_t) * cstart.size());
-    memcpy(in.data() + (L.o_seed - L.o_scale), boot_seeds, sizeof(uint64_t) * (size_t)A);
-    if (!blocks.empty()) memcpy(in.data() + (L.o_blk - L.o_scale), blocks.data(), sizeof(int32_t) * blocks.size());
-    HIP_TRY(hipMemcpyAsync(din + L.o_scale, in.data(), in.size(), hipMemcpyHostToDevice, st));
-    const rvll::ClusterArgs ca = cluster_args(h, L, Di, nboot, wrapped);
-    rc = cluster_core(h, ca);
-    if (rc) return rc;
-    HIP_TRY(rvll::launch_label_sort(ca.labels, d_lab_sorted, h->d_sort_rows, d_slot_sorted, A, M, d_seg, h->d_sort_temp,
-                                    h->sort_temp_bytes, st));
-    std::vector<char> out(L.out_bytes);
-    HIP_TRY(hipMemcpyAsync(out.data(), h->d_cl_out, L.out_bytes, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));                   // sync 2
-    const auto t2 = std::chrono::steady_clock::now();
-    const int32_t* ncl = reinterpret_cast<const int32_t*>(out.data() + L.p_ncl);
-    const int32_t* lab = reinterpret_cast<const int32_t*>(out.data() + L.p_lab);
-    // 3. per (run, cluster) its rows, and where it starts in the run's (label, rank) order; the clusters of at least 2 ndim rows of
-    // the runs with more than one cluster are the segments of one segmented moments pass
-    std::vector<std::vector<long long>> cnt((size_t)A);
-    std::vector<long long> segtab;
-    std::vector<double> segsc;
-    std::vector<std::pair<int32_t, int32_t>> seg_of;     // (listed run, cluster)
-    for (int32_t a = 0; a < A; ++a) {
-        const int32_t k = ncl[a];
-        if (k < 1 || k > m) return report_error(RVLL_E_HIP, "%s: the clustering of run %d returned %d clusters", who, (int)runs[a], (int)k);
-        cnt[(size_t)a].assign((size_t)k, 0);
-        for (long long j = 0; j < m; ++j) {
-            const int32_t c = lab[a * m + j];
-            if (c < 0 || c >= k) return report_error(RVLL_E_HIP, "%s: label %d of run %d is out of range", who, (int)c, (int)runs[a]);
-            ++cnt[(size_t)a][(size_t)c];
-        }
-        if (k == 1) continue;
-        long long off = (long long)a * m;
-        for (int32_t c = 0; c < k; ++c) {
-            const long long rows = cnt[(size_t)a][(size_t)c];
-            if (rows >= 2 * (long long)Di) {
-                segtab.push_back(off); segtab.push_back(rows);
-                segsc.push_back(1.0 / (double)rows); segsc.push_back(1.0 / (double)(rows > 1 ? rows - 1 : 1));
-                seg_of.emplace_back(a, c);
-            }
-            off += rows;
-        }
-    }
-    const int S = (int)seg_of.size();
-    std::vector<double> segcov(D * D * (size_t)S);
-    if (S > 0) {
-        const size_t o_sc = sizeof(long long) * 2 * (size_t)S, o_mean = o_sc + sizeof(double) * 2 * (size_t)S;
-        const size_t o_cov = o_mean + sizeof(double) * D * (size_t)S, bytes = o_cov + sizeof(double) * D * D * (size_t)S;
-        if (bytes > h->clseg_cap) {
-            HIP_TRY(hipStreamSynchronize(st));
-            if (h->d_clseg) { (void)hipFree(h->d_clseg); h->d_clseg = nullptr; }
-            h->clseg_cap = 0;
-            HIP_TRY(hipMalloc(&h->d_clseg, 2 * bytes));
-            h->clseg_cap = 2 * bytes;
-        }
-        std::vector<char> tab(o_mean);
-        memcpy(tab.data(), segtab.data(), o_sc);
-        memcpy(tab.data() + o_sc, segsc.data(), o_mean - o_sc);
-        char* dseg = static_cast<char*>(h->d_clseg);
-        HIP_TRY(hipMemcpyAsync(dseg, tab.data(), tab.size(), hipMemcpyHostToDevice, st));
-        // (the global moments' scratch, mean and covariance are spent: their block holds runs_mom_cap scratches)
-        HIP_TRY(rvll::launch_moments_segs(d_surv, d_slot_sorted, reinterpret_cast<const long long*>(dseg),
-                                          reinterpret_cast<const double*>(dseg + o_sc), S, Di, d_part, (int)std::min<long long>(h->runs_mom_cap, 65535),
-                                          reinterpret_cast<double*>(dseg + o_mean), reinterpret_cast<double*>(dseg + o_cov), st));
-        HIP_TRY(hipMemcpyAsync(segcov.data(), dseg + o_cov, sizeof(double) * segcov.size(), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));               // sync 3
-    }
-    const auto t3 = std::chrono::steady_clock::now();
-    // 4. the factors of every run: the global one alone (one cluster), else one per cluster — its own or the global one
-    std::vector<std::vector<double>> fac((size_t)A);
-    for (int32_t a = 0; a < A; ++a) {
-        const size_t k = ncl[a] > 1 ? (size_t)ncl[a] : 1;
-        fac[(size_t)a].resize(D * D * k);
-        for (size_t c = 0; c < k; ++c) memcpy(fac[(size_t)a].data() + D * D * c, gfac.data() + D * D * (size_t)a, sizeof(double) * D * D);
-    }
-    for (int s = 0; s < S; ++s) {
-        const int32_t a = seg_of[(size_t)s].first, c = seg_of[(size_t)s].second;
-        if (!whitening_factor(segcov.data() + D * D * (size_t)s, D, fac[(size_t)a].data() + D * D * (size_t)c))
-            return report_error(RVLL_E_INVALID, "%s: the covariance of cluster %d of run %d is not positive definite", who, (int)c, (int)runs[a]);
-    }
-    // 5. the walker groups (nested.py's _walk_groups): per run, the non-empty clusters of the start rows in label order, walkers in
-    // their order inside a group; walk row e is walker perm[e] = a kdead + i
-    std::vector<int32_t> perm((size_t)K), grun((size_t)K), grid((size_t)K), gsteps;
-    std::vector<double> glstar, gchol;
-    std::vector<uint64_t> gseed;
-    std::vector<int64_t> gofs, gcnt;                     // every group's survivors: slots gofs .. + gcnt of the (label, rank) order
-    {
-        int64_t e = 0;
-        std::vector<int32_t> wc((size_t)kdead);
-        std::vector<long long> first;
-        for (int32_t a = 0; a < A; ++a) {
-            const size_t k = cnt[(size_t)a].size();
-            first.assign(k + 1, 0);
-            for (int64_t i = 0; i < kdead; ++i) {
-                wc[(size_t)i] = lab[a * m + ranks[(size_t)a * kdead + i]];
-                ++first[(size_t)wc[(size_t)i] + 1];
-            }
-            for (size_t c = 0; c < k; ++c) first[c + 1] += first[c];
-            std::vector<int32_t> gof(k, -1);             // group number of cluster c (-1: no walker starts in it)
-            long long offc = (long long)a * m;
-            for (size_t c = 0; c < k; ++c) {
-                offc += c > 0 ? cnt[(size_t)a][c - 1] : 0;
-                if (first[c + 1] == first[c]) continue;
-                gofs.push_back(offc);
-                gcnt.push_back(cnt[(size_t)a][c]);
-                gsteps.push_back(steps ? steps[a] : nsteps);
-                gof[c] = (int32_t)glstar.size();
-                glstar.push_back(lstar[a]);
-                gseed.push_back(c == 0 ? seeds[a] : seeds[a] + (uint64_t)c * 0xD1B54A32D192ED03ull);
-                gchol.insert(gchol.end(), fac[(size_t)a].begin() + D * D * c, fac[(size_t)a].begin() + D * D * (c + 1));
-            }
-            std::vector<long long> at(first.begin(), first.end() - 1);
-            for (int64_t i = 0; i < kdead; ++i) {
-                const size_t c = (size_t)wc[(size_t)i];
-                const long long r = at[c]++;
-                const int64_t row = e + r;
-                perm[(size_t)row] = (int32_t)((int64_t)a * kdead + i);
-                grun[(size_t)row] = gof[c];
-                grid[(size_t)row] = (int32_t)(r - first[c]);
-            }
-            e += kdead;
-        }
-    }
-    HIP_TRY(hipMemcpyAsync(d_rank, perm.data(), sizeof(int32_t) * (size_t)K, hipMemcpyHostToDevice, st));
-    HIP_TRY(rvll::launch_compose_index(d_start, 0, d_rank, K, d_gstart, st));
-    HIP_TRY(rvll::launch_compose_index(d_dying, 0, d_rank, K, d_gdying, st));
-    HIP_TRY(hipMemcpyAsync(h->d_walk_run, grun.data(), sizeof(int32_t) * (size_t)K, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(h->d_walk_wid, grid.data(), sizeof(int32_t) * (size_t)K, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(h->d_run_lstar, glstar.data(), sizeof(double) * glstar.size(), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(h->d_run_seed, gseed.data(), sizeof(uint64_t) * gseed.size(), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(h->d_run_chol, gchol.data(), sizeof(double) * gchol.size(), hipMemcpyHostToDevice, st));
-    // 6. one run-mode walk for every group of every run, the end points back to the dying rows
-    HIP_TRY(rvll::launch_gather_rows(h->d_live_u, d_gstart, K, Di, h->d_walk_u, st));
-    HIP_TRY(rvll::launch_gather_rows(h->d_live_theta, d_gstart, K, Di, h->d_walk_theta, st));
-    HIP_TRY(rvll::launch_gather_rows(h->d_live_logl, d_gstart, K, 1, h->d_walk_logl, st));
-    const bool dist = move_out || pair_out;
-    double* d_wstart = nullptr;
-    int32_t* d_wgroup = nullptr;
-    if (dist) {                                          // the walkers' start rows and groups (walk_core may reuse d_walk_run)
-        rc = adapt_in_reserve(h, 8 * (size_t)K * D + 4 * (size_t)K + 16);
-        if (rc) return rc;
-        d_wstart = static_cast<double*>(h->d_adapt_in);
-        d_wgroup = reinterpret_cast<int32_t*>(d_wstart + (size_t)K * D);
-        HIP_TRY(hipMemcpyAsync(d_wstart, h->d_walk_u, 8 * (size_t)K * D, hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_wgroup, grun.data(), 4 * (size_t)K, hipMemcpyHostToDevice, st));
-    }
-    if (steps) HIP_TRY(hipMemcpyAsync(h->d_run_nsteps, gsteps.data(), sizeof(int32_t) * gsteps.size(), hipMemcpyHostToDevice, st));
-    rc = walk_upload_frame(h, nullptr, wrapped);         // (synchronises: the host tables above may go out of scope after it)
-    if (rc) return rc;
-    RunWalk rw{grun.data(), grid.data(), std::vector<long long>((size_t)K, 0), steps ? gsteps.data() : nullptr};
-    rc = walk_core(h, K, 0., nsteps, max_rounds, 0, 0, nullptr, &rw);
-    if (rc) return rc;
-    // the distances: group g's survivors are the packed rows of its cluster (d_surv through the label sort's slots), its factor the
-    // walk's
-    std::vector<int32_t> tables;
-    std::vector<double> hmove, hpair;
-    if (dist) {
-        double *d_pair = nullptr, *d_move = nullptr;
-        rc = walk_distances_core(h, d_surv, d_slot_sorted, gofs, gcnt, h->d_run_chol, wrapped_mask(wrapped, Di), d_wstart, h->d_walk_u,
-                                 d_wgroup, K, &d_pair, &d_move, tables);
-        if (rc) return rc;
-        hmove.resize((size_t)K); hpair.resize(gofs.size());
-        HIP_TRY(hipMemcpyAsync(hmove.data(), d_move, 8 * (size_t)K, hipMemcpyDeviceToHost, st));
-        if (!gofs.empty()) HIP_TRY(hipMemcpyAsync(hpair.data(), d_pair, 8 * gofs.size(), hipMemcpyDeviceToHost, st));
-    }
-    // births as rvll_live_runs_step: in the dead store's order (d_dying), each run's rows at its lstar
-    HIP_TRY(rvll::launch_births_step(d_dying, K, kdead, h->d_dead_logl + h->dead_n + (kdead - 1), 0., h->d_live_birth,
-                                     h->d_dead_birth + h->dead_n, st));
-    HIP_TRY(rvll::launch_scatter_rows(h->d_walk_u, d_gdying, K, Di, h->d_live_u, st));
-    HIP_TRY(rvll::launch_scatter_rows(h->d_walk_theta, d_gdying, K, Di, h->d_live_theta, st));
-    HIP_TRY(rvll::launch_scatter_rows(h->d_walk_logl, d_gdying, K, 1, h->d_live_logl, st));
-    std::vector<double> wl((size_t)K);
-    HIP_TRY(hipMemcpyAsync(wl.data(), h->d_walk_logl, sizeof(double) * (size_t)K, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const auto t4 = std::chrono::steady_clock::now();
-    for (int64_t e = 0; e < K; ++e) {
-        logl_new[perm[(size_t)e]] = wl[(size_t)e];
-        if (ncalls) ncalls[perm[(size_t)e] / kdead] += rw.row_calls[(size_t)e];
-        if (move_out) move_out[perm[(size_t)e]] = hmove[(size_t)e];
-        if (pair_out) pair_out[perm[(size_t)e]] = hpair[(size_t)grun[(size_t)e]];
-    }
-    for (int32_t a = 0; a < A; ++a) nclusters[a] = ncl[a];
-    h->cl_A = A;
-    h->cl_m = m;
-    h->cl_labels.assign(lab, lab + M);
-    h->cl_ncl.assign(ncl, ncl + A);
-    h->cl_scale = std::move(scale);
-    h->cl_factors = std::move(fac);
-    h->cl_phase_s[0] = std::chrono::duration<double>(t2 - t1).count();
-    h->cl_phase_s[1] = std::chrono::duration<double>(t3 - t2).count();
-    h->cl_phase_s[2] = std::chrono::duration<double>(t4 - t3).count();
-    for (int32_t a = 0; a < A; ++a) h->runs_dead[(size_t)runs[a]].emplace_back(h->dead_n + (long long)a * kdead, (long long)kdead);
-    h->dead_n += K;
-    return RVLL_OK;
-}
-
-int rvll_live_runs_step_clustered(rvll_handle* h, const int32_t* runs, int32_t A, int64_t kdead, const int32_t* ranks,
-                                  const double* lstar, const int32_t* wrapped, int32_t nsteps, int32_t max_rounds,
-                                  const uint64_t* seeds, int32_t nboot, const uint64_t* boot_seeds, int64_t* ncalls,
-                                  double* logl_new, int32_t* nclusters)
-{
-    return live_runs_step_clustered_impl(h, runs, A, kdead, ranks, lstar, wrapped, nsteps, nullptr, max_rounds, seeds, nboot, boot_seeds,
-                                         ncalls, logl_new, nclusters, nullptr, nullptr);
-}
-
-int rvll_live_runs_step_steps(rvll_handle* h, const int32_t* runs, int32_t A, int64_t kdead, const int32_t* ranks, const double* lstar,
-                              const int32_t* wrapped, const int32_t* nsteps, int32_t max_rounds, const uint64_t* seeds, int32_t clustered,
-                              int32_t nboot, const uint64_t* boot_seeds, int64_t* ncalls, double* logl_new, int32_t* nclusters,
-                              double* move, double* pair)
-{
-    if (A > 0 && !nsteps) return report_error(RVLL_E_INVALID, "rvll_live_runs_step_steps: null step table");
-    int32_t most = 0, least = A > 0 ? nsteps[0] : 0;
-    for (int32_t a = 0; a < A; ++a) {
-        if (nsteps[a] < 0 || nsteps[a] >= (1 << 18))
-            return report_error(RVLL_E_INVALID, "rvll_live_runs_step_steps: nsteps[%d] = %d out of range", (int)a, (int)nsteps[a]);
-        most = std::max(most, nsteps[a]);
-        least = std::min(least, nsteps[a]);
-    }
-    const int32_t* steps = least == most ? nullptr : nsteps;         // a uniform table is the scalar step
-    if (clustered)
-        return live_runs_step_clustered_impl(h, runs, A, kdead, ranks, lstar, wrapped, most, steps, max_rounds, seeds, nboot, boot_seeds,
-                                             ncalls, logl_new, nclusters, move, pair);
-    return live_runs_step_impl(h, runs, A, kdead, ranks, lstar, wrapped, most, steps, max_rounds, seeds, ncalls, logl_new, nullptr,
-                               move, pair);
-}
-
-int rvll_live_runs_clusters(rvll_handle* h, int32_t a, int64_t* nsurv, int32_t* nclusters, int32_t* labels, double* scale, double* factors,
-                            double* phase_s)
-{
-    if (!h) return report_error(RVLL_E_INVALID, "null handle");
-    if (h->cl_A < 1) return report_error(RVLL_E_INVALID, "rvll_live_runs_clusters: no rvll_live_runs_step_clustered since the live sets were loaded");
-    if (a < 0 || a >= h->cl_A) return report_error(RVLL_E_INVALID, "rvll_live_runs_clusters: listed run %d of %d", (int)a, (int)h->cl_A);
-    const size_t D = (size_t)h->L.ndim, m = (size_t)h->cl_m;
-    if (nsurv) *nsurv = (int64_t)m;
-    if (nclusters) *nclusters = h->cl_ncl[(size_t)a];
-    if (labels) memcpy(labels, h->cl_labels.data() + (size_t)a * m, sizeof(int32_t) * m);
-    if (scale) memcpy(scale, h->cl_scale.data() + (size_t)a * D, sizeof(double) * D);
-    if (factors) memcpy(factors, h->cl_factors[(size_t)a].data(), sizeof(double) * h->cl_factors[(size_t)a].size());
-    if (phase_s) for (int k = 0; k < 3; ++k) phase_s[k] = h->cl_phase_s[k];
-    return RVLL_OK;
-}
-
-int rvll_live_runs_get(rvll_handle* h, int32_t run, double* cube, double* theta, double* logl)
-{
-    int rc = use_device(h);
-    if (rc) return rc;
-    if (h->runs_R < 1) return report_error(RVLL_E_INVALID, "rvll_live_runs_init has not been called");
-    if (run < 0 || run >= h->runs_R) return report_error(RVLL_E_INVALID, "rvll_live_runs_get: run %d out of range", (int)run);
-    const size_t D = (size_t)h->L.ndim, n = (size_t)h->runs_n, r0 = (size_t)run * n;
-    hipStream_t st = h->compute;
-    if (cube) HIP_TRY(hipMemcpyAsync(cube, h->d_live_u + r0 * D, sizeof(double) * D * n, hipMemcpyDeviceToHost, st));
-    if (theta) HIP_TRY(hipMemcpyAsync(theta, h->d_live_theta + r0 * D, sizeof(double) * D * n, hipMemcpyDeviceToHost, st));
-    if (logl) HIP_TRY(hipMemcpyAsync(logl, h->d_live_logl + r0, sizeof(double) * n, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return RVLL_OK;
-}
-
-int rvll_live_runs_dead(rvll_handle* h, int32_t run, int64_t* n_dead, double* theta, double* logl)
-{
-    int rc = use_device(h);
-    if (rc) return rc;
-    if (!n_dead) return report_error(RVLL_E_INVALID, "n_dead is null");
-    if (h->runs_R < 1) return report_error(RVLL_E_INVALID, "rvll_live_runs_init has not been called");
-    if (run < 0 || run >= h->runs_R) return report_error(RVLL_E_INVALID, "rvll_live_runs_dead: run %d out of range", (int)run);
-    const auto& pieces = h->runs_dead[(size_t)run];
-    int64_t have = 0;
-    for (const auto& p : pieces) have += p.second;
-    const int64_t want = (theta || logl) ? std::min<int64_t>(*n_dead, have) : 0;
-    *n_dead = have;
-    if (want <= 0) return RVLL_OK;
-    // the run's rows of the store in death order, gathered through the walk's buffers a chunk at a time, one download per array
-    std::vector<int32_t> rows;
-    rows.reserve((size_t)want);
-    for (const auto& p : pieces)
-        for (long long i = 0; i < p.second && (int64_t)rows.size() < want; ++i) rows.push_back((int32_t)(p.first + i));
-    rc = walk_reserve(h, 1);
-    if (rc) return rc;
-    const int Di = h->L.ndim;
-    const size_t D = (size_t)Di;
-    hipStream_t st = h->compute;
-    for (int64_t lo = 0; lo < want; lo += h->walk_cap) {
-        const int64_t m = std::min<int64_t>(h->walk_cap, want - lo);
-        HIP_TRY(hipMemcpyAsync(h->d_walk_order, rows.data() + lo, sizeof(int32_t) * (size_t)m, hipMemcpyHostToDevice, st));
-        if (theta) {
-            HIP_TRY(rvll::launch_gather_rows(h->d_dead_theta, h->d_walk_order, m, Di, h->d_walk_theta, st));
-            HIP_TRY(hipMemcpyAsync(theta + (size_t)lo * D, h->d_walk_theta, sizeof(double) * D * (size_t)m, hipMemcpyDeviceToHost, st));
-        }
-        if (logl) {
-            HIP_TRY(rvll::launch_gather_rows(h->d_dead_logl, h->d_walk_order, m, 1, h->d_walk_logl, st));
-            HIP_TRY(hipMemcpyAsync(logl + lo, h->d_walk_logl, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, st));
-        }
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    return RVLL_OK;
-}
-
-// ---- birth contours of the resident rows ----------------------------------------------------------------------------------------
-int rvll_live_births(rvll_handle* h, int64_t* n_dead, double* dead_birth, double* live_birth)
-{
-    int rc = use_device(h);
-    if (rc) return rc;
-    if (!n_dead) return report_error(RVLL_E_INVALID, "n_dead is null");
-    if (h->runs_R > 0) return report_error(RVLL_E_INVALID, "rvll_live_births: the resident rows are an ensemble's (rvll_live_runs_births)");
-    if (live_birth && h->live_n < 1) return report_error(RVLL_E_INVALID, "rvll_live_init has not been called");
-    const int64_t have = h->dead_n, want = dead_birth ? std::min<int64_t>(*n_dead, have) : 0;
-    *n_dead = have;
-    hipStream_t st = h->compute;
-    if (want > 0) HIP_TRY(hipMemcpyAsync(dead_birth, h->d_dead_birth, sizeof(double) * (size_t)want, hipMemcpyDeviceToHost, st));
-    if (live_birth) HIP_TRY(hipMemcpyAsync(live_birth, h->d_live_birth, sizeof(double) * (size_t)h->live_n, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return RVLL_OK;
-}
-
-int rvll_live_runs_births(rvll_handle* h, int32_t run, int64_t* n_dead, double* dead_birth, double* live_birth)
-{
-    int rc = use_device(h);
-    if (rc) return rc;
-    if (!n_dead) return report_error(RVLL_E_INVALID, "n_dead is null");
-    if (h->runs_R < 1) return report_error(RVLL_E_INVALID, "rvll_live_runs_init has not been called");
-    if (run < 0 || run >= h->runs_R) return report_error(RVLL_E_INVALID, "rvll_live_runs_births: run %d out of range", (int)run);
-    const auto& pieces = h->runs_dead[(size_t)run];
-    int64_t have = 0;
-    for (const auto& p : pieces) have += p.second;
-    const int64_t want = dead_birth ? std::min<int64_t>(*n_dead, have) : 0;
-    *n_dead = have;
-    hipStream_t st = h->compute;
-    if (live_birth) {
-        const size_t n = (size_t)h->runs_n, r0 = (size_t)run * n;
-        HIP_TRY(hipMemcpyAsync(live_birth, h->d_live_birth + r0, sizeof(double) * n, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    if (want <= 0) return RVLL_OK;
-    // the run's rows of the store in death order, as rvll_live_runs_dead gathers them
-    std::vector<int32_t> rows;
-    rows.reserve((size_t)want);
-    for (const auto& p : pieces)
-        for (long long i = 0; i < p.second && (int64_t)rows.size() < want; ++i) rows.push_back((int32_t)(p.first + i));
-    rc = walk_reserve(h, 1);
-    if (rc) return rc;
-    for (int64_t lo = 0; lo < want; lo += h->walk_cap) {
-        const int64_t m = std::min<int64_t>(h->walk_cap, want - lo);
-        HIP_TRY(hipMemcpyAsync(h->d_walk_order, rows.data() + lo, sizeof(int32_t) * (size_t)m, hipMemcpyHostToDevice, st));
-        HIP_TRY(rvll::launch_gather_rows(h->d_dead_birth, h->d_walk_order, m, 1, h->d_walk_logl, st));
-        HIP_TRY(hipMemcpyAsync(dead_birth + lo, h->d_walk_logl, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    return RVLL_OK;
+    return slice_walk_runs_impl(h, cube, theta, logl, run_start, R, lstar, chol, seed, wrapped, uniform ? nullptr : nsteps, most,
+                                max_rounds, ncalls);
 }
 
 int rvll_set_walk_proposal(rvll_handle* h, int32_t kind, double width)

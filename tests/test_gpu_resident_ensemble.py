@@ -193,3 +193,53 @@ def test_failed_steps_leave_every_run_as_it_was(gpu_required):
         m.live_runs_step(runs, kdead, ranks, lstar2, None, 4, 200, [1, 2, 3])
         after = state(m)
         assert all(len(after[r][1][1]) == 2 * kdead for r in range(R)) and not same(after, before)
+
+
+@pytest.mark.parametrize("clustered", [False, True], ids=["unclustered", "clustered"])
+def test_a_step_that_fails_late_leaves_every_run_as_it_was(gpu_required, clustered):
+    """Every refusal of test_failed_steps_leave_every_run_as_it_was happens before anything is touched.  Here the step fails LATE: a
+    NaN among run 1's surviving cube rows (Uniform priors: no table lookup sees it) gives a covariance that cannot be factored, after
+    the dying rows of all three runs were copied to the dead store.  The store must not count them, no run may get a piece of it, no
+    live row and no birth may have changed; and since the failure spent the sort, the other runs step on after a fresh one."""
+    R, n, kdead = 3, 200, 50
+    rng = np.random.default_rng(6)
+    runs = np.arange(R, dtype=np.int32)
+
+    def step(m, which, ranks, lstar, seeds):
+        if clustered:
+            return m.live_runs_step_clustered(which, kdead, ranks, lstar, None, 4, 200, seeds, 10, [s + 100 for s in seeds])[:2]
+        return m.live_runs_step(which, kdead, ranks, lstar, None, 4, 200, seeds)
+
+    def state(m):
+        return [m.live_runs_get(r) + m.live_runs_dead(r) + (m.live_runs_dead_count(r),) + m.live_runs_births(r) for r in range(R)]
+
+    def same(a, b):
+        return all(np.array_equal(x, y, equal_nan=True) for ra, rb in zip(a, b) for x, y in zip(ra, rb))
+
+    with _gaussian() as m:
+        cube = rng.random((R * n, 2))
+        m.live_runs_init(cube, R)
+        dl, lstar, _ = m.live_runs_sort(runs, kdead)
+        step(m, runs, rng.integers(0, n - kdead, (R, kdead)), lstar, [1, 2, 3])          # a good step: the dead store is in use
+        assert all(m.live_runs_dead_count(r) == kdead for r in range(R))
+        bad = cube.copy()
+        bad[n + 17, 1] = np.nan                                                           # a cube row of run 1
+        logl = m.live_runs_init(bad, R)
+        assert np.isnan(logl[1, 17]) and np.isfinite(np.delete(logl.ravel(), n + 17)).all()
+        before = state(m)
+        assert all(s[5] == 0 for s in before)
+        dl, lstar, _ = m.live_runs_sort(runs, kdead)
+        assert np.isfinite(dl).all()                                                     # the NaN row sorts last: it survives, so the failure is late
+        ranks = rng.integers(0, n - kdead, (R, kdead))
+        with pytest.raises(RvllError) as e:
+            step(m, runs, ranks, lstar, [4, 5, 6])
+        assert e.value.code == _abi.E_INVALID and "positive definite" in str(e.value) and "run 1" in str(e.value), str(e.value)
+        assert same(state(m), before)
+        two = np.array([0, 2], dtype=np.int32)
+        dl2, lstar2, _ = m.live_runs_sort(two, kdead)
+        assert np.array_equal(dl2, dl[two]) and np.array_equal(lstar2, lstar[two])
+        wl, used = step(m, two, ranks[two], lstar2, [4, 6])
+        assert np.isfinite(wl).all() and (np.asarray(used) > 0).all()
+        after = state(m)
+        assert [s[5] for s in after] == [kdead, 0, kdead]
+        assert same([after[1]], [before[1]]) and not same([after[0]], [before[0]]) and not same([after[2]], [before[2]])

@@ -215,7 +215,7 @@ def test_run_mode_with_every_run_its_own_arguments(gpu_required, proposal):
 def test_the_resident_live_step(gpu_required, proposal):
     """live_step on a resident live set of 400 with the factor supplied, kdead = 50: the rows that replace the dying rows
     order[:kdead] are the replay of the rows `start`, walker i (the one that replaces row order[i]) drawing as walker
-    walker_base + i (rvll_live_step, in csrc/rvll_walk_host.hip, gathers the start rows into walk rows 0 .. kdead - 1 and hands
+    walker_base + i (rvll_live_step, in csrc/rvll_live_host.hip, gathers the start rows into walk rows 0 .. kdead - 1 and hands
     them to walk_core with that base; the end rows are scattered to order[:kdead] in the same order)."""
     with _model(1) as m:
         wrapped = wrapped_params(m.parnames)
