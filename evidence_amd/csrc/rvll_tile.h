@@ -347,6 +347,23 @@ __device__ __forceinline__ double eval_item(const LoglikeArgs& a, const ItemCtx&
                         ++steps;
                     } while (fabs(dE) > a.tol && steps < kSafeSteps);
                 }
+                if constexpr (CR) {
+                    // The redo pass in a tile whose shortcut is off because ANOTHER point's planet is wide: the same first
+                    // steps in the checked arithmetic (the same bits where the argument is in range), so that which solves
+                    // of a point are redone correctly rounded — those still going after eight steps — is the point's affair.
+                    if (!shortcut && a.itmax > kSafeSteps) {
+                        int steps = 0;
+                        do {
+                            sincos_any(E, s, c, kc);
+                            const double f  = E - ec * s - M;
+                            const double fp = 1 - ec * c;
+                            const double En = E - div_exact(f, fp);
+                            dE = En - E;
+                            E = En;
+                            ++steps;
+                        } while (fabs(dE) > a.tol && steps < kSafeSteps);
+                    }
+                }
                 bool hit_itmax = false, wander = false;
                 // (Both this test and the redo pass of the tile are marked UNLIKELY, and that is worth 4 % of every launch: the
                 // register allocator weighs a value by the estimated frequency of the blocks that use it, and with the correctly
@@ -388,10 +405,22 @@ __device__ __forceinline__ double eval_item(const LoglikeArgs& a, const ItemCtx&
 #endif
                 }
                 if (hit_itmax) {
-                    atomicMin(&cx.jfail[pl * Np + ip], j);
-                    atomicOr(&cx.anyfail[pl], 1);
-                    atomicOr(cx.nfail, 1);
-                    rv = p45.x + C0;
+                    if constexpr (CR) {
+                        // The redo pass runs a solve on another trajectory than the first pass did (correctly rounded sin / cos,
+                        // the reference's own) and can run out of steps where the first pass converged (9 < itmax <~ 1000,
+                        // e >= 0.97).  The reference aborts the planet's array there: the mark is lowered — while other lanes of
+                        // this pass read it, and past items already redone — and the tile is told to go round once more (bit 2
+                        // of nfail; 3b of loglike_tile repeats until a pass lowers no mark).  The marks then are the minimum over
+                        // the failing items of both passes, a function of the point alone.
+                        if (atomicMin(&cx.jfail[pl * Np + ip], j) > j) atomicOr(cx.nfail, 4);
+                        atomicOr(&cx.anyfail[pl], 1);
+                        rv = p45.x + C0;
+                    } else {
+                        atomicMin(&cx.jfail[pl * Np + ip], j);
+                        atomicOr(&cx.anyfail[pl], 1);
+                        atomicOr(cx.nfail, 1);
+                        rv = p45.x + C0;
+                    }
                 } else {
                     // (s, c) are at the previous iterate; the accepted step |dE| <= tol:
                     // rotate instead of a third range reduction.
@@ -1132,14 +1161,23 @@ __device__ __forceinline__ __attribute__((flatten)) void loglike_tile(const Logl
         // 3b. rare: a solve hit itmax (bit 0 of nfail) — the reference aborts that planet's array there and leaves nu = 0 from
         // that epoch on: the affected points' items are redone now that the first failing epoch per (point, planet) is
         // known — or a solve wandered (bit 1): that point's items are redone with the wandering solves on correctly rounded
-        // sin / cos (eval_item, CR).  Every other solve of those points takes the path it took before: the same bits.
+        // sin / cos (eval_item, CR).  Every other solve of those points takes the path it took before: the same bits.  Where such
+        // a redo itself runs out of steps it lowers the planet's mark, and the pass is repeated until no mark moves.
         if (__builtin_expect(L.nfail[0] != 0, 0)) {                // (cold: the register allocator is to favour the item loop)
-            for (int i = base + tid; i < cend; i += NT) {
-                const int pl = i / a.Ne;
-                if (L.anyfail[pl] || contrib[i - base] != contrib[i - base])       // a point with an itmax failure; an item left as NaN
-                    contrib[i - base] = eval_item<PREC, true, EXTRAS, PREC == RVLL_PREC_FP64, NP>(a, cx, pl, i - pl * a.Ne);
+            for (;;) {
+                for (int i = base + tid; i < cend; i += NT) {
+                    const int pl = i / a.Ne;
+                    if (L.anyfail[pl] || contrib[i - base] != contrib[i - base])       // a point with an itmax failure; an item left as NaN
+                        contrib[i - base] = eval_item<PREC, true, EXTRAS, PREC == RVLL_PREC_FP64, NP>(a, cx, pl, i - pl * a.Ne);
+                }
+                __syncthreads();
+                // a correctly rounded redo lowered a mark (eval_item, CR): the items of that point once more, until no pass does —
+                // the last pass reads marks nobody moves, and every item of a marked point is evaluated in it
+                if (PREC != RVLL_PREC_FP64 || !(L.nfail[0] & 4)) break;
+                __syncthreads();
+                if (tid == 0) L.nfail[0] &= ~4;
+                __syncthreads();
             }
-            __syncthreads();
         }
         // 3c. per-point partial sums of this window, fixed order (deterministic): the part of each point that
         // lies in the window, slice by slice

@@ -90,7 +90,12 @@ extern "C" {
                                      * WITHOUT this bit agrees with the reference to <= 1e-10; a point with it to what
                                      * the reference agrees with itself.  SURVEY 0.3 / 5: the per-point flag the
                                      * reference lacks (it ignores the solver's return code, rvmodel/__init__.py:488-492).
-                                     * With RVLL_FLAG_INVALID_ORBIT set, only that bit is reported. */
+                                     * With RVLL_FLAG_INVALID_ORBIT set, only that bit is reported.
+                                     * Such a solve is done again with correctly rounded sin / cos (rvll_set_wander_exact).
+                                     * With 9 < itmax that redo can run out of steps where the first try converged: the
+                                     * planet's array is then abandoned from the earliest epoch at which EITHER try ran out
+                                     * (RVLL_FLAG_NONCONVERGED is set) — a function of the point alone, whatever the kernel
+                                     * form and tiling. */
 
 /* ---- parameter slot: where a model scalar comes from ------------------- */
 /* idx >= 0 : free parameter, value = theta[idx]   (theta ordered as sorted(parnames),
