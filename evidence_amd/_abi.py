@@ -233,6 +233,9 @@ PROTOTYPES = {
                                        C.POINTER(C.c_int64), C.c_int64, C.POINTER(DrawTiming)]),
     "rvll_kep_rv_bands": (C.c_int, [Handle, _dp, C.c_int64, C.c_int32, _dp, C.c_int32, C.c_uint32, _dp, C.c_int32, _dp, _dp, _ip,
                                     C.c_int64, _dp]),
+    "rvll_residuals_batch": (C.c_int, [Handle, _dp, C.c_int64, C.c_uint32, _dp, _dp]),
+    "rvll_gls_bands": (C.c_int, [Handle, _dp, C.c_int64, C.c_int32, C.c_uint32, C.c_double, C.c_double, C.c_int32, _dp, C.c_int32,
+                                 _dp, _dp, _ip, _ip, _dp, _dp, C.c_int64, _dp]),
     "rvll_region_draw_runs": (C.c_int, [Handle, _dp, C.POINTER(C.c_int64), C.c_int64, _dp, _dp, _dp, C.POINTER(C.c_uint64), _ip,
                                         C.c_int32, C.c_int64, C.c_int64, C.c_int32, _dp, _dp, _dp, _ip, C.POINTER(C.c_int64),
                                         C.c_int64, _dp, _ip, _ip, _dp, C.POINTER(C.c_int64), _ip]),

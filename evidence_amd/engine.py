@@ -269,6 +269,72 @@ class GpuRVModel:
             timing.update(curves_ms=float(ms[0]), sort_ms=float(ms[1]))
         return q, mean, nv
 
+    # ---- residuals of the likelihood's model and their periodograms (periodogram.py) -------------
+    def _keep_mask(self, keep_planet):
+        """The planets that are subtracted: all, or all but keep_planet (1-based; kep_rv_batch's exclude_planet semantics)."""
+        if not (keep_planet is None or type(keep_planet) is int):
+            raise AssertionError(f"keep_planet has to be an {int}, got {type(keep_planet)}.")
+        mask = (1 << self.nplanets) - 1
+        if keep_planet is not None and 1 <= keep_planet <= self.nplanets:
+            mask &= ~(1 << (keep_planet - 1))
+        return mask
+
+    def residuals_batch(self, X, keep_planet=None):
+        """`res` and `noise` of RVModel.log_likelihood (rvmodel/__init__.py:180-215) for every row of X -> (res [n, Ne], var
+        [n, Ne]): the data minus the instruments' offsets, the Keplerian sum (kep_rv_batch(X, table.time, keep_planet), bit for
+        bit), the drift and the linear terms; var = svrad² (+ jitter²).  keep_planet=p leaves planet p in the residuals.  An
+        invalid orbit gives a NaN row of res.  periodogram.residuals_definition holds the definition."""
+        X = self._theta2d(np.atleast_2d(np.asarray(X, dtype=np.float64)))
+        ne = self.table.time.shape[0]
+        res, var = np.empty((X.shape[0], ne)), np.empty((X.shape[0], ne))
+        _abi.check(self._lib.rvll_residuals_batch(self._h, _abi.as_dp(X), X.shape[0], int(self._keep_mask(keep_planet)),
+                                                  _abi.as_dp(res), _abi.as_dp(var)))
+        return res, var
+
+    def gls_bands(self, theta, f0, df, nfreq, levels, keep_planet=None, return_power=False, chunk_bytes=None, timing=None):
+        """Generalised Lomb-Scargle periodograms of the residuals of groups of parameter vectors and their order statistics
+        (periodogram.gls_definition and predictive.bands_definition hold the definitions; rvll_gls_bands): theta [G, n, ndim]
+        is G groups of n rows (n <= 4096), the grid f0 + df k for k < nfreq, levels up to 16 numbers in (0, 1).  Returns a dict:
+        q [G, len(levels), F], mean [G, F], n_valid int32 [G, F] over every group's powers per frequency, peak_index int32
+        [G, n] (the first index of a row's largest power; -1 for an invalid orbit), peak_power [G, n], and with return_power
+        power [G, n, F].  chunk_bytes bounds the device buffers of a chunk of groups (default 256 MiB, at least one group); no
+        result depends on it.  timing: a dict that receives residuals_ms, gls_ms and reduce_ms."""
+        from .periodogram import check_grid
+        from .predictive import check_levels
+        theta = np.ascontiguousarray(theta, dtype=np.float64)
+        if theta.ndim != 3 or theta.shape[2] != self.ndim:
+            raise ValueError(f"expected an array of shape (groups, n, {self.ndim}), got {theta.shape}")
+        G, n = theta.shape[:2]
+        if not 1 <= n <= 4096:
+            raise ValueError("a group holds 1 to 4096 rows")
+        levels = check_levels(levels)
+        f0, df, F = check_grid(f0, df, nfreq, self.table.time.shape[0])
+        mask = self._keep_mask(keep_planet)
+        Q = levels.shape[0]
+        q, mean, nv = np.empty((G, Q, F)), np.empty((G, F)), np.empty((G, F), dtype=np.int32)
+        pidx, ppow = np.empty((G, n), dtype=np.int32), np.empty((G, n))
+        power = np.empty((G, n, F)) if return_power else None
+        ms = np.zeros(3)
+        _abi.check(self._lib.rvll_gls_bands(self._h, _abi.as_dp(theta), G, n, int(mask), f0, df, F, _abi.as_dp(levels), Q,
+                                            _abi.as_dp(q), _abi.as_dp(mean), _abi.as_ip(nv), _abi.as_ip(pidx), _abi.as_dp(ppow),
+                                            _abi.as_dp(power) if return_power else None, int(chunk_bytes or 0), _abi.as_dp(ms)))
+        if timing is not None:
+            timing.update(residuals_ms=float(ms[0]), gls_ms=float(ms[1]), reduce_ms=float(ms[2]))
+        out = dict(q=q, mean=mean, n_valid=nv, peak_index=pidx, peak_power=ppow)
+        if return_power:
+            out["power"] = power
+        return out
+
+    def gls_batch(self, X, f0, df, nfreq, keep_planet=None):
+        """The periodogram of every row's residuals -> power [n, F]: gls_bands' powers, the rows sent as groups of up to 4096
+        (a power's bits depend on its row and frequency alone)."""
+        X = self._theta2d(np.atleast_2d(np.asarray(X, dtype=np.float64)))
+        out = []
+        for lo in range(0, X.shape[0], 4096):
+            part = X[lo:lo + 4096]
+            out.append(self.gls_bands(part[None], f0, df, nfreq, [0.5], keep_planet=keep_planet, return_power=True)["power"][0])
+        return np.concatenate(out, axis=0) if out else np.empty((0, int(nfreq)))
+
     # ---- prior transform --------------------------------------------------------------------
     def prior_transform_batch(self, cubes):
         cubes = self._theta2d(cubes)

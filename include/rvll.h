@@ -590,6 +590,30 @@ int rvll_kep_rv_bands(rvll_handle* h, const double* theta /*[n_groups * n, ndim]
                       double* q /*[n_groups, n_q, n_times]*/, double* mean /*[n_groups, n_times]*/,
                       int32_t* n_valid /*[n_groups, n_times]*/, int64_t chunk_bytes, double* phase_ms /*NULL or [2]*/);
 
+/* ---- residuals of the likelihood's model and their periodograms (post-processing; evidence_amd/periodogram.py) ---- */
+/* res[b][j] and var[b][j] are `res` and `noise` of RVModel.log_likelihood (evidence/rvmodel/__init__.py:180-215) for theta[b] at
+ * epoch j of the resident table: the datum minus the instrument's offset, the Keplerian sum of the planets in include_mask
+ * (rvll_kep_rv_batch's value at the table's times, bit for bit), the drift about drift_tref or the table's first time, and the
+ * linear terms, added in that order; var = svrad^2 (+ jitter^2 of the instrument).  An invalid orbit gives a NaN row of res.
+ * Nothing is uploaded except theta.                                                                                        */
+int rvll_residuals_batch(rvll_handle* h, const double* theta, int64_t B, uint32_t include_mask, double* res /*[B, Ne]*/,
+                         double* var /*[B, Ne]*/);
+
+/* Generalised Lomb-Scargle powers (floating mean, Zechmeister & Kuerster 2009) of those residuals on the uniform grid
+ * f_k = f0 + df k, k < n_freq, with weights 1 / var, and per group of n rows what rvll_kep_rv_bands gives with the frequencies in
+ * the place of times: q, mean, n_valid.  peak_index[g][i] is the first index of row i's largest power (a NaN power counts as the
+ * largest) and peak_power the power there; -1 and NaN for a row whose powers are all NaN (an invalid orbit).  power_out (may be NULL) receives every
+ * power.  A power is NaN where YY D is not > 0.  The work goes in chunks of whole groups whose powers and weights take at most
+ * chunk_bytes (0: 256 MiB; at least one group); no result depends on it, nor on the other rows or groups of the call.  phase_ms
+ * (may be NULL) receives the HIP-event times of the residual stage, the periodogram kernel and the reductions.
+ * RVLL_E_INVALID: f0 or df not positive and finite, n_freq outside [1, 2^24], fewer than 4 epochs, n outside [1, 4096], n_q
+ * outside [1, 16], a level outside (0, 1), a negative size, null buffers.                                                   */
+int rvll_gls_bands(rvll_handle* h, const double* theta /*[n_groups * n, ndim]*/, int64_t n_groups, int32_t n, uint32_t include_mask,
+                   double f0, double df, int32_t n_freq, const double* levels /*[n_q]*/, int32_t n_q,
+                   double* q /*[n_groups, n_q, n_freq]*/, double* mean /*[n_groups, n_freq]*/, int32_t* n_valid /*[n_groups, n_freq]*/,
+                   int32_t* peak_index /*[n_groups, n]*/, double* peak_power /*[n_groups, n]*/,
+                   double* power_out /*NULL or [n_groups, n, n_freq]*/, int64_t chunk_bytes, double* phase_ms /*NULL or [3]*/);
+
 /* ---- FIP periodogram accumulation (post-processing; independent of any model handle) ------------ */
 /* Replaces the accumulation loop of evidence/fip_criterion.py:305-339.  The caller flattens the posterior
  * samples of all planet models of one run into rows, in the reference's loop order (kmod = 1.., then sample
