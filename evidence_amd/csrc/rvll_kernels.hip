@@ -430,6 +430,8 @@ void debug_eval_kernel(int op, const double* x, const double* y, long long n, do
             const f32x2 qf = div_f32x2(f32x2{nf, 3.0f * nf}, f32x2{df, 2.0f - df});
             r = (double)(op == 34 ? qf.x : qf.y);
             break; }
+        // the rotation between Newton steps: the pair at x rotated by y (tests/test_gpu_rotate.py)
+        case 36: case 37: sincos_f64(a, s, c); rotate_mid(b, s, c); r = op == 36 ? s : c; break;
         default: r = NAN; break;
         }
         out[i] = r;

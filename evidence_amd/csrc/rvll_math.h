@@ -626,6 +626,88 @@ RVLL_HD void rotate_small(double h, double& s, double& c)
     c = c0 + __builtin_fma(c0, ch1, -(s0 * sh));
 }
 
+// ---- the pair at E + h from the pair at E, between Newton steps --------------------------------------------------------------
+// From its second evaluation on a Newton solve wants (sin, cos) at E + h with (sin E, cos E) in registers and h, the step just
+// taken, known: the pair at E + h is the old pair rotated by h, and sin h, cos h - 1 need no range reduction, no quadrant and
+// no selects: s' = s + (s (cos h - 1) + c sin h), c' = c + (c (cos h - 1) - s sin h), two FMAs each.
+//
+// rotate_mid, |h| <= pi/4: the two minimax kernels of sincos_kernel on h itself — the same coefficients, the same chains —
+// stopped before the cosine's last fma(z, pc, 1.0): sh = h + h z ps, cm1 = z pc.  15 + 4 instructions, all fp64.
+RVLL_HD void rotate_mid(double h, double& s, double& c, const SincosConsts& k)
+{
+    const double S1 = k.S1, S2 = k.S2, S3 = k.S3, S4 = k.S4, S5 = k.S5, S6 = k.S6;
+    const double C1 = k.C1, C2 = k.C2, C3 = k.C3, C4 = k.C4, C5 = k.C5, C6 = k.C6;
+    double sh, cm1;
+#if defined(__HIP_DEVICE_COMPILE__)
+    double z, t;
+    asm("v_mul_f64 %2, %4, %4\n\t"
+        "v_fma_f64 %0, %2, %10, %9\n\t"
+        "v_fma_f64 %1, %2, %16, %15\n\t"
+        "v_fma_f64 %0, %2, %0, %8\n\t"
+        "v_fma_f64 %1, %2, %1, %14\n\t"
+        "v_fma_f64 %0, %2, %0, %7\n\t"
+        "v_fma_f64 %1, %2, %1, %13\n\t"
+        "v_fma_f64 %0, %2, %0, %6\n\t"
+        "v_fma_f64 %1, %2, %1, %12\n\t"
+        "v_fma_f64 %0, %2, %0, %5\n\t"
+        "v_fma_f64 %1, %2, %1, %11\n\t"
+        "v_mul_f64 %3, %4, %2\n\t"
+        "v_fma_f64 %1, %2, %1, -0.5\n\t"
+        "v_fma_f64 %0, %3, %0, %4\n\t"
+        "v_mul_f64 %1, %2, %1"
+        : "=&v"(sh), "=&v"(cm1), "=&v"(z), "=&v"(t)
+        : "v"(h), "s"(S1), "s"(S2), "s"(S3), "s"(S4), "s"(S5), "v"(S6),
+          "s"(C1), "s"(C2), "s"(C3), "s"(C4), "s"(C5), "v"(C6));      // one scalar operand per VALU instruction
+#else
+    const double z = h * h;
+    double ps = __builtin_fma(z, S6, S5);
+    double pc = __builtin_fma(z, C6, C5);
+    ps = __builtin_fma(z, ps, S4);
+    pc = __builtin_fma(z, pc, C4);
+    ps = __builtin_fma(z, ps, S3);
+    pc = __builtin_fma(z, pc, C3);
+    ps = __builtin_fma(z, ps, S2);
+    pc = __builtin_fma(z, pc, C2);
+    ps = __builtin_fma(z, ps, S1);
+    pc = __builtin_fma(z, pc, C1);
+    const double t = h * z;
+    pc = __builtin_fma(z, pc, -0.5);
+    sh = __builtin_fma(t, ps, h);
+    cm1 = z * pc;
+#endif
+    const double s0 = s, c0 = c;
+    s = __builtin_fma(c0, sh, __builtin_fma(s0, cm1, s0));
+    c = __builtin_fma(-s0, sh, __builtin_fma(c0, cm1, c0));
+}
+
+RVLL_HD void rotate_mid(double h, double& s, double& c) { rotate_mid(h, s, c, sincos_consts()); }
+
+constexpr double kRotateMidMax = 7.85398163397448279e-01;       // the double below pi/4
+
+// (sin, cos) at the new iterate E (= the old one + h) of Newton step k from the pair at the old iterate.  k = 0, the evaluation
+// at the start, has no old pair and takes the full routine; every later one rotates, and a lane whose step is beyond pi/4 — or
+// NaN — does the evaluation again the full way.  A function of (h, k) and the old pair alone: whatever shares the wave.
+// The rotation is computed for EVERY lane and the full routine sits behind an unlikely branch, so a wave stays on the straight
+// line: from E = M the first step is at most e / sqrt(1 - e^2) <= pi/4 for e <= 0.617 and later steps shrink quadratically, so
+// under cfg3's priors 96 % of the planets never leave it.  Choosing between the two per lane by an if / else (with or without an
+// eccentricity class in front, with or without a shorter series for |h| <= 2^-6) costs more in mask arithmetic and branches than
+// the rotation saves: profiles/r05_newton_rotation.txt.
+// CHECKED: the full routine is sincos_any (any finite argument), else sincos_f64 (|E| < 2^50: the same bits there).
+template <bool CHECKED>
+RVLL_HD void newton_next_sincos(double E, double h, int k, double& s, double& c, const SincosConsts& kc)
+{
+    if (k == 0) {
+        if constexpr (CHECKED) sincos_any(E, s, c, kc);
+        else                   sincos_f64(E, s, c, kc);
+    } else {
+        rotate_mid(h, s, c, kc);
+        if (__builtin_expect(!(__builtin_fabs(h) <= kRotateMidMax), 0)) {
+            if constexpr (CHECKED) sincos_any(E, s, c, kc);
+            else                   sincos_f64(E, s, c, kc);
+        }
+    }
+}
+
 // (sin r, cos r) of the reduced argument -> (sin x, cos x) by the quadrant: swap and signs with bit operations (compare +
 // v_cndmask cost ~4 cycles each, measured)
 RVLL_HD void quadrant_f32(float sr, float cr, uint32_t uq, float& s_out, float& c_out)

@@ -338,7 +338,8 @@ __device__ __forceinline__ double eval_item(const LoglikeArgs& a, const ItemCtx&
                 if (shortcut) {
                     int steps = 0;
                     do {
-                        sincos_f64(E, s, c, kc);
+                        // from the second evaluation on the pair is rotated by the step just taken (rvll_math.h)
+                        newton_next_sincos<false>(E, dE, steps, s, c, kc);
                         const double f  = E - ec * s - M;
                         const double fp = 1 - ec * c;
                         const double En = E - div_exact(f, fp);        // == f / fp, correctly rounded
@@ -354,7 +355,7 @@ __device__ __forceinline__ double eval_item(const LoglikeArgs& a, const ItemCtx&
                     if (!shortcut && a.itmax > kSafeSteps) {
                         int steps = 0;
                         do {
-                            sincos_any(E, s, c, kc);
+                            newton_next_sincos<true>(E, dE, steps, s, c, kc);
                             const double f  = E - ec * s - M;
                             const double fp = 1 - ec * c;
                             const double En = E - div_exact(f, fp);
@@ -384,8 +385,10 @@ __device__ __forceinline__ double eval_item(const LoglikeArgs& a, const ItemCtx&
 #ifdef RVLL_CR_FAKE                // (measurement builds only: the redo pass with the ordinary sin / cos — what the correctly rounded pair costs)
                         sincos_any(E, s, c, kc);
 #else
-                        if constexpr (CR) sincos_cr(E, s, c);
-                        else              sincos_any(E, s, c, kc);
+                        // (below kSafeSteps — the shortcut is off — the pair of step k is the shortcut loop's: the same rule)
+                        if constexpr (CR)            sincos_cr(E, s, c);
+                        else if (steps < kSafeSteps) newton_next_sincos<true>(E, dE, steps, s, c, kc);
+                        else                         sincos_any(E, s, c, kc);
 #endif
                         const double f  = E - ec * s - M;
                         const double fp = 1 - ec * c;
