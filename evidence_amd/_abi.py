@@ -106,6 +106,12 @@ class PosteriorTiming(C.Structure):
                 ("threads", C.c_int32), ("blocks", C.c_int32), ("reserved", C.c_int32)]
 
 
+class PointwiseTiming(C.Structure):
+    _fields_ = [("kernel_ms", C.c_double), ("total_ms", C.c_double), ("setup_ms", C.c_double), ("weights_ms", C.c_double),
+                ("reduce_ms", C.c_double), ("rows", C.c_int64), ("elements", C.c_int64), ("columns", C.c_int64),
+                ("launches", C.c_int32), ("threads", C.c_int32), ("blocks", C.c_int32), ("slabs", C.c_int32)]
+
+
 class FipMergedTiming(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("total_ms", C.c_double), ("setup_ms", C.c_double), ("weights_ms", C.c_double),
                 ("reduce_ms", C.c_double), ("rows", C.c_int64), ("elements", C.c_int64), ("events", C.c_int64),
@@ -221,6 +227,10 @@ PROTOTYPES = {
     "rvll_posterior_replicates": (C.c_int, [C.c_int32, _dp, _dp, C.c_int64, C.POINTER(C.c_int64), C.c_int32, _dp, C.c_int32, _dp,
                                             C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, _dp, _dp, _dp, _dp, _dp,
                                             C.c_int64, C.POINTER(PosteriorTiming)]),
+    "rvll_pointwise_replicates": (C.c_int, [C.c_int32, _dp, _dp, C.c_int64, C.POINTER(C.c_int64), C.c_int32, _dp, C.c_int32, _dp,
+                                            C.c_int32, C.c_int32, C.c_int32, C.c_uint64, _dp, _dp, _dp, _dp, _dp, _dp,
+                                            C.c_int64, C.POINTER(PointwiseTiming)]),
+    "rvll_pointwise_slab_rows": (C.c_int, [_ip]),
     "rvll_fip_replicates": (C.c_int, [C.c_int32, _dp, _dp, C.c_int64, C.POINTER(C.c_int64), C.c_int32, _dp, C.c_int32, _dp, _dp,
                                       C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, _dp, _dp, _dp, C.c_int64,
                                       C.POINTER(FipMergedTiming)]),

@@ -66,7 +66,8 @@ extern "C" {
                                        rvll_fip_replicates (rvll_fip_merged_timing),
                                        rvll_marginal_replicates (rvll_marginal_timing),
                                        rvll_region_draw_runs, rvll_region_tile_rows,
-                                       rvll_draw_replicates (rvll_draw_timing), rvll_kep_rv_bands */
+                                       rvll_draw_replicates (rvll_draw_timing), rvll_kep_rv_bands,
+                                       rvll_pointwise_replicates (rvll_pointwise_timing), rvll_pointwise_slab_rows */
 
 /* ---- error codes ------------------------------------------------------ */
 #define RVLL_OK             0
@@ -757,6 +758,49 @@ int rvll_posterior_replicates(int32_t device, const double* logl /*[n_rows]*/, c
                               double* logz /*[nsamples]*/, double* info /*[nsamples]*/, double* mean /*[nsamples * n_cols]*/,
                               double* sd /*[nsamples * n_cols]*/, double* quant /*[nsamples * n_q * n_cols]*/,
                               int64_t block_bytes, rvll_posterior_timing* timing);
+
+/* ---- pointwise predictive checks of the merged run's replicates (post-processing; independent of any model handle) */
+/* Per replicate s of rvll_merge_replicates (same seeds, multiplicities and merged order) and per unit u of table [n_rows,
+ * n_units] (row-major, in input row order: the log-likelihood of the unit's data in the row), with p_i = exp(logwt_i) (0 for a
+ * row without weight), P = sum p, t the unit's value in merged row i and the call's shifts [3, n_units] = (c, d, a)
+ * (evidence_amd/pointwise.py is the definition and computes the shifts):
+ *     lpd [s * n_units + u] = c_u + log(sum p exp(min(t - c_u, 0)) / P)     the in-sample log predictive density
+ *     loo [s * n_units + u] = d_u - log(sum p exp(min(d_u - t, 0)) / P)     the importance-sampling leave-one-out value
+ *     mean[s * n_units + u] = a_u + sum p (t - a_u) / P
+ *     var [s * n_units + u] = sum p (t - a_u)^2 / P - (sum p (t - a_u) / P)^2     the WAIC correction
+ * and logz[s], info[s] as rvll_merge_replicates gives them.  With c_u >= t and d_u <= t on every row with weight the two min
+ * change nothing; they keep exp finite on the others.  The sums are one fp64 product on the matrix units, [replicates, n_rows]
+ * by [n_rows, 4 n_units + 1], cut along n_rows into slabs of rvll_pointwise_slab_rows rows (a constant) that are added in
+ * rising order: a result depends on the input, the seed and the replicate's index, not on the batching, on the other units of
+ * the call or on the call.  P is a column of that product, so a unit whose t is one constant v (and c = d = a = v) gives lpd =
+ * loo = mean = v exactly and var = 0.  A replicate in which no row has weight gives NaN.
+ * block_bytes bounds the operand (8 bytes * (n_rows rounded up to 64) * (4 n_units + 1 rounded up to 64)), the partial sums
+ * of 64 replicates (8 * 64 * slabs * columns) and the block of replicates (8 * (n_rows + slabs * columns) each); 0 stands for
+ * the first two plus 8 GiB.  RVLL_E_NOMEM before any work when these and one replicate do not fit.
+ * RVLL_E_INVALID: everything rvll_merge_replicates refuses; n_units outside [1, 4096]; a table value or a shift that is not
+ * finite or is beyond 1e30 in size; null buffers.  timing may be NULL.  device < 0 uses the current device. */
+typedef struct rvll_pointwise_timing {
+    double  kernel_ms;       /* HIP-event time of all device work: setup_ms + weights_ms + reduce_ms                       */
+    double  total_ms;        /* the whole call: checks, allocation, uploads, kernels, downloads                            */
+    double  setup_ms;        /* the merge's setup and the kernel that writes the operand                                    */
+    double  weights_ms;      /* the replicate kernels (what rvll_merge_replicates spends on the same input)                 */
+    double  reduce_ms;       /* exp of the block, the product and the kernel that adds the slabs                            */
+    int64_t rows;            /* n_rows                                                                                      */
+    int64_t elements;        /* (row, replicate) pairs: n_rows * nsamples                                                   */
+    int64_t columns;         /* 4 * n_units + 1: the product takes 2 * elements * columns operations                        */
+    int32_t launches;        /* 5 for the setup, then 4 a block of replicates (a rocPRIM sort counted as one)               */
+    int32_t threads;         /* per workgroup                                                                               */
+    int32_t blocks;          /* blocks of replicates the call was split into                                                */
+    int32_t slabs;           /* slabs of rows: n_rows over rvll_pointwise_slab_rows, rounded up                             */
+} rvll_pointwise_timing;
+int rvll_pointwise_replicates(int32_t device, const double* logl /*[n_rows]*/, const double* birth /*[n_rows]*/, int64_t n_rows,
+                              const int64_t* run_start /*[n_runs + 1]*/, int32_t n_runs,
+                              const double* table /*[n_rows * n_units]*/, int32_t n_units, const double* shifts /*[3 * n_units]*/,
+                              int32_t nsamples, int32_t mode, int32_t bootstrap, uint64_t seed,
+                              double* logz /*[nsamples]*/, double* info /*[nsamples]*/, double* lpd /*[nsamples * n_units]*/,
+                              double* loo /*[nsamples * n_units]*/, double* mean /*[nsamples * n_units]*/,
+                              double* var /*[nsamples * n_units]*/, int64_t block_bytes, rvll_pointwise_timing* timing);
+int rvll_pointwise_slab_rows(int32_t* rows);
 
 /* ---- FIP periodogram of the merged run's replicates (post-processing; independent of any model handle) ----------- */
 /* Per replicate s of rvll_merge_replicates (same seeds, multiplicities and merged order) the true inclusion probability of
