@@ -9,6 +9,7 @@ writes small fixtures (inputs + expected outputs) next to this file:
     loglike_51peg.npz/.json the shipped 51Peg example, both configs
     priors.npz/.json        .ppf of every working distribution on a q grid (§8c.4)
     keprv.npz/.json         kep_rv(exclude_planet) / modelk(planet) curves at arbitrary times (§8f.3)
+    keprv_edges.npz/.json   the same curves for every parametrisation of loglike_edges.npz that has a planet
     loglike_high_ecc.npz    eccentricity sweep 0.90 .. 0.9925 (the solver's sensitive corner)
     loglike_wild.npz        adversarial parameter ranges (tiny / huge periods and amplitudes, invalid orbits, zero jitter)
 
@@ -359,6 +360,68 @@ def gen_keprv():
     (HERE / "keprv.json").write_text(json.dumps(meta, indent=1))
 
 
+KEPRV_EDGE_ROWS = 6
+KEPRV_EDGE_FAR = ("logk1_logperiod_ml0", "secos_sesin_ml0", "free_epoch")
+
+
+def edge_models():
+    """(case, the reference's RVModel of it) for every case of loglike_edges.npz, as gen_edges built them (the time column's
+    name and the linear series included)."""
+    sys.path.insert(0, str(REPO / "tests"))
+    import golden
+    time_key = {m["name"]: m["time_key"] for m in json.loads((HERE / "loglike_edges.json").read_text())}
+    for case in golden.edge_cases():
+        model = RVModel(dict(case.fixed), ref_datadict(case.table, time_key[case.name]), list(case.parnames))
+        assert model.parnames == case.parnames and np.array_equal(model.time, case.table.time)
+        if case.linpar:
+            model.linpar_dict = {k: np.asarray(v, dtype=float) for k, v in case.linpar.items()}
+        yield case, model
+
+
+def ref_pardict(model, x):
+    pardict = {name: x[i] for i, name in enumerate(model.parnames)}
+    pardict.update(model.fixedpardict)
+    return pardict
+
+
+def gen_keprv_edges():
+    """kep_rv / kep_rv(exclude_planet=p) / modelk(planet=p) of every parametrisation of loglike_edges.npz that has a planet, for
+    the first rows of its theta, at 41 times from 400.3 d before the first epoch to 777.7 d after the last (none of them a data
+    epoch, the earliest before the planets' epochs: negative phases), and for three cases at +-1e5 d besides.  Where the
+    reference returns None (an invalid orbit) the row is NaN."""
+    arrays, meta = {}, []
+    for case, model in edge_models():
+        npl = model.nplanets
+        if npl < 1:
+            continue
+        theta = case.theta[:KEPRV_EDGE_ROWS]
+        t = case.table.time
+        times = np.linspace(t.min() - 400.3, t.max() + 777.7, 41)
+        if case.name in KEPRV_EDGE_FAR:
+            times = np.concatenate([times, [t.min() - 1e5, t.max() + 1e5]])
+        assert not np.isin(times, t).any()
+        curves = {}
+
+        def put(key, val):
+            curves.setdefault(key, []).append(np.full(times.shape, np.nan) if val is None else np.asarray(val, dtype=float))
+
+        for x in theta:
+            pardict = ref_pardict(model, x)
+            put("exNone", model.kep_rv(pardict, times))
+            for p in range(1, npl + 1):
+                put(f"ex{p}", model.kep_rv(pardict, times, exclude_planet=p))
+                put(f"pl{p}", model.modelk(pardict, times, planet=p))
+        arrays[f"{case.name}_theta"], arrays[f"{case.name}_times"] = theta, times
+        for key, rows in curves.items():
+            arrays[f"{case.name}_{key}"] = np.array(rows)
+        nan_rows = int(np.isnan(arrays[f"{case.name}_exNone"]).all(axis=1).sum())
+        meta.append(dict(name=case.name, nplanets=npl, keys=sorted(curves), far=case.name in KEPRV_EDGE_FAR))
+        print(f"keprv edge {case.name:34s} {theta.shape[0]} rows x {len(times)} times, {len(curves)} kinds, {nan_rows} NaN rows")
+    np.savez_compressed(HERE / "keprv_edges.npz", **arrays)
+    (HERE / "keprv_edges.json").write_text(json.dumps(meta, indent=1))
+    print("wrote keprv_edges.npz", (HERE / "keprv_edges.npz").stat().st_size, "bytes")
+
+
 def gen_high_ecc():
     """The solver's sensitive corner: Newton from E = M at eccentricities near the 0.99 clamp wanders before it settles
     (6 .. 1159 steps) and amplifies any difference in an iterate.  A sweep of 10 eccentricities x 24 points on
@@ -419,7 +482,7 @@ def gen_wild():
 
 
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["configs", "edges", "51peg", "priors", "keprv", "high_ecc", "wild"]
+    which = sys.argv[1:] or ["configs", "edges", "51peg", "priors", "keprv", "high_ecc", "wild", "keprv_edges"]
     if "wild" in which: gen_wild()
     if "high_ecc" in which: gen_high_ecc()
     if "configs" in which: gen_configs()
@@ -427,3 +490,4 @@ if __name__ == "__main__":
     if "51peg" in which: gen_51peg()
     if "priors" in which: gen_priors()
     if "keprv" in which: gen_keprv()
+    if "keprv_edges" in which: gen_keprv_edges()      # reads loglike_edges.npz: after "edges"

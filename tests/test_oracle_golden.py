@@ -103,3 +103,59 @@ def test_the_references_value_is_conditioned_worse_than_the_bar_near_the_clamp()
     assert cond[ecc <= 0.965].max() <= 1e-13
     assert 1e-11 <= cond[ecc >= 0.975].max() <= 5e-9
     assert np.array_equal(om.loglike(case.theta), om.loglike(case.theta))          # and the probe leaves no trace
+
+
+def _oracle_curves(layout, table, theta, times, nplanets, keys):
+    om = orc.OracleModel(layout, table)
+    return {key: om.kep_rv(theta, times, golden.curve_mask(nplanets, key)) for key in keys}
+
+
+def test_oracle_curves_match_the_references_on_the_configurations():
+    """OracleModel.kep_rv, the reference of the host and device tests of everything built on curves, against keprv.npz."""
+    import json
+    from evidence_amd.layout import compile_layout
+    from evidence_amd.synthetic import make_workload
+    z = np.load(golden.GOLDEN / "keprv.npz")
+    for meta in json.loads((golden.GOLDEN / "keprv.json").read_text()):
+        cfg = meta["cfg"]
+        w = make_workload(cfg)
+        layout = compile_layout(list(w.parnames), dict(w.fixedpardict), w.table.insts, [])
+        got = _oracle_curves(layout, w.table, z[f"cfg{cfg}_theta"], z[f"cfg{cfg}_times"], meta["nplanets"], meta["keys"])
+        for key in meta["keys"]:
+            ref = z[f"cfg{cfg}_{key}"]
+            err = float(np.max(np.abs(got[key] - ref)))
+            print(f"cfg{cfg} {key}: largest |oracle - reference| {err:.3e}")
+            assert got[key].shape == ref.shape and err <= 1e-13 * max(1.0, np.abs(ref).max()), (cfg, key, err)
+
+
+KEPRV_EDGES = golden.keprv_edge_cases()
+
+
+def test_the_curve_fixture_covers_every_edge_case_with_a_planet():
+    want = [c.name for c in golden.edge_cases() if c.layout.nplanets >= 1]
+    assert [cc.name for cc in KEPRV_EDGES] == want and len(want) == 34
+    for cc in KEPRV_EDGES:
+        t = cc.case.table.time
+        assert cc.theta.shape[0] == min(6, cc.case.theta.shape[0]) and np.array_equal(cc.theta, cc.case.theta[:6])
+        assert np.array_equal(cc.times[:41], np.linspace(t.min() - 400.3, t.max() + 777.7, 41)) and not np.isin(cc.times, t).any()
+        assert cc.far == (cc.name in ("logk1_logperiod_ml0", "secos_sesin_ml0", "free_epoch"))
+        assert np.array_equal(cc.times[41:], [t.min() - 1e5, t.max() + 1e5] if cc.far else [])
+        assert sorted(cc.curves) == sorted(["exNone"] + [f"{k}{p}" for k in ("ex", "pl") for p in range(1, cc.nplanets + 1)])
+        epoch = golden.decode_planets(cc.case, cc.theta)["epoch"]
+        assert cc.times.min() < epoch.min()                                # negative phases
+
+
+@pytest.mark.parametrize("cc", KEPRV_EDGES, ids=[cc.name for cc in KEPRV_EDGES])
+def test_oracle_curves_match_the_references_on_every_model_form(cc):
+    """... against keprv_edges.npz within golden.curve_bound, the bound the device is held to (tests/test_gpu_model_forms.py):
+    the reference route itself stays inside it at every point; NaN rows where the reference returned None."""
+    got = _oracle_curves(cc.case.layout, cc.case.table, cc.theta, cc.times, cc.nplanets, cc.curves)
+    worst = {key: golden.check_curves(cc, key, got[key]) for key in cc.curves}
+    print(cc.name, "largest |oracle - reference| over its bound:", worst)
+    invalid = cc.name.endswith("_invalid")
+    assert golden.decode_planets(cc.case, cc.theta)["valid"].all() != invalid
+    for key, ref in cc.curves.items():
+        included = golden.curve_mask(cc.nplanets, key) != 0
+        assert np.isnan(ref).all() == (invalid and included) and np.isnan(ref).any() == (invalid and included), key
+        if not included:                                                   # kep_rv without its only planet: zeros, valid orbit or not
+            assert np.all(ref == 0.0) and np.all(got[key] == 0.0)
