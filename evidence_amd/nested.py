@@ -137,15 +137,8 @@ def run_nested(prior: Callable, loglike: Callable, ndim: int, nlive: Optional[in
             pool_u, pos = None, 0                                          # refresh the region now and then
         if np.max(logl) + logx < logz + np.log(np.expm1(dlogz)):           # remaining live mass is negligible
             break
-    # final live points share the remaining prior mass
-    logw_live = logx - np.log(max(1, len(logl))) + logl
-    logz_final = np.logaddexp(logz, _logaddexp_many(logw_live))
-    all_theta = np.vstack([np.array(dead_theta).reshape(-1, ndim), theta])
-    all_logl = np.concatenate([dead_logl, logl])
-    all_logw = np.concatenate([dead_logw, logw_live]) - logz_final
-    return NestedResult(float(logz_final), float(np.sqrt(max(h, 0.0) / nlive)), it, ncall, float(h),
-                        all_theta, all_logl, all_logw, nlive=nlive, kbatch=1,
-                        logl_birth=np.concatenate([np.array(dead_birth, dtype=np.float64), birth]))
+    return _finish(logz, h, logx, it, ncall, nlive, 1, [np.array(dead_theta), theta], [np.array(dead_logl, dtype=np.float64)],
+                   [np.array(dead_logw, dtype=np.float64)], logl, [np.array(dead_birth, dtype=np.float64), birth])
 
 
 # --------------------------------------------------------------------------------------------------
@@ -296,13 +289,6 @@ def _default_clusterer(clusterer):
 
 
 # ---- the proposal and PolyChord's stop rule (proposal=, precision_criterion=; DESIGN §4i, stepout.py) ---------------------------
-def _stop(logz, logx, logl, dlogz, precision_criterion):
-    """The stop test of a path that holds the whole live log-L array: the dlogz test, or PolyChord's rule when given."""
-    if precision_criterion is not None:
-        return _precision_stop(logz, logx, logl, precision_criterion)
-    return bool(np.max(logl) + logx < logz + np.log(np.expm1(dlogz)))
-
-
 def _walk_kwargs(proposal, step_width):
     """The proposal keywords a walker= / walker_runs= / live= call gets: none for the chord walk, so that walker callables
     written before the proposal existed keep working."""
@@ -393,14 +379,193 @@ def _check_region(live, walker, adaptive_nsteps, step_width=1.0):
         raise ValueError('adaptive_nsteps does not apply with proposal="region": a region draw takes no steps')
 
 
+# ---- the steps every driver is built from -----------------------------------------------------------------------
+def _schedule(ndim, nlive, kbatch, nsteps, wrapped):
+    """(nlive, kbatch, nsteps, wrapped) of a slice run: the reference's defaults (nlive = 25 ndim, nsteps = 3 ndim) where an
+    argument is not given, kbatch = nlive // 4, wrapped as a bool array or None."""
+    defaults = ultranest_defaults(ndim)
+    nlive = int(nlive or defaults["nlive"])
+    kbatch = int(kbatch or max(1, nlive // 4))
+    if not 1 <= kbatch < nlive:
+        raise ValueError("need 1 <= kbatch < nlive")
+    return nlive, kbatch, int(nsteps or defaults["nsteps"]), None if wrapped is None else np.asarray(wrapped, dtype=bool)
+
+
+def _evaluator(prior, loglike, prior_loglike):
+    """cand [n, ndim] -> (theta, logl) as float64 arrays: one prior_loglike call when it is given, else prior, then loglike."""
+    def call(cand):
+        if prior_loglike is not None:
+            ct, cl = prior_loglike(cand)                                # one round trip to the GPU
+            return np.asarray(ct, dtype=np.float64), np.asarray(cl, dtype=np.float64)
+        ct = np.asarray(prior(cand), dtype=np.float64)
+        return ct, np.asarray(loglike(ct), dtype=np.float64)            # one batch = one GPU launch
+    return call
+
+
+def _finish(logz, h, logx, niter, ncall, nlive, kbatch, samples, dead_logl, dead_logw, logl, births, timing=None, nclusters=None,
+            nsteps_trace=None, far_fraction=None, region=None):
+    """The result of a run that ended with the evidence state (logz, h, logx) and the live log-L `logl`: the live points share
+    the remaining prior mass.  dead_logl / dead_logw: lists of arrays in death order.  samples: the finished [dead + live, ndim]
+    array (the resident paths fill it from the device), or the list of blocks to stack — the dead blocks, then the live theta.
+    births: the list of blocks likewise, or None (a live set without a record).  nclusters / nsteps_trace / far_fraction: the
+    per-iteration lists, None when the feature is off.  region: (fallbacks, efficiencies, calls, fallback calls)."""
+    logw_live = logx - np.log(max(1, len(logl))) + logl
+    logz_final = np.logaddexp(logz, _logaddexp_many(logw_live))
+    if isinstance(samples, list):
+        samples = np.vstack([a.reshape(-1, samples[-1].shape[1]) for a in samples])
+    fallbacks, eff, rcalls, fallback_calls = region or (None, None, None, None)
+    return NestedResult(float(logz_final), float(np.sqrt(max(h, 0.0) / nlive)), niter, ncall, float(h), samples,
+                        np.concatenate(dead_logl + [logl]), np.concatenate(dead_logw + [logw_live]) - logz_final, timing,
+                        None if nclusters is None else np.array(nclusters, dtype=np.int64), nlive=nlive, kbatch=kbatch,
+                        logl_birth=None if births is None else np.concatenate(births),
+                        nsteps_trace=None if nsteps_trace is None else np.array(nsteps_trace, dtype=np.int64),
+                        far_fraction=None if far_fraction is None else np.array(far_fraction, dtype=np.float64),
+                        region_fallbacks=fallbacks, region_efficiency=None if eff is None else np.array(eff, dtype=np.float64),
+                        region_calls=None if rcalls is None else np.array(rcalls, dtype=np.int64),
+                        region_fallback_calls=fallback_calls)
+
+
+def _stop(logz, logx, top, live_ll, gap, precision_criterion):
+    """The stop test: the live points (highest log-L `top`) can add less than dlogz to ln Z — gap = log(expm1(dlogz)) — or,
+    when precision_criterion is given, PolyChord's rule on the live log-L multiset live_ll."""
+    if precision_criterion is not None:
+        return _precision_stop(logz, logx, live_ll, precision_criterion)
+    return bool(top + logx < logz + gap)
+
+
+class _EnsembleRun:
+    """The state of one run whose evidence sums the host keeps: its generator, the evidence state, the dead lists, and — for
+    the host-managed runs — the live set (u, theta, logl, birth).  The one-run resident paths keep logl alone (host order) or
+    not even that (device order), and theta = None."""
+
+    def __init__(self, seed, nlive, ndim, nsteps=None):
+        self.seed = seed
+        self.rng = np.random.default_rng(seed)
+        self.u = self.rng.random((nlive, ndim))
+        self.theta = self.logl = None
+        self.ncall = nlive
+        self.dead_theta, self.dead_logl, self.dead_logw = [], [], []
+        self.birth, self.dead_birth = np.full(nlive, -np.inf), []
+        self.logz, self.h, self.logx = -np.inf, 0.0, 0.0
+        self.it = 0
+        self.done = False
+        self.timing = {"host_s": 0.0, "walk_s": 0.0, "turns": 0}
+        self.order_s = 0.0                          # the seconds of `order` inside die (a one-run path's timing["order_s"])
+        self.nclusters = []
+        self.nsteps = nsteps                        # this run's step count; adaptive_nsteps: its trace and far fractions
+        self.trace, self.fars = [], []
+        self.fallbacks, self.fallback_calls, self.eff, self.rcalls = 0, 0, [], []      # proposal="region"
+
+    def stream(self, mul):
+        """The seed of this iteration's bootstrap (_BOOT_MUL) or region draw (_REGION_MUL): seed * mul + deaths so far."""
+        return (int(self.seed) * mul + self.it) & _M64
+
+    def order(self, kbatch):
+        """The host's order step: the stable sort of the live log-L; its first kbatch rows die, and what replaces them is
+        born above the highest of them."""
+        order = _stable_argsort(self.logl)
+        dead = order[:kbatch]
+        self.dead_birth.append(self.birth[dead])
+        self.birth[dead] = self.logl[dead[-1]]
+        return order
+
+    def account(self, dl, kbatch, nlive, dead=None):
+        """The evidence sums of an iteration whose dying log-L are dl (ascending), and the dead lists."""
+        logw, self.logz, self.h, self.logx = _deaths(self.logz, self.h, self.logx, dl, nlive, kbatch)
+        if self.theta is not None:
+            self.dead_theta.append(self.theta[dead])                   # (index arrays: already copies)
+        self.dead_logl.append(dl); self.dead_logw.append(logw)
+        self.it += kbatch
+
+    def die(self, kbatch, nlive):
+        """One iteration's deaths of a host-managed run.  Returns (dead rows, lstar, surviving rows in rank order)."""
+        t0 = time.perf_counter()
+        order = self.order(kbatch)
+        self.order_s += time.perf_counter() - t0
+        dead = order[:kbatch]
+        lstar = self.logl[dead[-1]]
+        self.account(self.logl[dead], kbatch, nlive, dead)
+        return dead, lstar, order[kbatch:]
+
+    def stopped(self, gap, precision_criterion):
+        return _stop(self.logz, self.logx, np.max(self.logl), self.logl, gap, precision_criterion)
+
+    def result(self, nlive, kbatch, clustering, adapting, region=False, one_run=False):
+        timing = {"order_s": self.order_s, "step_wait_s": 0.0, "turns": self.timing["turns"]} if one_run else self.timing
+        return _finish(self.logz, self.h, self.logx, self.it, self.ncall, nlive, kbatch, self.dead_theta + [self.theta],
+                       self.dead_logl, self.dead_logw, self.logl, self.dead_birth + [self.birth], timing,
+                       self.nclusters if clustering else None, self.trace if adapting else None, self.fars if adapting else None,
+                       (self.fallbacks, self.eff, self.rcalls, self.fallback_calls) if region else None)
+
+
+@dataclass
+class _Turn:
+    """One run's part of a lockstep turn: what die returned, then what the proposal draws and groups."""
+    run: _EnsembleRun
+    dead: np.ndarray                # the rows that died = the rows the new points go to
+    lstar: float
+    alive: np.ndarray               # the surviving rows in rank order
+    start: np.ndarray = None        # the walkers' start rows
+    chol: np.ndarray = None         # the whitening factor of all survivors
+    walk_seed: int = None
+    pick: np.ndarray = None         # start = alive[pick]
+    labels: np.ndarray = None       # clustering: the survivors' cluster labels
+    factors: list = None            # the whitening factor of every label ([chol] without clusters)
+    cw: np.ndarray = None           # every walker's label
+    order: np.ndarray = None        # the walkers in group order; sizes, factors and seeds of the non-empty groups (_walk_groups)
+    sizes: np.ndarray = None
+    gfactors: list = None
+    gseeds: list = None
+    used: int = 0                   # the likelihood calls of this turn's moves
+
+
+def _start_runs(seeds, nlive, ndim, nsteps, evaluate):
+    """The runs of a lockstep ensemble, their initial live points from ONE evaluate call."""
+    runs = [_EnsembleRun(s, nlive, ndim, nsteps) for s in seeds]
+    theta, logl = evaluate(np.concatenate([r.u for r in runs]))
+    for i, r in enumerate(runs):
+        r.theta, r.logl = theta[i * nlive:(i + 1) * nlive].copy(), logl[i * nlive:(i + 1) * nlive].copy()
+    return runs
+
+
+def _lockstep(runs, nlive, kbatch, dlogz, max_iter, max_calls, precision_criterion, propose):
+    """The host-managed runs in lockstep until each has met its own stop (dlogz or precision_criterion, max_iter, max_calls):
+    per turn the deaths of every running run, ONE propose(turn) that replaces the dead rows of them all and returns the
+    seconds of its shared walk or draw calls, then the stop tests.  A run's timing: host_s its own deaths and its share of the
+    turn's other host work, walk_s the shared calls it took part in, turns their number."""
+    gap = np.log(np.expm1(dlogz))
+    while True:
+        turn = []
+        for r in runs:
+            if r.done or not (r.it < max_iter and r.ncall < max_calls):
+                r.done = True
+                continue
+            t0 = time.perf_counter()
+            turn.append(_Turn(r, *r.die(kbatch, nlive)))
+            r.timing["host_s"] += time.perf_counter() - t0
+        if not turn:
+            return
+        t0 = time.perf_counter()
+        walk_s = propose(turn)
+        for t in turn:
+            t.run.done = t.run.stopped(gap, precision_criterion)
+        host_s = (time.perf_counter() - t0 - walk_s) / len(turn)
+        for t in turn:
+            t.run.timing["host_s"] += host_s
+            t.run.timing["walk_s"] += walk_s
+            t.run.timing["turns"] += 1
+
+
 def _host_chord_walk(wu, wt, wl, lstar, chol, wrapped, nsteps, rng, evaluate):
-    """nsteps chord moves of every walker inside logL > lstar, as run_nested_slice's host loop makes them (one whitening
-    factor); wu / wt / wl are updated in place.  Returns the likelihood calls."""
+    """nsteps chord moves of every walker inside logL > lstar on the host, drawn from rng; wu / wt / wl are updated in place.
+    chol: one whitening factor [ndim, ndim], or one per walker [k, ndim, ndim] (the two products round differently, and each
+    is what the device walk of that form computes).  Every shrink round is ONE evaluate call for all unfinished walkers.
+    Returns the likelihood calls."""
     k, ndim = wu.shape
     ncall = 0
     for _ in range(nsteps):
         z = rng.standard_normal((k, ndim))
-        d = z @ chol.T
+        d = np.einsum("kij,kj->ki", chol, z) if chol.ndim == 3 else z @ chol.T
         d /= np.linalg.norm(d, axis=1, keepdims=True)
         tmin, tmax = _chord(wu, d, wrapped)
         todo = np.arange(k)
@@ -417,7 +582,7 @@ def _host_chord_walk(wu, wt, wl, lstar, chol, wrapped, nsteps, rng, evaluate):
             acc = todo[ok]
             wu[acc], wt[acc], wl[acc] = cand[ok], ct[ok], cl[ok]
             rej = todo[~ok]
-            neg = t[~ok] < 0
+            neg = t[~ok] < 0                                        # shrink the bracket towards t = 0
             tmin[rej[neg]] = t[~ok][neg]
             tmax[rej[~neg]] = t[~ok][~neg]
             todo = rej
@@ -425,136 +590,257 @@ def _host_chord_walk(wu, wt, wl, lstar, chol, wrapped, nsteps, rng, evaluate):
     return ncall
 
 
+def _one_group(walker):
+    """walker= as a walker_runs of one run and one group: group 0 walks with the walk seed itself."""
+    def walker_runs(cube, theta, logl, run_start, lstar, chol, wrapped, nsteps, max_rounds, seeds, **pk):
+        wu, wt, wl, used = walker(cube, theta, logl, lstar[0], chol[0], wrapped, nsteps, max_rounds, seeds[0], **pk)
+        return wu, wt, wl, [int(used)]
+    return walker_runs
+
+
+def _move(turn, wrapped, walker_runs, pk, evaluate):
+    """The moves of every entry of the turn, from its start rows into its dead rows (u, theta, logl of its run), each run with
+    its own step count: ONE walker_runs call for the (run, cluster) groups of them all, or — without walker_runs — the host
+    walk run by run from the run's own generator (the chord walk, or stepout.walk when pk names that proposal).  Adds the
+    likelihood calls to the runs and leaves them in the entries' `used`.  Returns the seconds the walk took."""
+    t0 = time.perf_counter()
+    if walker_runs is None:
+        for t in turn:
+            r = t.run
+            wu, wt, wl = r.u[t.start], r.theta[t.start], r.logl[t.start]
+            fac = t.factors[0] if len(t.factors) == 1 else np.stack(t.factors)[t.cw]     # each walker's: its start row's cluster's
+            if pk:
+                from .stepout import walk as stepout_walk
+                t.used = stepout_walk(wu, wt, wl, t.lstar, fac, wrapped, r.nsteps, 200, pk["step_width"], r.rng, evaluate)
+            else:
+                t.used = _host_chord_walk(wu, wt, wl, t.lstar, fac, wrapped, r.nsteps, r.rng, evaluate)
+            r.u[t.dead], r.theta[t.dead], r.logl[t.dead] = wu, wt, wl
+            r.ncall += t.used
+        return time.perf_counter() - t0
+    for t in turn:
+        t.order, t.sizes, t.gfactors, t.gseeds = _walk_groups(t.cw, t.factors, t.walk_seed)
+    ngroups = [len(t.sizes) for t in turn]
+    steps = np.repeat([t.run.nsteps for t in turn], ngroups).astype(np.int32)
+    rows = [t.start[t.order] for t in turn]
+    cat = np.concatenate if len(turn) > 1 else (lambda parts: parts[0])      # (one run: its rows as they are, no second copy)
+    t0 = time.perf_counter()
+    wu, wt, wl, used = walker_runs(cat([t.run.u[s] for t, s in zip(turn, rows)]),
+                                   cat([t.run.theta[s] for t, s in zip(turn, rows)]),
+                                   cat([t.run.logl[s] for t, s in zip(turn, rows)]),
+                                   np.concatenate([[0], np.cumsum(np.concatenate([t.sizes for t in turn]))]).astype(np.int64),
+                                   np.repeat([t.lstar for t in turn], ngroups), np.stack([f for t in turn for f in t.gfactors]),
+                                   wrapped, int(steps[0]) if np.all(steps == steps[0]) else steps, 200,
+                                   [s for t in turn for s in t.gseeds], **pk)
+    walk_s = time.perf_counter() - t0
+    a = g = 0
+    for t, n in zip(turn, ngroups):
+        r, b = t.run, a + len(t.dead)
+        back = t.dead[t.order]                           # the walkers' rows in group order
+        r.u[back], r.theta[back], r.logl[back] = wu[a:b], wt[a:b], wl[a:b]
+        t.used = int(np.sum(used[g:g + n]))
+        r.ncall += t.used
+        a, g = b, g + n
+    return walk_s
+
+
+def _cluster_turn(turn, clusterer, wrapped, nboot):
+    """clustering=True: the survivors of every run of the turn clustered in ONE clusterer call (which draws nothing from the
+    runs' generators); every entry gets the survivors' labels, the factor of every cluster and its walkers' labels."""
+    uas = [t.run.u[t.alive] for t in turn]
+    run_start = np.concatenate([[0], np.cumsum([len(ua) for ua in uas])]).astype(np.int64)
+    labels, ncl, _ = clusterer(np.concatenate(uas), run_start, np.stack([_cluster_scale(ua) for ua in uas]), wrapped, nboot,
+                               [t.run.stream(_BOOT_MUL) for t in turn])
+    labels = np.asarray(labels, dtype=np.intp)
+    for j, t in enumerate(turn):
+        t.labels = labels[run_start[j]:run_start[j + 1]]
+        t.run.nclusters.append(int(ncl[j]))
+        t.factors = _cluster_factors(uas[j], t.labels, int(ncl[j]), t.chol)
+        t.cw = t.labels[t.pick]
+
+
+def _walk_proposal(kbatch, wrapped, walker_runs, clusterer, nboot, adapting, pk, evaluate):
+    """The slice walk as _lockstep's proposal.  Per run: the whitening from the survivors, then from the run's generator the
+    start rows and — for walker_runs only; the host walk draws its moves from the generator itself — the walk seed.  Then the
+    clustering (clusterer given), the moves (_move), and the step-count rule from ONE distances call (adapting)."""
+    def propose(turn):
+        for t in turn:
+            r = t.run
+            t.chol = _whitening(r.u[t.alive])
+            t.pick = r.rng.integers(0, len(t.alive), kbatch)
+            t.start = t.alive[t.pick]
+            if walker_runs is not None:
+                t.walk_seed = int(r.rng.integers(0, 2 ** 62))
+            t.factors, t.cw = [t.chol], np.zeros(kbatch, dtype=np.intp)
+        if clusterer is not None:
+            _cluster_turn(turn, clusterer, wrapped, nboot)
+        if adapting:
+            starts = [t.run.u[t.start] for t in turn]
+        walk_s = _move(turn, wrapped, walker_runs, pk, evaluate)
+        if adapting:
+            from .adapt import far_fraction, next_nsteps
+            c, f = _adapt_counts([(t.run.u[t.alive], t.labels, t.factors, t.cw, s, t.run.u[t.dead]) for t, s in zip(turn, starts)],
+                                 adapting[2], wrapped)
+            for j, t in enumerate(turn):
+                r = t.run
+                r.trace.append(r.nsteps)
+                r.fars.append(float(far_fraction(f[j], c[j])))
+                r.nsteps = next_nsteps(r.nsteps, int(f[j]), int(c[j]), adapting[0], adapting[1])
+        return walk_s
+    return propose
+
+
+def _region_proposal(kbatch, wrapped, walker_runs, clusterer, nboot, region_runs, cap, evaluate):
+    """MLFriends region sampling as _lockstep's proposal: ONE clusterer call (every running run's scale and radius2) and ONE
+    region_runs call (kbatch draws of every running run), then the chord walk (_move) for whatever a run is short of — only
+    such a run draws from its generator: the start rows, then the walk seed."""
+    def propose(turn):
+        uas = [t.run.u[t.alive] for t in turn]
+        run_start = np.concatenate([[0], np.cumsum([len(ua) for ua in uas])]).astype(np.int64)
+        surv = np.concatenate(uas)
+        scales = np.stack([_cluster_scale(ua) for ua in uas])
+        _lab, ncl, radius2 = clusterer(surv, run_start, scales, wrapped, nboot, [t.run.stream(_BOOT_MUL) for t in turn])
+        t1 = time.perf_counter()
+        cu, ct, cl, nfound, ncalls = region_runs(surv, run_start, scales, np.asarray(radius2, dtype=np.float64),
+                                                 np.array([t.lstar for t in turn], dtype=np.float64),
+                                                 [t.run.stream(_REGION_MUL) for t in turn], kbatch,
+                                                 wrapped=wrapped, max_candidates=cap)
+        short = []
+        for j, t in enumerate(turn):
+            r, nf, nc = t.run, int(nfound[j]), int(ncalls[j])
+            r.nclusters.append(int(ncl[j]))
+            r.rcalls.append(nc)
+            r.eff.append(nf / nc if nc > 0 else float("nan"))
+            r.ncall += nc
+            rows = t.dead[:nf]
+            r.u[rows], r.theta[rows], r.logl[rows] = cu[j, :nf], ct[j, :nf], cl[j, :nf]
+            if nf < kbatch:
+                k = kbatch - nf
+                start = t.alive[r.rng.integers(0, len(t.alive), k)]
+                chol = _whitening(uas[j])
+                short.append(_Turn(r, t.dead[nf:], t.lstar, t.alive, start, chol, int(r.rng.integers(0, 2 ** 62)),
+                                   factors=[chol], cw=np.zeros(k, dtype=np.intp)))
+                r.fallbacks += k
+        if short:
+            _move(short, wrapped, walker_runs, {}, evaluate)
+            for t in short:
+                t.run.fallback_calls += t.used
+        return time.perf_counter() - t1
+    return propose
+
+
+def _walk_ensemble(prior, loglike, prior_loglike, ndim, seeds, nlive, kbatch, nsteps, dlogz, max_iter, max_calls, wrapped,
+                   walker_runs, clustering, nboot, clusterer, adaptive_nsteps, min_nsteps, max_nsteps, distances, pk,
+                   precision_criterion, one_run=False):
+    """The host-managed slice walk of run_nested_slice (one seed, one_run: its timing keys) and run_nested_ensemble.  The
+    initial live points are one prior, then one loglike call, even when prior_loglike is given (the host walk's rounds use it)."""
+    clusterer = _default_clusterer(clusterer) if clustering else None
+    nlive, kbatch, nsteps, wrapped = _schedule(ndim, nlive, kbatch, nsteps, wrapped)
+    adapting = _adapt_setup(adaptive_nsteps, nsteps, min_nsteps, max_nsteps, distances)
+    runs = _start_runs(seeds, nlive, ndim, nsteps, _evaluator(prior, loglike, None))
+    _lockstep(runs, nlive, kbatch, dlogz, max_iter, max_calls, precision_criterion,
+              _walk_proposal(kbatch, wrapped, walker_runs, clusterer, nboot, adapting, pk, _evaluator(prior, loglike, prior_loglike)))
+    return [r.result(nlive, kbatch, clustering, bool(adapting), one_run=one_run) for r in runs]
+
+
 def _region_ensemble(prior, loglike, ndim, seeds, nlive, kbatch, nsteps, dlogz, max_iter, max_calls, wrapped, walker_runs, nboot,
                      clusterer, region_runs, region_max_candidates, precision_criterion, prior_loglike=None):
-    """proposal="region" of run_nested_slice (one seed) and run_nested_ensemble: the runs in lockstep, per iteration ONE
-    clusterer call (every running run's scale and MLFriends radius2) and ONE region_runs call (kbatch draws of every running
-    run), then the chord walk for whatever a run is short of.  Every draw of a run depends on its own seed, iteration and
-    survivors alone, so result[r] is the one-seed run bit for bit."""
+    """proposal="region" of run_nested_slice (one seed) and run_nested_ensemble.  Every draw of a run depends on its own seed,
+    iteration and survivors alone, so result[r] is the one-seed run bit for bit.  The initial live points are one call of the
+    evaluator the draws use (prior_loglike when it is given)."""
     from . import region as _region
     clusterer = _default_clusterer(clusterer)
-    defaults = ultranest_defaults(ndim)
-    nlive = int(nlive or defaults["nlive"])
-    kbatch = int(kbatch or max(1, nlive // 4))
-    if not 1 <= kbatch < nlive:
-        raise ValueError("need 1 <= kbatch < nlive")
-    nsteps = int(nsteps or defaults["nsteps"])
+    nlive, kbatch, nsteps, wrapped = _schedule(ndim, nlive, kbatch, nsteps, wrapped)
     cap = int(_region.DEFAULT_MAX_CANDIDATES if region_max_candidates is None else region_max_candidates)
     if cap < 0:
         raise ValueError("region_max_candidates must not be negative")
-    wrapped = None if wrapped is None else np.asarray(wrapped, dtype=bool)
-
-    def evaluate(cand):
-        if prior_loglike is not None:
-            ct, cl = prior_loglike(cand)
-            return np.asarray(ct, dtype=np.float64), np.asarray(cl, dtype=np.float64)
-        ct = np.asarray(prior(cand), dtype=np.float64)
-        return ct, np.asarray(loglike(ct), dtype=np.float64)
-
+    evaluate = _evaluator(prior, loglike, prior_loglike)
     if region_runs is None:
         def region_runs(surv, run_start, scale, radius2, lstar, rseeds, kdraw, wrapped=None, max_candidates=cap):
             return _region.draw_runs(surv, run_start, scale, radius2, lstar, rseeds, kdraw, evaluate, wrapped=wrapped,
                                      max_candidates=max_candidates)
-    runs = [_EnsembleRun(s, nlive, ndim) for s in seeds]
-    for r in runs:
-        r.fallbacks, r.fallback_calls, r.eff, r.rcalls = 0, 0, [], []
-    theta, logl = evaluate(np.concatenate([r.u for r in runs]))
-    for i, r in enumerate(runs):
-        r.theta, r.logl = theta[i * nlive:(i + 1) * nlive].copy(), logl[i * nlive:(i + 1) * nlive].copy()
-    stop_gap = np.log(np.expm1(dlogz))
-    while True:
-        turn = []                                   # (run, dead rows, lstar, surviving rows in rank order)
-        for r in runs:
-            if r.done:
-                continue
-            if not (r.it < max_iter and r.ncall < max_calls):
-                r.done = True
-                continue
-            t0 = time.perf_counter()
-            order = _stable_argsort(r.logl)
-            dead = order[:kbatch]
-            lstar = r.logl[dead[-1]]
-            dl = r.logl[dead]
-            logw, r.logz, r.h, r.logx = _deaths(r.logz, r.h, r.logx, dl, nlive, kbatch)
-            r.dead_theta.append(r.theta[dead])
-            r.dead_logl.append(dl); r.dead_logw.append(logw)
-            r.dead_birth.append(r.birth[dead])
-            r.birth[dead] = lstar
-            r.it += kbatch
-            turn.append((r, dead, lstar, order[kbatch:]))
-            r.timing["host_s"] += time.perf_counter() - t0
-        if not turn:
-            break
+    runs = _start_runs(seeds, nlive, ndim, nsteps, evaluate)
+    _lockstep(runs, nlive, kbatch, dlogz, max_iter, max_calls, precision_criterion,
+              _region_proposal(kbatch, wrapped, walker_runs, clusterer, nboot, region_runs, cap, evaluate))
+    return [r.result(nlive, kbatch, True, False, region=True) for r in runs]
+
+
+def _slice_resident(live, ndim, seed, nlive, kbatch, nsteps, dlogz, max_iter, max_calls, wrapped, live_chol, pk,
+                    precision_criterion):
+    """run_nested_slice(live=model), one run: the live set resident on the device (GpuRVModel.live_init / live_step).  Three
+    forms.  live_chol="host" mirrors the cube rows, whitens on the host and waits for the step.  live_chol="device" keeps the
+    log-L and the order on the host; the walk needs nothing of the iteration's evidence sums, so it starts first — on a helper
+    thread (the C call releases the interpreter lock) — and the sums run on the host while the GPU walks.  With
+    GpuRVModel.live_sort the ORDER is on the device as well: no per-point state on the host at all — per iteration the log-L
+    of the dying points comes down (the evidence sums need them) and ranks go up (the draw the host order's alive[...] makes)."""
+    nlive, kbatch, nsteps, wrapped = _schedule(ndim, nlive, kbatch, nsteps, wrapped)
+    if live_chol not in ("device", "host"):
+        raise ValueError(live_chol)
+    run = _EnsembleRun(seed, nlive, ndim)
+    rng, mirror = run.rng, live_chol == "host"
+    run.logl = live.live_init(run.u)
+    if not mirror:
+        run.u = None                                   # no host mirror of the rows at all
+    device_order = not mirror and hasattr(live, "live_sort")
+    top = float(np.max(run.logl)) if device_order else None
+    # precision_criterion on the device-ordered path: the live log-L multiset, from the values that come down anyway
+    live_ll = np.sort(run.logl) if device_order and precision_criterion is not None else None
+    timing = {"order_s": 0.0, "step_wait_s": 0.0, "turns": 0}
+    gap = np.log(np.expm1(dlogz))
+    while run.it < max_iter and run.ncall < max_calls:
+        timing["turns"] += 1
         t0 = time.perf_counter()
-        uas = [r.u[alive] for r, _d, _l, alive in turn]
-        run_start = np.concatenate([[0], np.cumsum([len(ua) for ua in uas])]).astype(np.int64)
-        surv = np.concatenate(uas)
-        scales = np.stack([_cluster_scale(ua) for ua in uas])
-        _lab, ncl, radius2 = clusterer(surv, run_start, scales, wrapped, nboot, [(r.seed * _BOOT_MUL + r.it) & _M64 for r, *_x in turn])
-        t1 = time.perf_counter()
-        cu, ct, cl, nfound, ncalls = region_runs(surv, run_start, scales, np.asarray(radius2, dtype=np.float64),
-                                                 np.array([t[2] for t in turn], dtype=np.float64),
-                                                 [(r.seed * _REGION_MUL + r.it) & _M64 for r, *_x in turn], kbatch,
-                                                 wrapped=wrapped, max_candidates=cap)
-        t2 = time.perf_counter()
-        # the chord walk for the points a run is short of: start rows and walk seed from the run's own generator
-        short = []
-        for j, (r, dead, lstar, alive) in enumerate(turn):
-            nf = int(nfound[j])
-            r.nclusters.append(int(ncl[j]))
-            r.rcalls.append(int(ncalls[j]))
-            r.eff.append(nf / int(ncalls[j]) if int(ncalls[j]) > 0 else float("nan"))
-            r.ncall += int(ncalls[j])
-            rows = dead[:nf]
-            r.u[rows], r.theta[rows], r.logl[rows] = cu[j, :nf], ct[j, :nf], cl[j, :nf]
-            if nf < kbatch:
-                k = kbatch - nf
-                start = alive[r.rng.integers(0, len(alive), k)]
-                short.append((r, dead[nf:], lstar, _whitening(uas[j]), start, int(r.rng.integers(0, 2 ** 62))))
-                r.fallbacks += k
-        if short and walker_runs is not None:
-            sizes = [len(rows) for _r, rows, *_x in short]
-            wu, wt, wl, used = walker_runs(np.concatenate([r.u[st] for r, _rows, _l, _c, st, _s in short]),
-                                           np.concatenate([r.theta[st] for r, _rows, _l, _c, st, _s in short]),
-                                           np.concatenate([r.logl[st] for r, _rows, _l, _c, st, _s in short]),
-                                           np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64),
-                                           np.array([t[2] for t in short], dtype=np.float64), np.stack([t[3] for t in short]),
-                                           wrapped, nsteps, 200, [t[5] for t in short])
-            a = 0
-            for g, (r, rows, *_x) in enumerate(short):
-                b = a + len(rows)
-                r.u[rows], r.theta[rows], r.logl[rows] = wu[a:b], wt[a:b], wl[a:b]
-                r.ncall += int(used[g]); r.fallback_calls += int(used[g])
-                a = b
+        if device_order:
+            order = dead = None
+            dl, lstar, top = live.live_sort(kbatch)
         else:
-            for r, rows, lstar, chol, start, _wseed in short:
-                wu, wt, wl = r.u[start], r.theta[start], r.logl[start]
-                used = _host_chord_walk(wu, wt, wl, lstar, chol, wrapped, nsteps, r.rng, evaluate)
-                r.u[rows], r.theta[rows], r.logl[rows] = wu, wt, wl
-                r.ncall += used; r.fallback_calls += used
-        t3 = time.perf_counter()
-        for r, *_x in turn:
-            if precision_criterion is not None:
-                if _precision_stop(r.logz, r.logx, r.logl, precision_criterion):
-                    r.done = True
-            elif np.max(r.logl) + r.logx < r.logz + stop_gap:
-                r.done = True
-            r.timing["walk_s"] += t3 - t1
-            r.timing["turns"] += 1
-            r.timing["host_s"] += (t1 - t0) / len(turn)
-    out = []
-    for r in runs:
-        logw_live = r.logx - np.log(nlive) + r.logl
-        logz_final = np.logaddexp(r.logz, _logaddexp_many(logw_live))
-        all_theta = np.vstack([a.reshape(-1, ndim) for a in r.dead_theta] + [r.theta])
-        all_logl = np.concatenate(r.dead_logl + [r.logl])
-        all_logw = np.concatenate(r.dead_logw + [logw_live]) - logz_final
-        out.append(NestedResult(float(logz_final), float(np.sqrt(max(r.h, 0.0) / nlive)), r.it, r.ncall, float(r.h),
-                                all_theta, all_logl, all_logw, r.timing, np.array(r.nclusters, dtype=np.int64), nlive=nlive,
-                                kbatch=kbatch, logl_birth=np.concatenate(r.dead_birth + [r.birth]),
-                                region_fallbacks=int(r.fallbacks), region_efficiency=np.array(r.eff, dtype=np.float64),
-                                region_calls=np.array(r.rcalls, dtype=np.int64), region_fallback_calls=int(r.fallback_calls)))
-    return out
+            order = run.order(kbatch)
+            dead = order[:kbatch]
+            dl, lstar = run.logl[dead], run.logl[dead[-1]]
+        timing["order_s"] += time.perf_counter() - t0
+        if mirror:
+            chol = _whitening(run.u[order[kbatch:]])
+        start = rng.integers(0, nlive - kbatch, kbatch)
+        if not device_order:
+            start = order[kbatch:][start]
+        step = (order, kbatch, start, lstar, wrapped, nsteps, 200, int(rng.integers(0, 2 ** 62)))
+        pending = None if mirror else _helper().submit(live.live_step, *step, **pk)
+        run.account(dl, kbatch, nlive)
+        if mirror:
+            # order and start rows up, the new log-L of the replaced rows down, and the mirror of the rows
+            wl, used = live.live_step(*step, chol=chol, **pk)
+        else:
+            t0 = time.perf_counter()
+            wl, used = pending.result()
+            timing["step_wait_s"] += time.perf_counter() - t0
+        run.ncall += int(used)
+        if device_order:
+            top = max(top, float(np.max(wl)))                     # the survivors' highest and the newcomers'
+            if live_ll is not None:
+                live_ll = _multiset_step(live_ll, kbatch, wl)
+            if _stop(run.logz, run.logx, top, live_ll, gap, precision_criterion):
+                break
+            continue
+        run.logl[dead] = wl
+        if mirror:
+            run.u = live.live_get()[0]
+        if run.stopped(gap, precision_criterion):
+            break
+    if device_order:
+        run.logl = live.live_get(cube=False, theta=False)[2]              # the live points' log-L: once, at the end
+    if hasattr(live, "live_dead_count"):
+        # the samples come down once, straight into the array that is returned: dead points first, then the live set
+        ndead = live.live_dead_count()
+        samples = np.empty((ndead + nlive, ndim))
+        live.live_dead(theta_out=samples[:ndead])
+        live.live_get(cube=False, logl=False, theta_out=samples[ndead:])
+    else:
+        samples = [live.live_dead()[0], live.live_get()[1]]
+    if hasattr(live, "live_births"):
+        births = live.live_births()                           # the device's own record (it chose the dying rows)
+    else:                                                     # (device order without it: the host never saw which rows died)
+        births = None if device_order else run.dead_birth + [run.birth]
+    return _finish(run.logz, run.h, run.logx, run.it, run.ncall, nlive, kbatch, samples, run.dead_logl, run.dead_logw, run.logl,
+                   births, timing)
 
 
 def run_nested_slice(prior: Callable, loglike: Callable, ndim: int, nlive: Optional[int] = None, kbatch: Optional[int] = None,
@@ -639,242 +925,22 @@ def run_nested_slice(prior: Callable, loglike: Callable, ndim: int, nlive: Optio
     if clustering and walker is not None:
         raise ValueError("walker= has one whitening factor for all walkers: with clustering=True pass walker_runs= "
                          "(GpuRVModel.slice_walk_runs)")
-    if adaptive_nsteps is not None and live is not None:
-        _check_resident_adaptive(live, distances, live_chol)
+    if live is not None and (clustering or adaptive_nsteps is not None):       # the one-run resident ensemble
+        if adaptive_nsteps is not None:
+            _check_resident_adaptive(live, distances, live_chol)
         if clustering:
             _check_resident_clustering(live, clusterer, live_chol, nboot)
         return _ensemble_resident(live, ndim, [int(seed)], nlive, kbatch, nsteps, dlogz, max_iter, max_calls, wrapped,
                                   clustering=clustering, nboot=nboot, adaptive_nsteps=adaptive_nsteps, min_nsteps=min_nsteps,
                                   max_nsteps=max_nsteps, pk=pk, precision_criterion=precision_criterion)[0]
-    if clustering and live is not None:
-        _check_resident_clustering(live, clusterer, live_chol, nboot)
-        return _ensemble_resident(live, ndim, [int(seed)], nlive, kbatch, nsteps, dlogz, max_iter, max_calls, wrapped,
-                                  clustering=True, nboot=nboot, pk=pk, precision_criterion=precision_criterion)[0]
     if walker is not None and walker_runs is not None:
         raise ValueError("pass walker= or walker_runs=, not both")
-    if clustering:
-        clusterer = _default_clusterer(clusterer)
-    nclusters = [] if clustering else None
-    rng = np.random.default_rng(seed)
-    defaults = ultranest_defaults(ndim)
-    nlive = int(nlive or defaults["nlive"])
-    kbatch = int(kbatch or max(1, nlive // 4))
-    if not 1 <= kbatch < nlive:
-        raise ValueError("need 1 <= kbatch < nlive")
-    nsteps = int(nsteps or defaults["nsteps"])
-    adapting = _adapt_setup(adaptive_nsteps, nsteps, min_nsteps, max_nsteps, distances)
-    trace, fars = [], []
-    wrapped = None if wrapped is None else np.asarray(wrapped, dtype=bool)
-    u = rng.random((nlive, ndim))
     if live is not None:
-        if live_chol not in ("device", "host"):
-            raise ValueError(live_chol)
-        theta = None
-        logl = live.live_init(u)
-        if live_chol == "device":
-            u = None                                   # no host mirror of the rows at all
-    else:
-        theta = np.asarray(prior(u), dtype=np.float64)
-        logl = np.asarray(loglike(theta), dtype=np.float64)
-    ncall = nlive
-    dead_theta, dead_logl, dead_logw = [], [], []
-    birth, dead_birth = np.full(nlive, -np.inf), []      # (host order: every path but device_order, which reads them at the end)
-    logz, h, logx = -np.inf, 0.0, 0.0
-    it = 0
-    # the resident live set with the ORDER on the device as well (GpuRVModel.live_sort, round 4): no per-point state on the host
-    # at all — per iteration the log-L of the dying points comes down (the evidence sums need them), ranks go up
-    device_order = live is not None and u is None and hasattr(live, "live_sort")
-    top = float(np.max(logl)) if device_order else None
-    # precision_criterion on the device-ordered path: the live log-L multiset, from the values that come down anyway
-    live_ll = np.sort(logl) if device_order and precision_criterion is not None else None
-    timing = {"order_s": 0.0, "step_wait_s": 0.0, "turns": 0}
-    while it < max_iter and ncall < max_calls:
-        timing["turns"] += 1
-        t_turn = time.perf_counter()
-        if device_order:
-            dl, lstar, top = live.live_sort(kbatch)
-            timing["order_s"] += time.perf_counter() - t_turn
-            ranks = rng.integers(0, nlive - kbatch, kbatch)          # (the draw the host order's alive[rng.integers(...)] makes)
-            seed_it = int(rng.integers(0, 2 ** 62))
-            pending = _helper().submit(live.live_step, None, kbatch, ranks, lstar, wrapped, nsteps, 200, seed_it, **pk)
-            order = dead = None
-        else:
-            order = _stable_argsort(logl)
-            dead = order[:kbatch]
-            lstar = logl[dead[-1]]
-            dl = logl[dead]
-            dead_birth.append(birth[dead])
-            birth[dead] = lstar                                   # (the replacements of this iteration are drawn above lstar)
-            timing["order_s"] += time.perf_counter() - t_turn
-        if device_order:
-            pass
-        elif live is not None and u is None:
-            # the resident live set, whitening on the device: the walk needs nothing of this iteration's evidence
-            # bookkeeping, so it starts first — on a helper thread (the C call releases the interpreter lock) — and the
-            # vectorised sums below run on the host while the GPU walks
-            alive = order[kbatch:]
-            start = alive[rng.integers(0, len(alive), kbatch)]
-            seed_it = int(rng.integers(0, 2 ** 62))
-            pending = _helper().submit(live.live_step, order, kbatch, start, lstar, wrapped, nsteps, 200, seed_it, **pk)
-        else:
-            pending = None
-        logw, logz, h, logx = _deaths(logz, h, logx, dl, nlive, kbatch)
-        if live is None:
-            dead_theta.append(theta[dead])                                                # (index arrays: already copies)
-        dead_logl.append(dl); dead_logw.append(logw)
-        it += kbatch
-        if pending is not None:
-            t_wait = time.perf_counter()
-            wl, used = pending.result()
-            timing["step_wait_s"] += time.perf_counter() - t_wait
-            ncall += int(used)
-            if device_order:
-                top = max(top, float(np.max(wl)))                     # the survivors' highest and the newcomers'
-                if live_ll is not None:
-                    live_ll = _multiset_step(live_ll, kbatch, wl)
-            else:
-                logl[dead] = wl
-                top = np.max(logl)
-            if precision_criterion is not None:
-                if _precision_stop(logz, logx, live_ll if device_order else logl, precision_criterion):
-                    break
-            elif top + logx < logz + np.log(np.expm1(dlogz)):
-                break
-            continue
-        alive = order[kbatch:]
-        # whitening from the surviving live points
-        chol = _whitening(u[alive]) if u is not None else None
-        pick = rng.integers(0, len(alive), kbatch)
-        start = alive[pick]
-        if live is not None:
-            # live_chol="host": order and start rows up, the new log-L of the replaced rows down, and the mirror of the rows
-            wl, used = live.live_step(order, kbatch, start, lstar, wrapped, nsteps, 200, int(rng.integers(0, 2 ** 62)), chol=chol,
-                                      **pk)
-            ncall += int(used)
-            logl[dead] = wl
-            u = live.live_get()[0]
-            if _stop(logz, logx, logl, dlogz, precision_criterion):
-                break
-            continue
-        wu, wt, wl = u[start], theta[start], logl[start]
-        starts = wu.copy() if adapting else None
-        factors = [chol]
-        cw = np.zeros(kbatch, dtype=np.intp)
-        labels = None
-        if clustering:
-            ua = u[alive]
-            labels, ncl, _ = clusterer(ua, [0, len(ua)], _cluster_scale(ua)[None, :], wrapped, nboot,
-                                       [(int(seed) * _BOOT_MUL + it) & _M64])
-            nclusters.append(int(ncl[0]))
-            factors = _cluster_factors(ua, labels, int(ncl[0]), chol)
-            cw = np.asarray(labels, dtype=np.intp)[pick]
-        if walker is not None:
-            wu, wt, wl, used = walker(wu, wt, wl, lstar, chol, wrapped, nsteps, 200, int(rng.integers(0, 2 ** 62)), **pk)
-            ncall += int(used)
-        elif walker_runs is not None:
-            wo, sizes, gf, gseeds = _walk_groups(cw, factors, int(rng.integers(0, 2 ** 62)))
-            gu, gt, gl, used = walker_runs(wu[wo], wt[wo], wl[wo], np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64),
-                                           np.full(len(sizes), lstar), np.stack(gf), wrapped, nsteps, 200, gseeds, **pk)
-            wu[wo], wt[wo], wl[wo] = gu, gt, gl
-            ncall += int(np.sum(used))
-        many = len(factors) > 1
-        if many:
-            wfac = np.stack(factors)[cw]                        # each walker's factor: that of its start row's cluster
-        if pk and walker is None and walker_runs is None:
-            def evaluate(cand):
-                if prior_loglike is not None:
-                    return prior_loglike(cand)
-                ct = np.asarray(prior(cand), dtype=np.float64)
-                return ct, np.asarray(loglike(ct), dtype=np.float64)
-            from .stepout import walk as stepout_walk
-            ncall += stepout_walk(wu, wt, wl, lstar, wfac if many else chol, wrapped, nsteps, 200, pk["step_width"], rng, evaluate)
-        for _ in range(0 if (walker is not None or walker_runs is not None or pk) else nsteps):
-            z = rng.standard_normal((kbatch, ndim))
-            d = np.einsum("kij,kj->ki", wfac, z) if many else z @ chol.T
-            d /= np.linalg.norm(d, axis=1, keepdims=True)
-            tmin, tmax = _chord(wu, d, wrapped)
-            todo = np.arange(kbatch)
-            rounds = 0
-            while todo.size and rounds < 200:
-                t = tmin[todo] + (tmax[todo] - tmin[todo]) * rng.random(todo.size)
-                cand = wu[todo] + t[:, None] * d[todo]
-                if wrapped is not None:
-                    cand[:, wrapped] %= 1.0
-                cand = np.clip(cand, 0.0, np.nextafter(1.0, 0.0))
-                if prior_loglike is not None:
-                    ct, cl = prior_loglike(cand)                        # one round trip to the GPU
-                else:
-                    ct = np.asarray(prior(cand), dtype=np.float64)
-                    cl = np.asarray(loglike(ct), dtype=np.float64)      # one batch = one GPU launch
-                ncall += todo.size
-                ok = cl > lstar
-                acc = todo[ok]
-                wu[acc], wt[acc], wl[acc] = cand[ok], ct[ok], cl[ok]
-                rej = todo[~ok]
-                neg = t[~ok] < 0                                        # shrink the bracket towards t = 0
-                tmin[rej[neg]] = t[~ok][neg]
-                tmax[rej[~neg]] = t[~ok][~neg]
-                todo = rej
-                rounds += 1
-        u[dead], theta[dead], logl[dead] = wu, wt, wl
-        if adapting:
-            from .adapt import far_fraction, next_nsteps
-            c, f = _adapt_counts([(u[alive], None if labels is None else np.asarray(labels, dtype=np.intp), factors, cw, starts,
-                                   wu)], adapting[2], wrapped)
-            trace.append(nsteps)
-            fars.append(float(far_fraction(f[0], c[0])))
-            nsteps = next_nsteps(nsteps, int(f[0]), int(c[0]), adapting[0], adapting[1])
-        if _stop(logz, logx, logl, dlogz, precision_criterion):
-            break
-    if device_order:
-        logl = live.live_get(cube=False, theta=False)[2]              # the live points' log-L: once, at the end
-    logw_live = logx - np.log(nlive) + logl
-    logz_final = np.logaddexp(logz, _logaddexp_many(logw_live))
-    if live is not None and hasattr(live, "live_dead_count"):
-        # the samples come down once, straight into the array that is returned: dead points first, then the live set
-        ndead = live.live_dead_count()
-        all_theta = np.empty((ndead + nlive, ndim))
-        live.live_dead(theta_out=all_theta[:ndead])
-        live.live_get(cube=False, logl=False, theta_out=all_theta[ndead:])
-    else:
-        if live is not None:
-            dead_theta = [live.live_dead()[0]]
-            theta = live.live_get()[1]
-        all_theta = np.vstack([a.reshape(-1, ndim) for a in dead_theta] + [theta])
-    all_logl = np.concatenate(dead_logl + [logl])
-    all_logw = np.concatenate(dead_logw + [logw_live]) - logz_final
-    if live is not None and hasattr(live, "live_births"):
-        all_birth = np.concatenate(live.live_births())        # the device's own record (it chose the dying rows)
-    elif device_order:
-        all_birth = None                                      # (a live set without births: the host never saw which rows died)
-    else:
-        all_birth = np.concatenate(dead_birth + [birth])
-    return NestedResult(float(logz_final), float(np.sqrt(max(h, 0.0) / nlive)), it, ncall, float(h),
-                        all_theta, all_logl, all_logw, timing, None if nclusters is None else np.array(nclusters, dtype=np.int64),
-                        nlive=nlive, kbatch=kbatch, logl_birth=all_birth,
-                        nsteps_trace=np.array(trace, dtype=np.int64) if adapting else None,
-                        far_fraction=np.array(fars, dtype=np.float64) if adapting else None)
-
-
-class _EnsembleRun:
-    """One run of run_nested_ensemble: the state run_nested_slice keeps in its locals."""
-
-    def __init__(self, seed, nlive, ndim):
-        self.seed = seed
-        self.rng = np.random.default_rng(seed)
-        self.u = self.rng.random((nlive, ndim))
-        self.theta = self.logl = None
-        self.ncall = nlive
-        self.dead_theta, self.dead_logl, self.dead_logw = [], [], []
-        self.birth, self.dead_birth = np.full(nlive, -np.inf), []
-        self.logz, self.h, self.logx = -np.inf, 0.0, 0.0
-        self.it = 0
-        self.done = False
-        self.timing = {"host_s": 0.0, "walk_s": 0.0, "turns": 0}
-        self.nclusters = []
-        self.nsteps = None                          # adaptive_nsteps: this run's step count, its trace and far fractions
-        self.trace, self.fars = [], []
-        self.groups = None                          # adaptive_nsteps: (survivors, labels, factors, walker labels) of the turn
+        return _slice_resident(live, ndim, seed, nlive, kbatch, nsteps, dlogz, max_iter, max_calls, wrapped, live_chol, pk,
+                               precision_criterion)
+    return _walk_ensemble(prior, loglike, prior_loglike, ndim, [seed], nlive, kbatch, nsteps, dlogz, max_iter, max_calls, wrapped,
+                          walker_runs if walker is None else _one_group(walker), clustering, nboot, clusterer, adaptive_nsteps,
+                          min_nsteps, max_nsteps, distances, pk, precision_criterion, one_run=True)[0]
 
 
 def run_nested_ensemble(prior: Callable, loglike: Callable, ndim: int, seeds, nlive: Optional[int] = None,
@@ -932,17 +998,15 @@ def run_nested_ensemble(prior: Callable, loglike: Callable, ndim: int, seeds, nl
     with live=."""
     if proposal == "region":
         _check_region(live, None, adaptive_nsteps)
-        _check_precision(precision_criterion)
-        seeds = [int(s) for s in seeds]
-        if not seeds:
-            raise ValueError("need at least one seed")
-        return _region_ensemble(prior, loglike, ndim, seeds, nlive, kbatch, nsteps, dlogz, max_iter, max_calls, wrapped,
-                                walker_runs, nboot, clusterer, region_runs, region_max_candidates, precision_criterion)
-    pk = _walk_kwargs(proposal, step_width)
+    else:
+        pk = _walk_kwargs(proposal, step_width)
     _check_precision(precision_criterion)
     seeds = [int(s) for s in seeds]
     if not seeds:
         raise ValueError("need at least one seed")
+    if proposal == "region":
+        return _region_ensemble(prior, loglike, ndim, seeds, nlive, kbatch, nsteps, dlogz, max_iter, max_calls, wrapped,
+                                walker_runs, nboot, clusterer, region_runs, region_max_candidates, precision_criterion)
     if adaptive_nsteps is not None and live is not None:
         _check_resident_adaptive(live, distances, "device")
     if live is not None:
@@ -955,159 +1019,19 @@ def run_nested_ensemble(prior: Callable, loglike: Callable, ndim: int, seeds, nl
                                   max_nsteps=max_nsteps, pk=pk, precision_criterion=precision_criterion)
     if walker_runs is None:
         raise ValueError("walker_runs is required (GpuRVModel.slice_walk_runs)")
-    if clustering:
-        clusterer = _default_clusterer(clusterer)
-    defaults = ultranest_defaults(ndim)
-    nlive = int(nlive or defaults["nlive"])
-    kbatch = int(kbatch or max(1, nlive // 4))
-    if not 1 <= kbatch < nlive:
-        raise ValueError("need 1 <= kbatch < nlive")
-    nsteps = int(nsteps or defaults["nsteps"])
-    adapting = _adapt_setup(adaptive_nsteps, nsteps, min_nsteps, max_nsteps, distances)
-    wrapped = None if wrapped is None else np.asarray(wrapped, dtype=bool)
-    runs = [_EnsembleRun(s, nlive, ndim) for s in seeds]
-    for r in runs:
-        r.nsteps = nsteps
-    theta = np.asarray(prior(np.concatenate([r.u for r in runs])), dtype=np.float64)
-    logl = np.asarray(loglike(theta), dtype=np.float64)
-    for i, r in enumerate(runs):
-        r.theta, r.logl = theta[i * nlive:(i + 1) * nlive].copy(), logl[i * nlive:(i + 1) * nlive].copy()
-    stop_gap = np.log(np.expm1(dlogz))
-    while True:
-        turn = []                                   # (run, dead rows, start rows, lstar, chol, walk seed)
-        for r in runs:
-            if r.done:
-                continue
-            if not (r.it < max_iter and r.ncall < max_calls):
-                r.done = True
-                continue
-            t0 = time.perf_counter()
-            order = _stable_argsort(r.logl)
-            dead = order[:kbatch]
-            lstar = r.logl[dead[-1]]
-            dl = r.logl[dead]
-            logw, r.logz, r.h, r.logx = _deaths(r.logz, r.h, r.logx, dl, nlive, kbatch)
-            r.dead_theta.append(r.theta[dead])
-            r.dead_logl.append(dl); r.dead_logw.append(logw)
-            r.dead_birth.append(r.birth[dead])
-            r.birth[dead] = lstar
-            r.it += kbatch
-            alive = order[kbatch:]
-            chol = _whitening(r.u[alive])
-            pick = r.rng.integers(0, len(alive), kbatch)
-            start = alive[pick]
-            turn.append((r, dead, start, lstar, chol, int(r.rng.integers(0, 2 ** 62)), alive, pick))
-            r.timing["host_s"] += time.perf_counter() - t0
-        if not turn:
-            break
-        if adapting:
-            starts = [r.u[st] for r, _d, st, *_x in turn]
-        if clustering:
-            turn = _cluster_turn(turn, clusterer, wrapped, nboot, keep_groups=bool(adapting))
-        else:
-            if adapting:
-                for r, _d, _st, _ls, chol, _sd, alive, _pick in turn:
-                    r.groups = (r.u[alive], None, [chol], np.zeros(kbatch, dtype=np.intp))
-            turn = [t[:6] + (np.arange(kbatch), [kbatch], [t[4]], [t[5]]) for t in turn]
-        # (run, dead rows, start rows, lstar, chol, walk seed, walker order, group sizes, group factors, group seeds)
-        sizes = np.concatenate([t[7] for t in turn])
-        run_start = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-        steps = nsteps
-        if adapting:
-            steps = np.repeat([t[0].nsteps for t in turn], [len(t[7]) for t in turn]).astype(np.int32)
-            steps = int(steps[0]) if np.all(steps == steps[0]) else steps
-        t0 = time.perf_counter()
-        wu, wt, wl, used = walker_runs(np.concatenate([r.u[st[wo]] for r, _, st, _, _, _, wo, *_ in turn]),
-                                       np.concatenate([r.theta[st[wo]] for r, _, st, _, _, _, wo, *_ in turn]),
-                                       np.concatenate([r.logl[st[wo]] for r, _, st, _, _, _, wo, *_ in turn]),
-                                       run_start, np.repeat([t[3] for t in turn], [len(t[7]) for t in turn]),
-                                       np.stack([f for t in turn for f in t[8]]),
-                                       wrapped, steps, 200, [s for t in turn for s in t[9]], **pk)
-        t_walk = time.perf_counter() - t0
-        g = 0
-        for j, (r, dead, _st, _ls, _ch, _sd, wo, gsizes, *_rest) in enumerate(turn):
-            t0 = time.perf_counter()
-            rows = slice(j * kbatch, (j + 1) * kbatch)
-            r.ncall += int(np.sum(used[g:g + len(gsizes)]))
-            g += len(gsizes)
-            back = dead[wo]                                  # the walkers' rows in group order
-            r.u[back], r.theta[back], r.logl[back] = wu[rows], wt[rows], wl[rows]
-            if precision_criterion is not None:
-                if _precision_stop(r.logz, r.logx, r.logl, precision_criterion):
-                    r.done = True
-            elif np.max(r.logl) + r.logx < r.logz + stop_gap:
-                r.done = True
-            r.timing["walk_s"] += t_walk
-            r.timing["turns"] += 1
-            r.timing["host_s"] += time.perf_counter() - t0
-        if adapting:
-            from .adapt import far_fraction, next_nsteps
-            t0 = time.perf_counter()
-            c, f = _adapt_counts([t[0].groups + (starts[j], t[0].u[t[1]]) for j, t in enumerate(turn)], adapting[2], wrapped)
-            dt = (time.perf_counter() - t0) / len(turn)
-            for j, t in enumerate(turn):
-                r = t[0]
-                r.trace.append(r.nsteps)
-                r.fars.append(float(far_fraction(f[j], c[j])))
-                r.nsteps = next_nsteps(r.nsteps, int(f[j]), int(c[j]), adapting[0], adapting[1])
-                r.groups = None
-                r.timing["host_s"] += dt
-    out = []
-    for r in runs:
-        logw_live = r.logx - np.log(nlive) + r.logl
-        logz_final = np.logaddexp(r.logz, _logaddexp_many(logw_live))
-        all_theta = np.vstack([a.reshape(-1, ndim) for a in r.dead_theta] + [r.theta])
-        all_logl = np.concatenate(r.dead_logl + [r.logl])
-        all_logw = np.concatenate(r.dead_logw + [logw_live]) - logz_final
-        out.append(NestedResult(float(logz_final), float(np.sqrt(max(r.h, 0.0) / nlive)), r.it, r.ncall, float(r.h),
-                                all_theta, all_logl, all_logw, r.timing,
-                                np.array(r.nclusters, dtype=np.int64) if clustering else None, nlive=nlive, kbatch=kbatch,
-                                logl_birth=np.concatenate(r.dead_birth + [r.birth]),
-                                nsteps_trace=np.array(r.trace, dtype=np.int64) if adapting else None,
-                                far_fraction=np.array(r.fars, dtype=np.float64) if adapting else None))
-    return out
-
-
-def _cluster_turn(turn, clusterer, wrapped, nboot, keep_groups=False):
-    """run_nested_ensemble(clustering=True): the survivors of every run of the turn clustered in ONE clusterer call, then per
-    run its walkers grouped by cluster as run_nested_slice groups them.  Appends the group order, sizes, factors and seeds
-    to every turn entry; keep_groups: leaves (survivors, labels, factors, walker labels) in every run's `groups`."""
-    t0 = time.perf_counter()
-    uas = [r.u[alive] for r, *_x, alive, _pick in turn]
-    run_start = np.concatenate([[0], np.cumsum([len(ua) for ua in uas])]).astype(np.int64)
-    labels, ncl, _ = clusterer(np.concatenate(uas), run_start, np.stack([_cluster_scale(ua) for ua in uas]), wrapped, nboot,
-                               [(r.seed * _BOOT_MUL + r.it) & _M64 for r, *_x in turn])
-    labels = np.asarray(labels, dtype=np.intp)
-    dt = (time.perf_counter() - t0) / len(turn)
-    out = []
-    for j, (r, dead, start, lstar, chol, wseed, alive, pick) in enumerate(turn):
-        t0 = time.perf_counter()
-        lab = labels[run_start[j]:run_start[j + 1]]
-        r.nclusters.append(int(ncl[j]))
-        factors = _cluster_factors(uas[j], lab, int(ncl[j]), chol)
-        wo, sizes, gf, gseeds = _walk_groups(lab[pick], factors, wseed)
-        if keep_groups:
-            r.groups = (uas[j], lab, factors, lab[pick])
-        out.append((r, dead, start, lstar, chol, wseed, wo, sizes, gf, gseeds))
-        r.timing["host_s"] += dt + time.perf_counter() - t0
-    return out
+    return _walk_ensemble(prior, loglike, None, ndim, seeds, nlive, kbatch, nsteps, dlogz, max_iter, max_calls, wrapped, walker_runs,
+                          clustering, nboot, clusterer, adaptive_nsteps, min_nsteps, max_nsteps, distances, pk, precision_criterion)
 
 
 def _ensemble_resident(live, ndim, seeds, nlive, kbatch, nsteps, dlogz, max_iter, max_calls, wrapped, clustering=False, nboot=30,
                        adaptive_nsteps=None, min_nsteps=None, max_nsteps=None, pk=None, precision_criterion=None):
-    """run_nested_ensemble(live=model): the device_order branch of run_nested_slice for every seed, the runs' live sets resident
+    """run_nested_ensemble(live=model): the device-order form of _slice_resident for every seed, the runs' live sets resident
     side by side (run r = rows r nlive .. r nlive + nlive - 1 of the ensemble), their bookkeeping vectorised across runs.
     clustering: the clustered step, with run r's bootstrap seed (seeds[r] _BOOT_MUL + deaths after this iteration) mod 2^64 —
     what run_nested_slice's host clustered path passes.  adaptive_nsteps: every run walks with its own step count, and the step
     returns the walkers' distances from the device rows (GpuRVModel.live_runs_step(nsteps=[...], return_distances=True))."""
-    defaults = ultranest_defaults(ndim)
-    nlive = int(nlive or defaults["nlive"])
-    kbatch = int(kbatch or max(1, nlive // 4))
-    if not 1 <= kbatch < nlive:
-        raise ValueError("need 1 <= kbatch < nlive")
-    nsteps = int(nsteps or defaults["nsteps"])
+    nlive, kbatch, nsteps, wrapped = _schedule(ndim, nlive, kbatch, nsteps, wrapped)
     adapting = _adapt_setup(adaptive_nsteps, nsteps, min_nsteps, max_nsteps, None)
-    wrapped = None if wrapped is None else np.asarray(wrapped, dtype=bool)
     R = len(seeds)
     steps = np.full(R, nsteps, dtype=np.int64)
     trace, fars = [[] for _ in range(R)], [[] for _ in range(R)]
@@ -1187,19 +1111,11 @@ def _ensemble_resident(live, ndim, seeds, nlive, kbatch, nsteps, dlogz, max_iter
     out = []
     for r in range(R):
         logl = live.live_runs_get(r, cube=False, theta=False)[2]
-        logw_live = logx_run[r] - np.log(nlive) + logl
-        logz_final = np.logaddexp(logz[r], _logaddexp_many(logw_live))
         ndead = live.live_runs_dead_count(r)
         all_theta = np.empty((ndead + nlive, ndim))
         live.live_runs_dead(r, theta_out=all_theta[:ndead])
         live.live_runs_get(r, cube=False, logl=False, theta_out=all_theta[ndead:])
-        all_logl = np.concatenate(dead_logl[r] + [logl])
-        all_logw = np.concatenate(dead_logw[r] + [logw_live]) - logz_final
-        all_birth = np.concatenate(live.live_runs_births(r)) if hasattr(live, "live_runs_births") else None
-        out.append(NestedResult(float(logz_final), float(np.sqrt(max(h[r], 0.0) / nlive)), int(niter[r]), int(ncall[r]), float(h[r]),
-                                all_theta, all_logl, all_logw, timing[r],
-                                np.array(ncls[r], dtype=np.int64) if clustering else None, nlive=nlive, kbatch=kbatch,
-                                logl_birth=all_birth,
-                                nsteps_trace=np.array(trace[r], dtype=np.int64) if adapting else None,
-                                far_fraction=np.array(fars[r], dtype=np.float64) if adapting else None))
+        out.append(_finish(logz[r], h[r], logx_run[r], int(niter[r]), int(ncall[r]), nlive, kbatch, all_theta, dead_logl[r],
+                           dead_logw[r], logl, live.live_runs_births(r) if hasattr(live, "live_runs_births") else None, timing[r],
+                           ncls[r] if clustering else None, trace[r] if adapting else None, fars[r] if adapting else None))
     return out
