@@ -626,6 +626,39 @@ RVLL_HD void rotate_small(double h, double& s, double& c)
     c = c0 + __builtin_fma(c0, ch1, -(s0 * sh));
 }
 
+// ---- one division per log-L item ----------------------------------------------------------------------------------------------
+// An item's planets each give a Keplerian quotient n_p / d_p (n = K cos w (cos E - e) - K q sin w sin E, d = 1 - e cos E >= 0.01)
+// and the item itself one more, res^2 / (2 var).  Four corrected quotients at three planets are 150 of an item's ~2500 cycles, and
+// three of them are not needed: the quotients are pooled over their common denominator,
+//     sum_p n_p / d_p = N / D,  D = prod_p d_p,      res = R - N / D = (R D - N) / D,      res^2 / (2 var) = (R D - N)^2 / (2 var D^2),
+// with R = y - (everything of the model that is no quotient).  D^2 >= 1e-4^Np and <= 2^(2 Np): no range to worry about below
+// seventy planets.  Every step is one rounding of an fp64 product or FMA, R D - N is formed by ONE FMA (the cancellation of a
+// good fit happens inside it), and the one quotient is the corrected one (div_fast): against the sum of separately rounded
+// quotients the item moves by a few 2^-53 of its terms, either way from the exact value (tests/test_item_pool_host.py).
+// The order below is the contract: every instantiation of eval_item (rvll_tile.h) and the host build run exactly this.
+struct ItemPool {
+    double N, D;
+};
+// planet ip of the item joins the pool: the first one starts it, every later one is cross-multiplied in.  A planet whose true
+// anomaly stays 0 (the solver ran out of steps: K cos w, the quotient A / 1) joins as (A, 1.0) — a multiplication by 1 is exact.
+RVLL_HD void pool_add(ItemPool& p, bool first, double num, double den)
+{
+    if (first) {
+        p.N = num;
+        p.D = den;
+    } else {
+        p.N = __builtin_fma(num, p.D, p.N * den);
+        p.D = p.D * den;
+    }
+}
+// res^2 / (2 var) of the item: R = y - (offset + sum_p K e cos w + drift + linear terms).  A pool nothing joined is {0, 1}: the
+// residual is then R itself, bit for bit (fma(R, 1, -0) = R, (var + var) (1 * 1) = 2 var).
+RVLL_HD double pool_chi2(const ItemPool& p, double R, double var)
+{
+    const double T = __builtin_fma(R, p.D, -p.N);
+    return div_fast(T * T, (var + var) * (p.D * p.D));
+}
+
 // ---- the pair at E + h from the pair at E, between Newton steps --------------------------------------------------------------
 // From its second evaluation on a Newton solve wants (sin, cos) at E + h with (sin E, cos E) in registers and h, the step just
 // taken, known: the pair at E + h is the old pair rotated by h, and sin h, cos h - 1 need no range reduction, no quadrant and

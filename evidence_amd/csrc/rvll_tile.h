@@ -277,6 +277,15 @@ struct ItemCtx {
 __device__ __forceinline__ bool f32_astray(float E, float Mf, float tolf) { return !(fabsf(E - Mf) <= 1.0f + tolf); }
 
 // One (point, epoch) item: returns res^2 / (2 var) (the ln sqrt(var) of rvmodel:80 is summed per point by tile_logdet).
+// fp64 forms ONE quotient per item (rvll_math.h, ItemPool), so the reference's lines no longer map to operations one to one:
+//   rvmodel:187  rvm = 0 + offset                        the decode step's 0. + offset (L.ins), read here as it is
+//   rvmodel:463  K (cos(nu + w) + e cos w) per planet    split: the quotient num / den = K cos(nu + w) stays a pair, the constant
+//                                                        K e cos w is summed over the planets, in planet order, by the decode
+//                                                        step (P[7] of the point's first planet) and added to rvm ONCE
+//   rvmodel:383  the sum over the planets                pool_add: N / D = sum_p num_p / den_p, never divided out
+//   rvmodel:199  rvm += kep, :215 res = y - rvm, :80     pool_chi2: with R = y - rvm (rvm: offset, constants, drift, linear terms),
+//                                                        res = (R D - N) / D and res^2 / (2 var) = (R D - N)^2 / (2 var D^2)
+// The reduced-precision branch keeps the reference's sequence (one quotient and one K e cos w per planet, their sum, the residual).
 // FAILCHECK: honour the itmax marks of earlier solves (nu = 0 from the first failing epoch of that planet on).  The
 // first pass over a tile runs without it: the marks can only come from that very pass, and every point that got one
 // is re-evaluated with FAILCHECK afterwards (3b of loglike_tile) — so the normal path carries no reads of the marks.
@@ -299,26 +308,34 @@ __device__ __forceinline__ double eval_item(const LoglikeArgs& a, const ItemCtx&
     const int    in = a.inst[j];
 
     const double2 oj = *reinterpret_cast<const double2*>(cx.ins + (pl * a.Ni + in) * 2);
-    double rvm = 0. + oj.x;                                   // rvmodel:187
+    // what of the model is no quotient.  fp64: 0 + offset (rvmodel:187; the decode step has added the 0) + sum_p K e cos w (the
+    // constant of rvmodel:463's K (cos(nu + w) + e cos w), summed over the planets by the decode step: P[7] of the first one);
+    // reduced precision: 0 + offset, every planet's whole term is added below
+    double rvm = PREC == RVLL_PREC_FP64 ? oj.x : 0. + oj.x;
     const double var = s2 + oj.y;                             // rvmodel:189-192 (oj.y = jitter^2 or 0)
 
     const int Np = NP > 0 ? NP : a.Np;
+    [[maybe_unused]] ItemPool pool{0., 1.};                   // fp64: the planets' quotients over one denominator (rvll_math.h)
     if (Np > 0) {
         const bool wide = __builtin_amdgcn_readfirstlane(*cx.wide) != 0;
         bool point_failed = false;
         if constexpr (FAILCHECK) point_failed = cx.anyfail[pl] != 0;
         double ksum = 0.;
+        if constexpr (PREC == RVLL_PREC_FP64) rvm += cx.pp[pl * Np * kPlanetFields + 7];
 #pragma clang loop unroll_count(NP > 0 ? NP : 1)
         for (int ip = 0; ip < Np; ++ip) {
             const double* P = cx.pp + (pl * Np + ip) * kPlanetFields;
             const double2 p01 = *reinterpret_cast<const double2*>(P);       // w, epoch
             const double2 p23 = *reinterpret_cast<const double2*>(P + 2);   // ma0, ec
             const double2 p45 = *reinterpret_cast<const double2*>(P + 4);   // A=K cos w, Bq=K q sin w
-            const double  C0  = P[6];                                       // K e cos w
             const double ec = p23.y;
-            double rv;
+            // fp64: the planet's quotient num / den = K (cos(nu + w)), joined to the pool below; nu = 0 is A / 1
+            [[maybe_unused]] double num, den;
+            [[maybe_unused]] double rv;                                     // reduced precision: the planet's whole term
             if (FAILCHECK && point_failed && j >= cx.jfail[pl * Np + ip]) {
-                rv = p45.x + C0;            // nu left at 0 (rvmodel:488, trueanomaly.c:32-33)
+                // nu left at 0 (rvmodel:488, trueanomaly.c:32-33): K cos w + K e cos w
+                if constexpr (PREC == RVLL_PREC_FP64) { num = p45.x; den = 1.0; }
+                else                                  rv = p45.x + P[6];
             } else if constexpr (PREC == RVLL_PREC_FP64) {
                 // mean anomaly, rvmodel:459 — two roundings in (t-epoch), then mul, then add
                 const double M = p01.x * (t - p01.y) + p23.x;
@@ -417,32 +434,34 @@ __device__ __forceinline__ double eval_item(const LoglikeArgs& a, const ItemCtx&
                         // the failing items of both passes, a function of the point alone.
                         if (atomicMin(&cx.jfail[pl * Np + ip], j) > j) atomicOr(cx.nfail, 4);
                         atomicOr(&cx.anyfail[pl], 1);
-                        rv = p45.x + C0;
                     } else {
                         atomicMin(&cx.jfail[pl * Np + ip], j);
                         atomicOr(&cx.anyfail[pl], 1);
                         atomicOr(cx.nfail, 1);
-                        rv = p45.x + C0;
                     }
+                    num = p45.x;                // nu left at 0: A / 1
+                    den = 1.0;
                 } else {
                     // (s, c) are at the previous iterate; the accepted step |dE| <= tol:
                     // rotate instead of a third range reduction.
                     if (a.tol <= 1e-3) rotate_small(dE, s, c);
                     else               sincos_any(E, s, c, kc);
-                    // K (cos(nu+w) + e cos w) with cos nu = (cos E - e)/(1 - e cos E),
-                    // sin nu = sqrt(1-e^2) sin E/(1 - e cos E)  == trueanomaly.c:36 + rvmodel:463
-                    const double den = __builtin_fma(-ec, c, 1.0);
-                    const double num = __builtin_fma(p45.x, c - ec, -(p45.y * s));
-                    rv = div_fast(num, den) + C0;
+                    // K cos(nu+w) = num / den with cos nu = (cos E - e)/(1 - e cos E), sin nu = sqrt(1-e^2) sin E/(1 - e cos E)
+                    // == trueanomaly.c:36 + rvmodel:463 without its constant K e cos w (in rvm already); the quotient itself
+                    // is never formed: it joins the item's pool
+                    den = __builtin_fma(-ec, c, 1.0);
+                    num = __builtin_fma(p45.x, c - ec, -(p45.y * s));
                     // the first pass leaves an item with a wandering solve as NaN: the redo pass (3b) finds the item by it and
                     // does it again with correctly rounded sin / cos — that item, not the 200 of its point: in a sampler's
                     // candidates, unlike in prior draws, points with a planet at e >= 0.97 are common, and redoing whole points
                     // cost the walk a third of its rate (profiles/r04_high_ecc_parity.txt)
-                    if constexpr (!CR && !FAILCHECK) { if (__builtin_expect(wander, 0)) rv = __builtin_nan(""); }
+                    // (through the pooled numerator: NaN N, NaN contribution)
+                    if constexpr (!CR && !FAILCHECK) { if (__builtin_expect(wander, 0)) num = __builtin_nan(""); }
                 }
             } else {
                 // reduced precision: phase in fp64 (|M| ~ 1e4 rad, rvmodel:459), reduced to [-pi, pi]
                 // in fp64, then the same Newton rule (start E = M, stop |dE| <= tol, >= 1 step) in fp32
+                const double C0 = P[6];                                     // K e cos w
                 const double M = p01.x * (t - p01.y) + p23.x;
                 const float Mf = reduce_2pi_to_f32(M);
                 const float ecf = (float)ec, tolf = (float)a.tol;
@@ -492,9 +511,10 @@ __device__ __forceinline__ double eval_item(const LoglikeArgs& a, const ItemCtx&
                     rv = p45.x + C0;
                 }
             }
-            ksum += rv;                                                     // rvmodel:383
+            if constexpr (PREC == RVLL_PREC_FP64) pool_add(pool, ip == 0, num, den);   // rvmodel:383, as N / D
+            else                                  ksum += rv;                          // rvmodel:383
         }
-        rvm += ksum;                                                        // rvmodel:199
+        if constexpr (PREC != RVLL_PREC_FP64) rvm += ksum;                  // rvmodel:199
     }
 
     if constexpr (EXTRAS) {
@@ -508,8 +528,18 @@ __device__ __forceinline__ double eval_item(const LoglikeArgs& a, const ItemCtx&
             rvm += cx.lin[pl * a.nlin + k] * a.linpar[(size_t)k * a.Ne + j];
     }
 
-    const double res = y - rvm;                                             // rvmodel:215
+    // fp64: rvm holds everything but the quotients, R = y - rvm, and rvmodel:199 + :215 + :80 are the pool's one division,
+    // (R D - N)^2 / (2 var D^2); without planets (N = 0, D = 1) that is R^2 / (2 var), the bits of the separate form
+    if constexpr (PREC == RVLL_PREC_FP64) {
 #ifdef RVLL_AB_NO_LOGDET              // (measurement builds only: the normalisation term per item, as up to round 2)
+        return 0.5 * log_pos(var) + pool_chi2(pool, y - rvm, var);
+#else
+        // the point's ln sqrt(var) terms are summed by tile_logdet, once per point
+        return pool_chi2(pool, y - rvm, var);
+#endif
+    }
+    const double res = y - rvm;                                             // rvmodel:215
+#ifdef RVLL_AB_NO_LOGDET
     if constexpr (PREC == RVLL_PREC_FP32) {
         const float rf = (float)res, vf = (float)var;
         return (double)(0.5f * __logf(vf) + div_f32(rf * rf, 2.0f * vf));
@@ -763,68 +793,92 @@ __device__ RVLL_DECODE_INLINE void tile_decode(const LoglikeArgs& __restrict__ a
     const rvll_planet* lp = reinterpret_cast<const rvll_planet*>(L.lay);
     const rvll_inst*   li = reinterpret_cast<const rvll_inst*>(L.lay + a.Np * kPlanetDoubles);
     const rvll_slot*   ll = reinterpret_cast<const rvll_slot*>(L.lay + a.Np * kPlanetDoubles + a.Ni * kInstDoubles);
-    for (int wk = tid; wk < npts * a.Np; wk += NT) {
-        const int pl = wk / a.Np;
-        const int k  = wk - pl * a.Np;
-        const double* th = L.theta_s + pl * a.D;
-        // All six slots first (one 16-byte LDS read each), then the six theta values they point at: two LDS round
-        // trips instead of twelve dependent ones — measured, the slot reads were 1900 of the decode's 2800 cycles.
-        const rvll_planet d = lp[k];
-        const double tk = th[max(d.k.idx, 0)], tp = th[max(d.p.idx, 0)], t1 = th[max(d.e1.idx, 0)],
-                     t2 = th[max(d.e2.idx, 0)], ta = th[max(d.anom.idx, 0)], te = th[max(d.epoch.idx, 0)];
-        const double kraw = d.k.idx >= 0 ? tk : d.k.val;
-        const double praw = d.p.idx >= 0 ? tp : d.p.val;
-        const double K = d.k_kind == RVLL_K_LOGK1 ? exp(kraw) : kraw;
-        const double Pd = d.p_kind == RVLL_P_LOGPERIOD ? exp(praw) : praw;
-        const double e1 = d.e1.idx >= 0 ? t1 : d.e1.val;
-        const double e2 = d.e2.idx >= 0 ? t2 : d.e2.val;
-        double ecc, omega;
-        if (d.ecc_kind == RVLL_ECC_SECOS_SESIN) {
-            ecc = e1 * e1 + e2 * e2;
-            omega = atan2(e2, e1);
-            if (ecc > 1) atomicOr(&L.pflags[pl], RVLL_FLAG_INVALID_ORBIT);
-        } else if (d.ecc_kind == RVLL_ECC_ECOS_ESIN) {
-            ecc = sqrt(e1 * e1 + e2 * e2);
-            omega = atan2(e2, e1);
-            if (ecc > 1) atomicOr(&L.pflags[pl], RVLL_FLAG_INVALID_ORBIT);
-        } else {
-            ecc = e1;
-            omega = e2;
-        }
-        const double anom = d.anom.idx >= 0 ? ta : d.anom.val;
-        const double ma0 = d.anom_kind == RVLL_ANOM_ML0 ? anom - omega : anom;
-        const double ec = ecc > 0.99 ? 0.99 : ecc;                  // trueanomaly.c:11-12
-        // a planet this eccentric may hold a solve that wanders for hundreds of steps: the CU-wide form starts its tickets
-        // at the wave round the tile's most eccentric such point begins in (loglike_tile).  Key: eccentricity above the
-        // threshold (0 .. 30: ec <= 0.99) over that round, in the upper bits of the ticket word — atomicMax keeps the most
-        // eccentric; no ticket has been drawn yet (the barrier after this step comes first)
+    // The planets of a point sit in ONE wave (64 / Np points a wave, lanes left over idle; beyond 64 planets a wave takes one
+    // point, 64 planets of it a pass): the point's sum of K e cos w — what of rvmodel:463 is no quotient, a constant of the
+    // point the fp64 item reads as one number (eval_item) — is then added up in planet order by the lane of the first planet
+    // from what the wave's own lanes have just written, with no barrier of the workgroup in between.
+    const int lane_d = tid & (kWave - 1);
+    const int ppw = a.Np <= kWave ? kWave / max(a.Np, 1) : 1;                    // points a wave
+    const int nchunk = a.Np <= kWave ? 1 : (a.Np + kWave - 1) / kWave;           // passes a point
+    const int q_d = a.Np <= kWave ? lane_d / max(a.Np, 1) : 0;                   // this lane's point within its wave, its planet
+    const int k_d = lane_d - q_d * a.Np;
+    for (int g = tid >> 6, c = 0; g * ppw < npts && a.Np > 0; ) {               // (g, c: wave-uniform)
+        const int pl = g * ppw + q_d;
+        const int k = k_d + c * kWave;
+        const bool mine = q_d < ppw && pl < npts;
+        if (mine && k < a.Np) {
+            const double* th = L.theta_s + pl * a.D;
+            // All six slots first (one 16-byte LDS read each), then the six theta values they point at: two LDS round
+            // trips instead of twelve dependent ones — measured, the slot reads were 1900 of the decode's 2800 cycles.
+            const rvll_planet d = lp[k];
+            const double tk = th[max(d.k.idx, 0)], tp = th[max(d.p.idx, 0)], t1 = th[max(d.e1.idx, 0)],
+                         t2 = th[max(d.e2.idx, 0)], ta = th[max(d.anom.idx, 0)], te = th[max(d.epoch.idx, 0)];
+            const double kraw = d.k.idx >= 0 ? tk : d.k.val;
+            const double praw = d.p.idx >= 0 ? tp : d.p.val;
+            const double K = d.k_kind == RVLL_K_LOGK1 ? exp(kraw) : kraw;
+            const double Pd = d.p_kind == RVLL_P_LOGPERIOD ? exp(praw) : praw;
+            const double e1 = d.e1.idx >= 0 ? t1 : d.e1.val;
+            const double e2 = d.e2.idx >= 0 ? t2 : d.e2.val;
+            double ecc, omega;
+            if (d.ecc_kind == RVLL_ECC_SECOS_SESIN) {
+                ecc = e1 * e1 + e2 * e2;
+                omega = atan2(e2, e1);
+                if (ecc > 1) atomicOr(&L.pflags[pl], RVLL_FLAG_INVALID_ORBIT);
+            } else if (d.ecc_kind == RVLL_ECC_ECOS_ESIN) {
+                ecc = sqrt(e1 * e1 + e2 * e2);
+                omega = atan2(e2, e1);
+                if (ecc > 1) atomicOr(&L.pflags[pl], RVLL_FLAG_INVALID_ORBIT);
+            } else {
+                ecc = e1;
+                omega = e2;
+            }
+            const double anom = d.anom.idx >= 0 ? ta : d.anom.val;
+            const double ma0 = d.anom_kind == RVLL_ANOM_ML0 ? anom - omega : anom;
+            const double ec = ecc > 0.99 ? 0.99 : ecc;                  // trueanomaly.c:11-12
+            // a planet this eccentric may hold a solve that wanders for hundreds of steps: the CU-wide form starts its tickets
+            // at the wave round the tile's most eccentric such point begins in (loglike_tile).  Key: eccentricity above the
+            // threshold (0 .. 30: ec <= 0.99) over that round, in the upper bits of the ticket word — atomicMax keeps the most
+            // eccentric; no ticket has been drawn yet (the barrier after this step comes first)
 #ifndef RVLL_AB_NO_ROT
-        if (ec >= kLongSolveEcc)
-            atomicMax(L.ticket, ((int)((ec - kLongSolveEcc) * 340.) << (kTicketBits + kTicketRoundBits)) |
-                                (min((pl * a.Ne) >> 6, kTicketRoundMask) << kTicketBits));
+            if (ec >= kLongSolveEcc)
+                atomicMax(L.ticket, ((int)((ec - kLongSolveEcc) * 340.) << (kTicketBits + kTicketRoundBits)) |
+                                    (min((pl * a.Ne) >> 6, kTicketRoundMask) << kTicketBits));
 #endif
-        double so, co;
-        sincos_any(omega, so, co);                                  // (omega is a free parameter: any finite value)
-        const double q = sqrt((1. - ec) * (1. + ec));
-        double* P = L.pp + (pl * a.Np + k) * kPlanetFields;
-        P[0] = kTwoPi / Pd;
-        P[1] = d.epoch.idx >= 0 ? te : d.epoch.val;
-        P[2] = ma0;
-        P[3] = ec;
-        P[4] = K * co;
-        P[5] = K * q * so;
-        P[6] = K * (ecc * co);
-        // a bound on |M| over the epoch table: the solver's first eight steps skip the range check of their sin / cos
-        // arguments when it is below 2^48 for every planet of the tile (eval_item)
-        const double ep = d.epoch.idx >= 0 ? te : d.epoch.val;
-        const double mbound = fabs(kTwoPi / Pd) * fmax(fabs(a.tmax - ep), fabs(a.tmin - ep)) + fabs(ma0);
-        if (!(mbound < kExcursionM)) atomicOr(L.wide, 1);
-        P[7] = 0.;
+            double so, co;
+            sincos_any(omega, so, co);                                  // (omega is a free parameter: any finite value)
+            const double q = sqrt((1. - ec) * (1. + ec));
+            double* P = L.pp + (pl * a.Np + k) * kPlanetFields;
+            P[0] = kTwoPi / Pd;
+            P[1] = d.epoch.idx >= 0 ? te : d.epoch.val;
+            P[2] = ma0;
+            P[3] = ec;
+            P[4] = K * co;
+            P[5] = K * q * so;
+            P[6] = K * (ecc * co);
+            // a bound on |M| over the epoch table: the solver's first eight steps skip the range check of their sin / cos
+            // arguments when it is below 2^48 for every planet of the tile (eval_item)
+            const double ep = d.epoch.idx >= 0 ? te : d.epoch.val;
+            const double mbound = fabs(kTwoPi / Pd) * fmax(fabs(a.tmax - ep), fabs(a.tmin - ep)) + fabs(ma0);
+            if (!(mbound < kExcursionM)) atomicOr(L.wide, 1);
+            P[7] = 0.;
+        }
+        // P[6] of the point's planets are in LDS, written by lanes of this wave (LDS operations of one wave complete in order)
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        const bool last = c == nchunk - 1;
+        if (last && mine && k_d == 0) {
+            double* P0 = L.pp + pl * a.Np * kPlanetFields;
+            double sum = P0[6];
+            for (int k2 = 1; k2 < a.Np; ++k2) sum += P0[k2 * kPlanetFields + 6];
+            P0[7] = sum;
+        }
+        if (last) { c = 0; g += NT / kWave; } else ++c;
     }
     for (int pl = NT - 1 - tid; pl < npts; pl += NT) {
         const double* th = L.theta_s + pl * a.D;
         for (int i = 0; i < a.Ni; ++i) {
-            L.ins[(pl * a.Ni + i) * 2] = slot_lds(&li[i].offset, th);
+            L.ins[(pl * a.Ni + i) * 2] = 0. + slot_lds(&li[i].offset, th);      // rvmodel:187: the items' 0 + offset, added once here
             double j2 = 0.;
             if (a.has_jitter) { const double jit = slot_lds(&li[i].jitter, th); j2 = jit * jit; }
             L.ins[(pl * a.Ni + i) * 2 + 1] = j2;
@@ -1170,8 +1224,16 @@ __device__ __forceinline__ __attribute__((flatten)) void loglike_tile(const Logl
             for (;;) {
                 for (int i = base + tid; i < cend; i += NT) {
                     const int pl = i / a.Ne;
+                    // (itmax <= kSafeSteps: no solve can wander, there is nothing to round correctly, and the redo takes the first
+                    // pass's arithmetic — CR with the shortcut off would run EVERY solve on sincos_cr, other bits than the first pass
+                    // gave the same solve, and which items of a point are redone differs between the forms: an itmax mark deep in
+                    // the epoch array is redone from its LDS window on in the tile form, from the point's start in the CU-wide
+                    // one.  The pooled item shows such a last-bit difference where the separate quotients happened to hide it:
+                    // tests/test_gpu_solver_settings.py, 9000 epochs.  Chosen here, not inside eval_item: there it moved scalar
+                    // spills of the item loop, +0.45 us on every launch — profiles/r06_item_pool.txt)
                     if (L.anyfail[pl] || contrib[i - base] != contrib[i - base])       // a point with an itmax failure; an item left as NaN
-                        contrib[i - base] = eval_item<PREC, true, EXTRAS, PREC == RVLL_PREC_FP64, NP>(a, cx, pl, i - pl * a.Ne);
+                        contrib[i - base] = a.itmax > kSafeSteps ? eval_item<PREC, true, EXTRAS, PREC == RVLL_PREC_FP64, NP>(a, cx, pl, i - pl * a.Ne)
+                                                                 : eval_item<PREC, true, EXTRAS, false, NP>(a, cx, pl, i - pl * a.Ne);
                 }
                 __syncthreads();
                 // a correctly rounded redo lowered a mark (eval_item, CR): the items of that point once more, until no pass does —

@@ -19,6 +19,11 @@
  *                            -> :343-385 (kep_rv) -> :388-463 (modelk)
  *                            -> :466-494 (true_anomaly) -> rvmodel/trueanomaly.c:8-41
  *                            -> :222-273 (drift) -> :59-80 (logL)
+ *                            (fp64: the planets' Keplerian quotients of :463 and
+ *                            the res^2 / (2 var) of :80 are pooled over one
+ *                            denominator and divided once per (point, epoch);
+ *                            the constants K e cos w of :463 are summed per
+ *                            point: rvll_math.h ItemPool, rvll_tile.h eval_item)
  *                            i.e. it is the batched form of the existing FFI
  *                            `int trueanomaly(double*,int,double,double*,int,double)`
  *                            (rvmodel/trueanomaly.h:4) fused with its caller.
