@@ -432,6 +432,12 @@ void debug_eval_kernel(int op, const double* x, const double* y, long long n, do
             break; }
         // the rotation between Newton steps: the pair at x rotated by y (tests/test_gpu_rotate.py)
         case 36: case 37: sincos_f64(a, s, c); rotate_mid(b, s, c); r = op == 36 ? s : c; break;
+        // the Newton step's residuals f, f' (tests/test_gpu_newton_fused.py): x holds records (E, s, c, e, M) of five doubles,
+        // the result stands at the record's first element (NaN elsewhere and for a record cut short by n)
+        case 38: case 39: {
+            r = NAN;
+            if (i % 5 == 0 && i + 4 < n) { double f, fp; newton_residuals(a, x[i + 1], x[i + 2], x[i + 3], x[i + 4], f, fp); r = op == 38 ? f : fp; }
+            break; }
         default: r = NAN; break;
         }
         out[i] = r;

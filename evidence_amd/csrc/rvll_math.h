@@ -741,6 +741,24 @@ RVLL_HD void newton_next_sincos(double E, double h, int k, double& s, double& c,
     }
 }
 
+// The residuals of one Newton step, f = E - e sin E - M and f' = 1 - e cos E, from the pair (s, c) at E.  The reference rounds
+// every operation (trueanomaly.c:25-26: E - ecc * sin(E) - M, 1 - ecc * cos(E); five operations); here the two products are
+// fused into the subtractions that follow them: f = fma(-e, s, E) - M, f' = fma(-e, c, 1), three operations.  The fused form is
+// the more accurate one — it drops the product's own rounding (<= 2^-53) beside the subtraction's (half an ulp of E, 1e-12 at
+// |E| ~ 1e4) — and differs from the reference's on about 1e-4 of the steps at such E, more often at small |E|: a perturbation
+// of the size the rotated pair carries already.  It may stand in for the reference's line wherever a solve ends within
+// kSafeSteps steps: there Newton's iteration contracts, the last-bit difference moves the root by a few ulp (measured on the
+// host build: tests/test_newton_fused_host.py) and the step count on no solve in millions; a solve that goes on beyond
+// kSafeSteps — where the reference wanders and where it stops hangs on last bits — starts again from E = M on the reference's
+// own separately rounded operations, in the first pass and in the correctly rounded redo alike (eval_item), so nothing of these
+// steps survives in it.  The quotient f / f' and the step E - q stay as they are.  A function of its arguments alone: host and
+// device give the same bits.
+RVLL_HD void newton_residuals(double E, double s, double c, double ec, double M, double& f, double& fp)
+{
+    f  = __builtin_fma(-ec, s, E) - M;
+    fp = __builtin_fma(-ec, c, 1.0);
+}
+
 // (sin r, cos r) of the reduced argument -> (sin x, cos x) by the quadrant: swap and signs with bit operations (compare +
 // v_cndmask cost ~4 cycles each, measured)
 RVLL_HD void quadrant_f32(float sr, float cr, uint32_t uq, float& s_out, float& c_out)

@@ -357,8 +357,8 @@ __device__ __forceinline__ double eval_item(const LoglikeArgs& a, const ItemCtx&
                     do {
                         // from the second evaluation on the pair is rotated by the step just taken (rvll_math.h)
                         newton_next_sincos<false>(E, dE, steps, s, c, kc);
-                        const double f  = E - ec * s - M;
-                        const double fp = 1 - ec * c;
+                        double f, fp;
+                        newton_residuals(E, s, c, ec, M, f, fp);       // the products fused into their subtractions (rvll_math.h)
                         const double En = E - div_exact(f, fp);        // == f / fp, correctly rounded
                         dE = En - E;
                         E = En;
@@ -373,8 +373,8 @@ __device__ __forceinline__ double eval_item(const LoglikeArgs& a, const ItemCtx&
                         int steps = 0;
                         do {
                             newton_next_sincos<true>(E, dE, steps, s, c, kc);
-                            const double f  = E - ec * s - M;
-                            const double fp = 1 - ec * c;
+                            double f, fp;
+                            newton_residuals(E, s, c, ec, M, f, fp);
                             const double En = E - div_exact(f, fp);
                             dE = En - E;
                             E = En;
@@ -398,17 +398,31 @@ __device__ __forceinline__ double eval_item(const LoglikeArgs& a, const ItemCtx&
 #endif
                     int steps = shortcut ? kSafeSteps : 0;
                     if constexpr (CR) { E = M; steps = 0; }       // (the first eight steps seed where it ends as much as the later ones)
+                    // The first pass: while this loop makes a solve's first kSafeSteps steps itself (the shortcut is off) it forms
+                    // the residuals by the shortcut loop's fused rule (rvll_math.h, newton_residuals): the same bits.  A solve still
+                    // going after those steps, here or in the shortcut loop, keeps nothing of them: it starts again from E = M on
+                    // the reference's separately rounded residuals (trueanomaly.c:25-26) — where it ends, and whether it runs out
+                    // of steps at a middling itmax, which marks the planet's array (tests/test_gpu_solver_settings.py), hang on
+                    // the last bit of every step it took.  The redo pass is the reference's arithmetic throughout.
+                    [[maybe_unused]] bool fused = !CR;
                     do {
+                        if constexpr (!CR) {
+                            if (fused && steps >= kSafeSteps) { E = M; dE = __builtin_inf(); steps = 0; fused = false; }
+                        }
 #ifdef RVLL_CR_FAKE                // (measurement builds only: the redo pass with the ordinary sin / cos — what the correctly rounded pair costs)
                         sincos_any(E, s, c, kc);
 #else
-                        // (below kSafeSteps — the shortcut is off — the pair of step k is the shortcut loop's: the same rule)
+                        // (below kSafeSteps the pair of step k is the shortcut loop's: the same rule)
                         if constexpr (CR)            sincos_cr(E, s, c);
                         else if (steps < kSafeSteps) newton_next_sincos<true>(E, dE, steps, s, c, kc);
                         else                         sincos_any(E, s, c, kc);
 #endif
-                        const double f  = E - ec * s - M;
-                        const double fp = 1 - ec * c;
+                        double f, fp;
+                        newton_residuals(E, s, c, ec, M, f, fp);
+                        if (CR || !fused) {
+                            f  = E - ec * s - M;
+                            fp = 1 - ec * c;
+                        }
                         const double En = E - div_exact(f, fp);
                         dE = En - E;
                         E = En;
@@ -783,97 +797,112 @@ __device__ __forceinline__ void tile_stage(const LoglikeArgs& __restrict__ a, co
     for (int i = tid; i < layout_doubles(a.Np, a.Ni, a.nlin); i += NT) L.lay[i] = a.layblob[i];
 }
 
+// One (point, planet) of the decode step: rvmodel:412-456 into the planet's fields in LDS (P[7], the point's sum of K e cos w,
+// is left 0 here: tile_decode).
+__device__ __forceinline__ void decode_planet(const LoglikeArgs& __restrict__ a, const TileLds& L, const rvll_planet* lp, int pl, int k)
+{
+    const double* th = L.theta_s + pl * a.D;
+    // All six slots first (one 16-byte LDS read each), then the six theta values they point at: two LDS round
+    // trips instead of twelve dependent ones — measured, the slot reads were 1900 of the decode's 2800 cycles.
+    const rvll_planet d = lp[k];
+    const double tk = th[max(d.k.idx, 0)], tp = th[max(d.p.idx, 0)], t1 = th[max(d.e1.idx, 0)],
+                 t2 = th[max(d.e2.idx, 0)], ta = th[max(d.anom.idx, 0)], te = th[max(d.epoch.idx, 0)];
+    const double kraw = d.k.idx >= 0 ? tk : d.k.val;
+    const double praw = d.p.idx >= 0 ? tp : d.p.val;
+    const double K = d.k_kind == RVLL_K_LOGK1 ? exp(kraw) : kraw;
+    const double Pd = d.p_kind == RVLL_P_LOGPERIOD ? exp(praw) : praw;
+    const double e1 = d.e1.idx >= 0 ? t1 : d.e1.val;
+    const double e2 = d.e2.idx >= 0 ? t2 : d.e2.val;
+    double ecc, omega;
+    if (d.ecc_kind == RVLL_ECC_SECOS_SESIN) {
+        ecc = e1 * e1 + e2 * e2;
+        omega = atan2(e2, e1);
+        if (ecc > 1) atomicOr(&L.pflags[pl], RVLL_FLAG_INVALID_ORBIT);
+    } else if (d.ecc_kind == RVLL_ECC_ECOS_ESIN) {
+        ecc = sqrt(e1 * e1 + e2 * e2);
+        omega = atan2(e2, e1);
+        if (ecc > 1) atomicOr(&L.pflags[pl], RVLL_FLAG_INVALID_ORBIT);
+    } else {
+        ecc = e1;
+        omega = e2;
+    }
+    const double anom = d.anom.idx >= 0 ? ta : d.anom.val;
+    const double ma0 = d.anom_kind == RVLL_ANOM_ML0 ? anom - omega : anom;
+    const double ec = ecc > 0.99 ? 0.99 : ecc;                  // trueanomaly.c:11-12
+    // a planet this eccentric may hold a solve that wanders for hundreds of steps: the CU-wide form starts its tickets
+    // at the wave round the tile's most eccentric such point begins in (loglike_tile).  Key: eccentricity above the
+    // threshold (0 .. 30: ec <= 0.99) over that round, in the upper bits of the ticket word — atomicMax keeps the most
+    // eccentric; no ticket has been drawn yet (the barrier after this step comes first)
+#ifndef RVLL_AB_NO_ROT
+    if (ec >= kLongSolveEcc)
+        atomicMax(L.ticket, ((int)((ec - kLongSolveEcc) * 340.) << (kTicketBits + kTicketRoundBits)) |
+                            (min((pl * a.Ne) >> 6, kTicketRoundMask) << kTicketBits));
+#endif
+    double so, co;
+    sincos_any(omega, so, co);                                  // (omega is a free parameter: any finite value)
+    const double q = sqrt((1. - ec) * (1. + ec));
+    double* P = L.pp + (pl * a.Np + k) * kPlanetFields;
+    P[0] = kTwoPi / Pd;
+    P[1] = d.epoch.idx >= 0 ? te : d.epoch.val;
+    P[2] = ma0;
+    P[3] = ec;
+    P[4] = K * co;
+    P[5] = K * q * so;
+    P[6] = K * (ecc * co);
+    // a bound on |M| over the epoch table: the solver's first eight steps skip the range check of their sin / cos
+    // arguments when it is below 2^48 for every planet of the tile (eval_item)
+    const double ep = d.epoch.idx >= 0 ? te : d.epoch.val;
+    const double mbound = fabs(kTwoPi / Pd) * fmax(fabs(a.tmax - ep), fabs(a.tmin - ep)) + fabs(ma0);
+    if (!(mbound < kExcursionM)) atomicOr(L.wide, 1);
+    P[7] = 0.;
+}
+
 // 2. decode per-point scalars once (rvmodel:412-456, :181-192, :242-260): one lane per (point, planet) from the
 //    front of the workgroup, one lane per point for the instrument / drift / linear terms from its back, so the two
 //    kinds of work sit in different waves whenever the tile leaves room
-template <int NT>
+// SUM: the point's sum of K e cos w is formed here (P[7] of its first planet) — the fp64 item reads it (eval_item); the
+// reduced-precision items add K e cos w per planet and never look at P[7], so their kernels take the flat loop without it: the
+// wave-local loop the sum needs cost them 4 VGPRs and 17 spilled SGPRs (profiles/r06_item_pool.txt, r07_newton_fused.txt).
+template <int NT, bool SUM>
 __device__ RVLL_DECODE_INLINE void tile_decode(const LoglikeArgs& __restrict__ a, const TileLds& L, int npts)
 {
     const int tid = threadIdx.x;
     const rvll_planet* lp = reinterpret_cast<const rvll_planet*>(L.lay);
     const rvll_inst*   li = reinterpret_cast<const rvll_inst*>(L.lay + a.Np * kPlanetDoubles);
     const rvll_slot*   ll = reinterpret_cast<const rvll_slot*>(L.lay + a.Np * kPlanetDoubles + a.Ni * kInstDoubles);
-    // The planets of a point sit in ONE wave (64 / Np points a wave, lanes left over idle; beyond 64 planets a wave takes one
-    // point, 64 planets of it a pass): the point's sum of K e cos w — what of rvmodel:463 is no quotient, a constant of the
-    // point the fp64 item reads as one number (eval_item) — is then added up in planet order by the lane of the first planet
-    // from what the wave's own lanes have just written, with no barrier of the workgroup in between.
-    const int lane_d = tid & (kWave - 1);
-    const int ppw = a.Np <= kWave ? kWave / max(a.Np, 1) : 1;                    // points a wave
-    const int nchunk = a.Np <= kWave ? 1 : (a.Np + kWave - 1) / kWave;           // passes a point
-    const int q_d = a.Np <= kWave ? lane_d / max(a.Np, 1) : 0;                   // this lane's point within its wave, its planet
-    const int k_d = lane_d - q_d * a.Np;
-    for (int g = tid >> 6, c = 0; g * ppw < npts && a.Np > 0; ) {               // (g, c: wave-uniform)
-        const int pl = g * ppw + q_d;
-        const int k = k_d + c * kWave;
-        const bool mine = q_d < ppw && pl < npts;
-        if (mine && k < a.Np) {
-            const double* th = L.theta_s + pl * a.D;
-            // All six slots first (one 16-byte LDS read each), then the six theta values they point at: two LDS round
-            // trips instead of twelve dependent ones — measured, the slot reads were 1900 of the decode's 2800 cycles.
-            const rvll_planet d = lp[k];
-            const double tk = th[max(d.k.idx, 0)], tp = th[max(d.p.idx, 0)], t1 = th[max(d.e1.idx, 0)],
-                         t2 = th[max(d.e2.idx, 0)], ta = th[max(d.anom.idx, 0)], te = th[max(d.epoch.idx, 0)];
-            const double kraw = d.k.idx >= 0 ? tk : d.k.val;
-            const double praw = d.p.idx >= 0 ? tp : d.p.val;
-            const double K = d.k_kind == RVLL_K_LOGK1 ? exp(kraw) : kraw;
-            const double Pd = d.p_kind == RVLL_P_LOGPERIOD ? exp(praw) : praw;
-            const double e1 = d.e1.idx >= 0 ? t1 : d.e1.val;
-            const double e2 = d.e2.idx >= 0 ? t2 : d.e2.val;
-            double ecc, omega;
-            if (d.ecc_kind == RVLL_ECC_SECOS_SESIN) {
-                ecc = e1 * e1 + e2 * e2;
-                omega = atan2(e2, e1);
-                if (ecc > 1) atomicOr(&L.pflags[pl], RVLL_FLAG_INVALID_ORBIT);
-            } else if (d.ecc_kind == RVLL_ECC_ECOS_ESIN) {
-                ecc = sqrt(e1 * e1 + e2 * e2);
-                omega = atan2(e2, e1);
-                if (ecc > 1) atomicOr(&L.pflags[pl], RVLL_FLAG_INVALID_ORBIT);
-            } else {
-                ecc = e1;
-                omega = e2;
+    if constexpr (!SUM) {
+        for (int wk = tid; wk < npts * a.Np; wk += NT) {
+            const int pl = wk / a.Np;
+            decode_planet(a, L, lp, pl, wk - pl * a.Np);
+        }
+    } else {
+        // The planets of a point sit in ONE wave (64 / Np points a wave, lanes left over idle; beyond 64 planets a wave takes one
+        // point, 64 planets of it a pass): the point's sum of K e cos w — what of rvmodel:463 is no quotient, a constant of the
+        // point the fp64 item reads as one number (eval_item) — is then added up in planet order by the lane of the first planet
+        // from what the wave's own lanes have just written, with no barrier of the workgroup in between.
+        const int lane_d = tid & (kWave - 1);
+        const int ppw = a.Np <= kWave ? kWave / max(a.Np, 1) : 1;                    // points a wave
+        const int nchunk = a.Np <= kWave ? 1 : (a.Np + kWave - 1) / kWave;           // passes a point
+        const int q_d = a.Np <= kWave ? lane_d / max(a.Np, 1) : 0;                   // this lane's point within its wave, its planet
+        const int k_d = lane_d - q_d * a.Np;
+        for (int g = tid >> 6, c = 0; g * ppw < npts && a.Np > 0; ) {               // (g, c: wave-uniform)
+            const int pl = g * ppw + q_d;
+            const int k = k_d + c * kWave;
+            const bool mine = q_d < ppw && pl < npts;
+            if (mine && k < a.Np) decode_planet(a, L, lp, pl, k);
+            // P[6] of the point's planets are in LDS, written by lanes of this wave (LDS operations of one wave complete in order)
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            const bool last = c == nchunk - 1;
+            if (last && mine && k_d == 0) {
+                double* P0 = L.pp + pl * a.Np * kPlanetFields;
+                double sum = P0[6];
+                for (int k2 = 1; k2 < a.Np; ++k2) sum += P0[k2 * kPlanetFields + 6];
+                P0[7] = sum;
             }
-            const double anom = d.anom.idx >= 0 ? ta : d.anom.val;
-            const double ma0 = d.anom_kind == RVLL_ANOM_ML0 ? anom - omega : anom;
-            const double ec = ecc > 0.99 ? 0.99 : ecc;                  // trueanomaly.c:11-12
-            // a planet this eccentric may hold a solve that wanders for hundreds of steps: the CU-wide form starts its tickets
-            // at the wave round the tile's most eccentric such point begins in (loglike_tile).  Key: eccentricity above the
-            // threshold (0 .. 30: ec <= 0.99) over that round, in the upper bits of the ticket word — atomicMax keeps the most
-            // eccentric; no ticket has been drawn yet (the barrier after this step comes first)
-#ifndef RVLL_AB_NO_ROT
-            if (ec >= kLongSolveEcc)
-                atomicMax(L.ticket, ((int)((ec - kLongSolveEcc) * 340.) << (kTicketBits + kTicketRoundBits)) |
-                                    (min((pl * a.Ne) >> 6, kTicketRoundMask) << kTicketBits));
-#endif
-            double so, co;
-            sincos_any(omega, so, co);                                  // (omega is a free parameter: any finite value)
-            const double q = sqrt((1. - ec) * (1. + ec));
-            double* P = L.pp + (pl * a.Np + k) * kPlanetFields;
-            P[0] = kTwoPi / Pd;
-            P[1] = d.epoch.idx >= 0 ? te : d.epoch.val;
-            P[2] = ma0;
-            P[3] = ec;
-            P[4] = K * co;
-            P[5] = K * q * so;
-            P[6] = K * (ecc * co);
-            // a bound on |M| over the epoch table: the solver's first eight steps skip the range check of their sin / cos
-            // arguments when it is below 2^48 for every planet of the tile (eval_item)
-            const double ep = d.epoch.idx >= 0 ? te : d.epoch.val;
-            const double mbound = fabs(kTwoPi / Pd) * fmax(fabs(a.tmax - ep), fabs(a.tmin - ep)) + fabs(ma0);
-            if (!(mbound < kExcursionM)) atomicOr(L.wide, 1);
-            P[7] = 0.;
+            if (last) { c = 0; g += NT / kWave; } else ++c;
         }
-        // P[6] of the point's planets are in LDS, written by lanes of this wave (LDS operations of one wave complete in order)
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const bool last = c == nchunk - 1;
-        if (last && mine && k_d == 0) {
-            double* P0 = L.pp + pl * a.Np * kPlanetFields;
-            double sum = P0[6];
-            for (int k2 = 1; k2 < a.Np; ++k2) sum += P0[k2 * kPlanetFields + 6];
-            P0[7] = sum;
-        }
-        if (last) { c = 0; g += NT / kWave; } else ++c;
     }
     for (int pl = NT - 1 - tid; pl < npts; pl += NT) {
         const double* th = L.theta_s + pl * a.D;
@@ -1099,7 +1128,7 @@ __device__ __forceinline__ __attribute__((flatten)) void loglike_tile(const Logl
         }
     }
     if constexpr (TRACE && DYN) { if (tid == 0) tr[2] = __builtin_amdgcn_s_memrealtime(); }
-    tile_decode<NT>(a, L, npts);
+    tile_decode<NT, PREC == RVLL_PREC_FP64>(a, L, npts);
     __syncthreads();
 #ifndef RVLL_AB_NO_LOGDET
     bool done_pre = false;
@@ -1231,9 +1260,14 @@ __device__ __forceinline__ __attribute__((flatten)) void loglike_tile(const Logl
                     // one.  The pooled item shows such a last-bit difference where the separate quotients happened to hide it:
                     // tests/test_gpu_solver_settings.py, 9000 epochs.  Chosen here, not inside eval_item: there it moved scalar
                     // spills of the item loop, +0.45 us on every launch — profiles/r06_item_pool.txt)
-                    if (L.anyfail[pl] || contrib[i - base] != contrib[i - base])       // a point with an itmax failure; an item left as NaN
-                        contrib[i - base] = a.itmax > kSafeSteps ? eval_item<PREC, true, EXTRAS, PREC == RVLL_PREC_FP64, NP>(a, cx, pl, i - pl * a.Ne)
-                                                                 : eval_item<PREC, true, EXTRAS, false, NP>(a, cx, pl, i - pl * a.Ne);
+                    // (reduced precision has no CR instantiation: one call, not the same item inlined twice behind a choice)
+                    if (L.anyfail[pl] || contrib[i - base] != contrib[i - base]) {     // a point with an itmax failure; an item left as NaN
+                        if constexpr (PREC == RVLL_PREC_FP64)
+                            contrib[i - base] = a.itmax > kSafeSteps ? eval_item<PREC, true, EXTRAS, true, NP>(a, cx, pl, i - pl * a.Ne)
+                                                                     : eval_item<PREC, true, EXTRAS, false, NP>(a, cx, pl, i - pl * a.Ne);
+                        else
+                            contrib[i - base] = eval_item<PREC, true, EXTRAS, false, NP>(a, cx, pl, i - pl * a.Ne);
+                    }
                 }
                 __syncthreads();
                 // a correctly rounded redo lowered a mark (eval_item, CR): the items of that point once more, until no pass does —

@@ -968,7 +968,9 @@ int rvll_region_tile_rows(int32_t ndim, int32_t* rows);
  * 22/23 sin/cos of sincos_any, 24/25 reduce_huge: r and q mod 4 (|x| >= 2^-10, finite; nan elsewhere).
  * The fp32 layer, floats cast in and widened out: 26/27 sincos_f32, 28 - 31 sincos_f32x2 on (x, y): s.x, s.y, c.x, c.y,
  * 32 reduce_2pi_to_f32, 33 div_f32(x, y), 34/35 div_f32x2 of (x, 3 x) by (y, 2 - y): .x, .y.
- * The rotation between Newton steps: 36/37 sin/cos of the pair sincos(x) after rotate_mid by y (|y| <= pi/4).   */
+ * The rotation between Newton steps: 36/37 sin/cos of the pair sincos(x) after rotate_mid by y (|y| <= pi/4).
+ * The Newton step's residuals: 38/39 f / f' of newton_residuals; x holds records (E, s, c, e, M) of five doubles, y is not
+ * read, the result stands at the record's first element (nan at the other four).   */
 int rvll_debug_eval(rvll_handle* h, int32_t op, const double* x, const double* y,
                     int64_t n, double* out);
 
