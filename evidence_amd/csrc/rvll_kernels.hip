@@ -34,6 +34,11 @@ constexpr bool kLeanKernels = false;
 #else
 constexpr bool kLeanKernels = true;
 #endif
+#ifdef RVLL_AB_NO_ASM_NEWTON           // (measurement builds only: the compiled shortcut loop throughout, as before rvll_math.h's newton_trips_asm)
+constexpr bool kAsmNewton = false;
+#else
+constexpr bool kAsmNewton = true;
+#endif
 
 // The CU-wide form: one 1024-thread workgroup per tile of a.PB points (loglike_tile, NT = 1024, DYN); FUSED as in
 // loglike_kernel
@@ -49,7 +54,7 @@ void loglike_cu_kernel(const LoglikeArgs a)
     const long long p0 = (long long)blockIdx.x * a.PB;
     const int npts = (int)min((long long)a.PB, a.B - p0);
     if (npts <= 0) return;
-    loglike_tile<PREC, FUSED, TRACE, kCuThreads, true, EXTRAS, false, NP>(a, smem, p0, npts);
+    loglike_tile<PREC, FUSED, TRACE, kCuThreads, true, EXTRAS, false, NP, kAsmNewton && PREC == RVLL_PREC_FP64>(a, smem, p0, npts);
 }
 
 // 4 workgroups of 256 per CU (4 waves/SIMD): caps the kernel at 128 VGPRs
@@ -62,7 +67,7 @@ void loglike_kernel(const LoglikeArgs a)                                // form 
     const long long p0 = (long long)blockIdx.x * a.PB;
     const int npts = (int)min((long long)a.PB, a.B - p0);
     if (npts <= 0) return;
-    loglike_tile<PREC, FUSED, false, kThreads, false, EXTRAS, false, NP>(a, smem, p0, npts);
+    loglike_tile<PREC, FUSED, false, kThreads, false, EXTRAS, false, NP, kAsmNewton && PREC == RVLL_PREC_FP64>(a, smem, p0, npts);
 }
 
 
@@ -437,6 +442,21 @@ void debug_eval_kernel(int op, const double* x, const double* y, long long n, do
         case 38: case 39: {
             r = NAN;
             if (i % 5 == 0 && i + 4 < n) { double f, fp; newton_residuals(a, x[i + 1], x[i + 2], x[i + 3], x[i + 4], f, fp); r = op == 38 ? f : fp; }
+            break; }
+        // the shortcut solve from E = M at the default tol (tests/test_gpu_newton_asm.py): x holds n / 2 records (M, e) of two doubles,
+        // lane i takes record i — 64 records a wave — and its result stands at out[i] (NaN from n / 2 on): s, c and dE as the
+        // solve leaves them, and whether it settled within kSafeSteps steps (1 / 0).  Ops 40 .. 43: the first trip compiled and
+        // the later ones hand-written (rvll_math.h, newton_trips_asm); 44 .. 47: the compiled loop throughout, same geometry
+        case 40: case 41: case 42: case 43: case 44: case 45: case 46: case 47: {
+            r = NAN;
+            if (i < n / 2) {
+                const double M = x[2 * i], ec = x[2 * i + 1], tol = 1e-4;
+                double E, dE;
+                if (op < 44) newton_shortcut<true>(E, dE, s, c, ec, M, tol, sincos_consts());
+                else         newton_shortcut<false>(E, dE, s, c, ec, M, tol, sincos_consts());
+                const int w = (op - 40) & 3;
+                r = w == 0 ? s : w == 1 ? c : w == 2 ? dE : (fabs(dE) <= tol ? 1. : 0.);
+            }
             break; }
         default: r = NAN; break;
         }

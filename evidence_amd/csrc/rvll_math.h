@@ -759,6 +759,150 @@ RVLL_HD void newton_residuals(double E, double s, double c, double ec, double M,
     fp = __builtin_fma(-ec, c, 1.0);
 }
 
+// ---- trips 1 .. kSafeSteps - 1 of the shortcut loop, hand-written --------------------------------------------------------------
+// The compiled trip (rotate_mid, newton_residuals, div_exact, the step) forms the new c, s and E in fresh registers and copies them
+// over the old ones at the bottom of every trip — the loop's phi nodes, three v_mov_b64 of 35 instructions — with two more copies
+// on the way in, one on the way out and three around the first evaluation.  They cannot be scheduled away inside ONE copy of the
+// trip: each new value of the pair needs both old values, and dE = E' - E needs the old E after the new one exists.  Two copies of
+// the trip with swapped register roles have none: half A reads the set (s, c, E)_A and writes (s, c, E)_B, half B is its mirror
+// image, and the registers of the set being written are the half's temporaries until it writes them:
+//     z = h^2 in E', t = h z in s', the cosine chain and cm1 in c', the sine chain and sh in T (the one register pair beyond the
+//     two sets and h: 8 pairs are live, as in the compiled loop); then s' = fma(s, cm1, s), c' = fma(c, cm1, c), s' = fma(c, sh, s'),
+//     c' = fma(-s, sh, c') — the old pair is dead — f' in T, v_rcp_f64 in E', f in s, the quotient's e and q in c, E' = E - q, h = E' - E.
+// Every arithmetic instruction is one of the compiled trip's with its operands in its order: the same bits.  v_rcp_f64 keeps the
+// compiled trip's distance (two VALU instructions) to the first reader of its result; nothing else in here is a hazard pair.
+// Lanes leave by EXEC, which the block narrows and restores: after each half the lanes with |h| <= tol (or NaN) drop out, and the
+// wave leaves when none is left or `steps` reaches kSafeSteps.  mB holds the lanes whose latest state is in set B; on the way
+// out their set is copied to A (three masked copies, skipped when mB is empty — E too: a loose tol reads it afterwards).
+// A step beyond pi/4 (or NaN) in an active lane wants the full pair (newton_next_sincos): the block then leaves that half BEFORE
+// it writes anything but its temporaries (the compare opens the half, its branch follows the chain, which hides the compare) and
+// returns true, and the caller goes on from `steps` in the compiled loop — the pair of step k is a function of (h, k) and the
+// old pair alone, so the bits are the same.  EXEC on entry may be partial; it is left as found.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define RVLL_NEWTON_HALF(sa, ca, ea, sb, cb, eb)                                                                          \
+    "v_cmp_nle_f64_e64 vcc, |%[h]|, %[pio4]\n\t"                                                                          \
+    "v_mul_f64 %[" eb "], %[h], %[h]\n\t"                                                                                 \
+    "v_fma_f64 %[t], %[" eb "], %[S6], %[S5]\n\t"                                                                         \
+    "v_fma_f64 %[" cb "], %[" eb "], %[C6], %[C5]\n\t"                                                                    \
+    "v_fma_f64 %[t], %[" eb "], %[t], %[S4]\n\t"                                                                          \
+    "v_fma_f64 %[" cb "], %[" eb "], %[" cb "], %[C4]\n\t"                                                                \
+    "v_fma_f64 %[t], %[" eb "], %[t], %[S3]\n\t"                                                                          \
+    "v_fma_f64 %[" cb "], %[" eb "], %[" cb "], %[C3]\n\t"                                                                \
+    "v_fma_f64 %[t], %[" eb "], %[t], %[S2]\n\t"                                                                          \
+    "v_fma_f64 %[" cb "], %[" eb "], %[" cb "], %[C2]\n\t"                                                                \
+    "v_fma_f64 %[t], %[" eb "], %[t], %[S1]\n\t"                                                                          \
+    "v_fma_f64 %[" cb "], %[" eb "], %[" cb "], %[C1]\n\t"                                                                \
+    "v_mul_f64 %[" sb "], %[h], %[" eb "]\n\t"                                                                            \
+    "v_fma_f64 %[" cb "], %[" eb "], %[" cb "], -0.5\n\t"                                                                 \
+    "v_fma_f64 %[t], %[" sb "], %[t], %[h]\n\t"                                                                           \
+    "v_mul_f64 %[" cb "], %[" eb "], %[" cb "]\n\t"                                                                       \
+    "s_cbranch_vccnz .Lrvll_nt_bail%=\n\t"                                                                                \
+    "v_fma_f64 %[" sb "], %[" sa "], %[" cb "], %[" sa "]\n\t"                                                            \
+    "v_fma_f64 %[" cb "], %[" ca "], %[" cb "], %[" ca "]\n\t"                                                            \
+    "v_fma_f64 %[" sb "], %[" ca "], %[t], %[" sb "]\n\t"                                                                 \
+    "v_fma_f64 %[" cb "], -%[" sa "], %[t], %[" cb "]\n\t"                                                                \
+    "v_fma_f64 %[t], -%[ec], %[" cb "], 1.0\n\t"                                                                          \
+    "v_rcp_f64 %[" eb "], %[t]\n\t"                                                                                       \
+    "v_fma_f64 %[" sa "], -%[ec], %[" sb "], %[" ea "]\n\t"                                                               \
+    "v_add_f64 %[" sa "], %[" sa "], -%[M]\n\t"                                                                           \
+    "v_fma_f64 %[" ca "], -%[t], %[" eb "], 1.0\n\t"                                                                      \
+    "v_fma_f64 %[" eb "], %[" eb "], %[" ca "], %[" eb "]\n\t"                                                            \
+    "v_mul_f64 %[" ca "], %[" sa "], %[" eb "]\n\t"                                                                       \
+    "v_fma_f64 %[t], -%[t], %[" ca "], %[" sa "]\n\t"                                                                     \
+    "v_fma_f64 %[" ca "], %[t], %[" eb "], %[" ca "]\n\t"                                                                 \
+    "v_add_f64 %[" eb "], %[" ea "], -%[" ca "]\n\t"                                                                      \
+    "v_add_f64 %[h], %[" eb "], -%[" ea "]\n\t"                                                                           \
+    "s_add_i32 %[n], %[n], 1\n\t"
+// the lanes still going after a half: |h| > tol; the wave leaves when there is none or the steps are used up
+#define RVLL_NEWTON_NARROW                                                                                                \
+    "v_cmp_gt_f64_e64 vcc, |%[h]|, %[tol]\n\t"                                                                            \
+    "s_and_b64 exec, exec, vcc\n\t"                                                                                       \
+    "s_cbranch_execz .Lrvll_nt_done%=\n\t"
+__device__ __forceinline__ bool newton_trips_asm(double& E, double& dE, int& steps, double& s, double& c, double ec, double M,
+                                                 double tol, const SincosConsts& k)
+{
+    double sB, cB, EB, T;
+    unsigned long long ex0, mB;
+    int bail;
+    asm("s_mov_b64 %[ex0], exec\n\t"
+        "s_mov_b64 %[mB], 0\n\t"
+        "s_mov_b32 %[bail], 0\n\t"
+        RVLL_NEWTON_NARROW
+        ".Lrvll_nt_top%=:\n\t"
+        RVLL_NEWTON_HALF("s", "c", "E", "sB", "cB", "EB")
+        "s_or_b64 %[mB], %[mB], exec\n\t"
+        RVLL_NEWTON_NARROW
+        "s_cmp_ge_i32 %[n], %[nmax]\n\t"
+        "s_cbranch_scc1 .Lrvll_nt_done%=\n\t"
+        RVLL_NEWTON_HALF("sB", "cB", "EB", "s", "c", "E")
+        "s_andn2_b64 %[mB], %[mB], exec\n\t"
+        RVLL_NEWTON_NARROW
+        "s_cmp_lt_i32 %[n], %[nmax]\n\t"
+        "s_cbranch_scc1 .Lrvll_nt_top%=\n\t"
+        "s_branch .Lrvll_nt_done%=\n\t"
+        ".Lrvll_nt_bail%=:\n\t"
+        "s_mov_b32 %[bail], 1\n\t"
+        ".Lrvll_nt_done%=:\n\t"
+        "s_mov_b64 exec, %[ex0]\n\t"
+        "s_cmp_eq_u64 %[mB], 0\n\t"
+        "s_cbranch_scc1 .Lrvll_nt_end%=\n\t"
+        "s_mov_b64 exec, %[mB]\n\t"
+        "v_mov_b64 %[s], %[sB]\n\t"
+        "v_mov_b64 %[c], %[cB]\n\t"
+        "v_mov_b64 %[E], %[EB]\n\t"
+        "s_mov_b64 exec, %[ex0]\n\t"
+        ".Lrvll_nt_end%=:"
+        : [s] "+v"(s), [c] "+v"(c), [E] "+v"(E), [h] "+v"(dE), [n] "+s"(steps), [sB] "=&v"(sB), [cB] "=&v"(cB), [EB] "=&v"(EB),
+          [t] "=&v"(T), [ex0] "=&s"(ex0), [mB] "=&s"(mB), [bail] "=&s"(bail)
+        : [ec] "v"(ec), [M] "v"(M), [tol] "s"(tol), [pio4] "s"(kRotateMidMax), [nmax] "i"(kSafeSteps),
+          [S1] "s"(k.S1), [S2] "s"(k.S2), [S3] "s"(k.S3), [S4] "s"(k.S4), [S5] "s"(k.S5), [S6] "v"(k.S6),
+          [C1] "s"(k.C1), [C2] "s"(k.C2), [C3] "s"(k.C3), [C4] "s"(k.C4), [C5] "s"(k.C5), [C6] "v"(k.C6)   // one scalar operand per VALU instruction
+        : "vcc", "scc");
+    return bail != 0;
+}
+#undef RVLL_NEWTON_HALF
+#undef RVLL_NEWTON_NARROW
+#endif
+
+// The shortcut loop of a solve from E = M: at most kSafeSteps steps on the unchecked pair, until |dE| <= tol.  ASM: the first trip
+// (the full pair at E = M) compiled, the later ones by newton_trips_asm, and the compiled loop for what is left of a solve that
+// met a step beyond pi/4; else (and on the host) the compiled loop throughout.  The same bits either way.  E and dE are results
+// only, formed from M: start values set by the caller in front of a branch around this call are three copies a solve.
+// eval_item (rvll_tile.h) calls this with ASM = true only; where it keeps the compiled loop it has the loop in its own body, as
+// before this function existed, so that those kernels' code does not move.  ASM = false is the host build's
+// (tests/native/hostshortcut.hip) and the debug-eval kernel's (ops 44 .. 47).
+template <bool ASM>
+RVLL_HD void newton_shortcut(double& E, double& dE, double& s, double& c, double ec, double M, double tol, const SincosConsts& kc)
+{
+    int steps = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+    if constexpr (ASM) {
+        sincos_f64(M, s, c, kc);
+        double f, fp;
+        newton_residuals(M, s, c, ec, M, f, fp);
+        E = M - div_exact(f, fp);
+        dE = E - M;
+        steps = 1;
+        if (__builtin_expect(!newton_trips_asm(E, dE, steps, s, c, ec, M, tol, kc), 1)) return;
+        if (!(__builtin_fabs(dE) > tol && steps < kSafeSteps)) return;
+    } else
+#endif
+    {
+        E = M;
+        dE = __builtin_inf();
+    }
+    do {
+        // from the second evaluation on the pair is rotated by the step just taken
+        newton_next_sincos<false>(E, dE, steps, s, c, kc);
+        double f, fp;
+        newton_residuals(E, s, c, ec, M, f, fp);       // the products fused into their subtractions
+        const double En = E - div_exact(f, fp);        // == f / fp, correctly rounded
+        dE = En - E;
+        E = En;
+        ++steps;
+    } while (__builtin_fabs(dE) > tol && steps < kSafeSteps);
+}
+
 // (sin r, cos r) of the reduced argument -> (sin x, cos x) by the quadrant: swap and signs with bit operations (compare +
 // v_cndmask cost ~4 cycles each, measured)
 RVLL_HD void quadrant_f32(float sr, float cr, uint32_t uq, float& s_out, float& c_out)

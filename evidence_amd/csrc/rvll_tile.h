@@ -267,6 +267,7 @@ struct ItemCtx {
     int* jfail;
     const int* wide;      // != 0: some planet of the tile has |M| beyond 2^48 (absurd period): no solve takes the shortcut
     int* pflags;          // per-point flag bits (RVLL_FLAG_WANDERED is set from the solver's second loop)
+    double S6, C6;        // the two chain constants of sincos_consts() that the sin / cos blocks take in vector registers (loglike_tile)
 };
 
 // A root of Kepler's equation lies within e < 1 of M: E - M = e sin E.  A float iterate that stops moving anywhere else has not
@@ -299,7 +300,19 @@ __device__ __forceinline__ bool f32_astray(float E, float Mf, float tolf) { retu
 // addresses fold; instantiated for the lean fp64 batch kernels at one and three planets (rvll_kernels.hip): 63.5 -> 62.6 us at
 // cfg3 on the final tree of round 4 (it measured SLOWER on the tree before the redo pass got its cold-path hints:
 // profiles/r04_isa_budget_addendum.txt).  Same operations in the same order: same bits.
-template <int PREC, bool FAILCHECK, bool EXTRAS = true, bool CR = false, int NP = 0>
+// ASMN: trips 1 .. kSafeSteps - 1 of the fp64 shortcut loop by the hand-written routine (rvll_math.h, newton_trips_asm): the first
+// pass of the fp64 batch kernels (rvll_kernels.hip).  The same instructions on the same operands: same bits (profiles/r08_newton_asm.txt).
+// (Every other instantiation's code is what it was without the parameter, byte for byte: it takes neither the routine nor the
+// function the routine is wrapped in.)
+template <bool ASMN>
+__device__ __forceinline__ SincosConsts item_consts(const ItemCtx& cx)
+{
+    SincosConsts k = sincos_consts();
+    if constexpr (ASMN) { k.S6 = cx.S6; k.C6 = cx.C6; }           // the same numbers, held in registers (loglike_tile)
+    return k;
+}
+
+template <int PREC, bool FAILCHECK, bool EXTRAS = true, bool CR = false, int NP = 0, bool ASMN = false>
 __device__ __forceinline__ double eval_item(const LoglikeArgs& a, const ItemCtx& cx, int pl, int j)
 {
     const double t  = a.t[j];
@@ -344,7 +357,7 @@ __device__ __forceinline__ double eval_item(const LoglikeArgs& a, const ItemCtx&
 #ifdef RVLL_LOCAL_CONSTS
                 const SincosConsts kc = sincos_consts_pinned();     // loaded here, live through the loop (rvll_math.h)
 #else
-                const SincosConsts kc = sincos_consts();
+                const SincosConsts kc = item_consts<ASMN>(cx);      // (sincos_consts(), rvll_math.h)
 #endif
                 // The first kSafeSteps iterations: an iterate cannot leave the range of the short sin / cos reduction
                 // (2^50, rvll_math.h) in fewer than eight steps — f' >= 0.01 and |f| <= |E - M| + e bound |E_k - M| by
@@ -352,7 +365,14 @@ __device__ __forceinline__ double eval_item(const LoglikeArgs& a, const ItemCtx&
                 // unconditionally (the flag is wave-uniform: a scalar branch).  Nearly every
                 // solve ends here (cfg3's priors: 2.9 steps on average, 0.01 % of the waves go past eight).
                 const bool shortcut = a.itmax > kSafeSteps && !wide;  // wave-uniform
-                if (shortcut) {
+                if constexpr (ASMN) {
+                    // The first trip compiled and the rest hand-written (rvll_math.h, newton_shortcut<true>): E and dE are its
+                    // results, so the start values above are read only without the shortcut, and are made to stay on that
+                    // branch: hoisted above it, as the compiler likes to, they are three copies in front of every solve.
+                    // Every other instantiation keeps the loop below as it stands, and with it its code.
+                    if (shortcut) newton_shortcut<true>(E, dE, s, c, ec, M, a.tol, kc);
+                    else          asm volatile("" : "+v"(E), "+v"(dE));
+                } else if (shortcut) {
                     int steps = 0;
                     do {
                         // from the second evaluation on the pair is rotated by the step just taken (rvll_math.h)
@@ -1081,7 +1101,8 @@ __device__ __forceinline__ void tile_write_point(const LoglikeArgs& __restrict__
 // buffer nothing else reads; no stamp executes in the product kernels.
 // PRE: the caller holds its lanes' share of the epoch table for the per-point normalisation in registers (LogdetPre; the
 // scalar-call server) — used when the tile has one point and the preload is valid, ignored otherwise
-template <int PREC, int FUSED, bool TRACE = false, int NT = kThreads, bool DYN = false, bool EXTRAS = true, bool PRE = false, int NP = 0>
+template <int PREC, int FUSED, bool TRACE = false, int NT = kThreads, bool DYN = false, bool EXTRAS = true, bool PRE = false, int NP = 0,
+          bool ASMN = false>
 __device__ __forceinline__ __attribute__((flatten)) void loglike_tile(const LoglikeArgs& __restrict__ a, double* __restrict__ smem, long long p0, int npts,
                                                                       const double* cube_rows = nullptr, const LogdetPre& pre = LogdetPre{}
 #ifdef RVLL_WALK_TRACE                 // diagnostic build of the walk only: thread 0 sums the tile's own phases into tph[0..3]
@@ -1140,7 +1161,12 @@ __device__ __forceinline__ __attribute__((flatten)) void loglike_tile(const Logl
     if constexpr (TRACE) { if (tid == 0) tr[DYN ? 3 : 1] = __builtin_amdgcn_s_memrealtime(); }
 
     // 3. items: flattened (point, epoch) pairs of this block, CH at a time
-    const ItemCtx cx{L.pp, L.ins, L.dr, L.lin, L.nfail, L.anyfail, L.jfail, L.wide, L.pflags};
+    // With the hand-written Newton trips (ASMN) the two chain constants that travel in vector registers are made opaque here, once
+    // in front of the item loop: as plain constants the register allocator re-creates them in front of every solve (two v_mov_b64
+    // and four s_mov_b32 a solve) where the compiled loop had them hoisted.  Same numbers.
+    double pS6 = sincos_consts().S6, pC6 = sincos_consts().C6;
+    if constexpr (ASMN) asm volatile("" : "+v"(pS6), "+v"(pC6));
+    const ItemCtx cx{L.pp, L.ins, L.dr, L.lin, L.nfail, L.anyfail, L.jfail, L.wide, L.pflags, pS6, pC6};
     // CU-wide form: the point with the most eccentric planet goes FIRST.  One wandering solve keeps its wave busy for
     // tens of microseconds; drawn late from the ticket counter it is the launch's tail (profiles/r02_long_solve_tail.txt:
     // 65 -> 73 .. 88 us on the one prior draw in five to ten that holds such a point).  The decode step leaves the wave
@@ -1210,7 +1236,7 @@ __device__ __forceinline__ __attribute__((flatten)) void loglike_tile(const Logl
                 if (i < cend) {
                     int pl, j;
                     item_of(r * kWave, lane, a.Ne, pl, j);
-                    contrib[i] = eval_item<PREC, false, EXTRAS, false, NP>(a, cx, pl, j);
+                    contrib[i] = eval_item<PREC, false, EXTRAS, false, NP, ASMN>(a, cx, pl, j);
                 }
             }
             if constexpr (TRACE) { if (tid == 0) tr[4] = __builtin_amdgcn_s_memrealtime(); }
@@ -1237,7 +1263,7 @@ __device__ __forceinline__ __attribute__((flatten)) void loglike_tile(const Logl
             for (int i = base + tid; i < cend; i += NT) {
                 int pl, j;
                 item_of(i - lane, lane, a.Ne, pl, j);            // i - lane = base + 64 wave + k NT: the same for the whole wave
-                contrib[i - base] = eval_item<PREC, false, EXTRAS, false, NP>(a, cx, pl, j);
+                contrib[i - base] = eval_item<PREC, false, EXTRAS, false, NP, ASMN>(a, cx, pl, j);
             }
             if constexpr (TRACE) { if (lane == 0) tr[2 + wave] = __builtin_amdgcn_s_memrealtime(); }
         }

@@ -970,7 +970,11 @@ int rvll_region_tile_rows(int32_t ndim, int32_t* rows);
  * 32 reduce_2pi_to_f32, 33 div_f32(x, y), 34/35 div_f32x2 of (x, 3 x) by (y, 2 - y): .x, .y.
  * The rotation between Newton steps: 36/37 sin/cos of the pair sincos(x) after rotate_mid by y (|y| <= pi/4).
  * The Newton step's residuals: 38/39 f / f' of newton_residuals; x holds records (E, s, c, e, M) of five doubles, y is not
- * read, the result stands at the record's first element (nan at the other four).   */
+ * read, the result stands at the record's first element (nan at the other four).
+ * The shortcut solve from E = M at tol 1e-4: x holds n / 2 records (M, e) of two doubles, y is not read, record i is lane i's and
+ * its result stands at out[i] (nan from n / 2 on): 40/41/42 s, c, dE as the solve leaves them and 43 whether it settled within
+ * eight steps (1 / 0), first trip compiled and the later ones hand-written (newton_trips_asm); 44 - 47 the same by the compiled
+ * loop throughout.   */
 int rvll_debug_eval(rvll_handle* h, int32_t op, const double* x, const double* y,
                     int64_t n, double* out);
 
