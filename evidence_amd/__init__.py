@@ -18,12 +18,13 @@ from . import insertion
 from . import merge
 from . import posterior
 from . import pointwise
+from . import sensitivity
 from . import marginals                  # the module; its entry points are marginals.marginals, marginals_arrays, credible_levels
 from .marginals import credible_levels, marginals_arrays
 from .shrinkage import logz_error, replicates
 
 __all__ = ["GpuRVModel", "EpochTable", "ModelLayout", "compile_layout", "PriorSpec", "PriorError",
            "prior_constructor", "RvllError", "RvllLibraryError", "FLAG_INVALID_ORBIT", "FLAG_NONCONVERGED",
-           "FLAG_WANDERED", "run_nested_ensemble", "shrinkage", "replicates", "logz_error", "insertion", "merge", "posterior", "pointwise", "marginals",
+           "FLAG_WANDERED", "run_nested_ensemble", "shrinkage", "replicates", "logz_error", "insertion", "merge", "posterior", "pointwise", "sensitivity", "marginals",
            "marginals_arrays", "credible_levels"]
 __version__ = "0.1.0"

@@ -34,6 +34,12 @@ PRECISIONS = {"fp64": PREC_FP64, "mixed": PREC_MIXED, "fp32": PREC_FP32}
 PRIOR_NARGS = 6
 COMM_ID_BYTES = 128
 
+(DENSITY_SKIP, DENSITY_UNIFORM, DENSITY_JEFFREYS, DENSITY_MODJEFFREYS, DENSITY_UNIFORMFREQUENCY, DENSITY_NORMAL,
+ DENSITY_LOGNORMAL, DENSITY_LOG10NORMAL, DENSITY_TRUNCRAYLEIGH, DENSITY_TRUNCUNORMAL, DENSITY_POWERLAW, DENSITY_DOUBLEPOWERLAW,
+ DENSITY_SINE, DENSITY_BINORMAL, DENSITY_ASYMNORMAL, DENSITY_ALPHA, DENSITY_BETA, DENSITY_GAMMA, DENSITY_SORTED_UNIFORM,
+ DENSITY_SORTED_LOGUNIFORM) = range(20)
+DENSITY_NARGS = 8
+
 
 # ---- structs ---------------------------------------------------------------------
 class Slot(C.Structure):
@@ -71,6 +77,15 @@ class Prior(C.Structure):
     _fields_ = [("kind", C.c_int32), ("group", C.c_int32), ("args", C.c_double * PRIOR_NARGS),
                 ("table_cdf", C.POINTER(C.c_double)), ("table_x", C.POINTER(C.c_double)),
                 ("table_n", C.c_int32), ("table_post", C.c_int32)]
+
+
+class PriorDensity(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("group", C.c_int32), ("args", C.c_double * DENSITY_NARGS)]
+
+
+class DensityTiming(C.Structure):
+    _fields_ = [("kernel_ms", C.c_double), ("total_ms", C.c_double), ("rows", C.c_int64), ("elements", C.c_int64),
+                ("launches", C.c_int32), ("threads", C.c_int32)]
 
 
 class Timing(C.Structure):
@@ -231,6 +246,8 @@ PROTOTYPES = {
                                             C.c_int32, C.c_int32, C.c_int32, C.c_uint64, _dp, _dp, _dp, _dp, _dp, _dp,
                                             C.c_int64, C.POINTER(PointwiseTiming)]),
     "rvll_pointwise_slab_rows": (C.c_int, [_ip]),
+    "rvll_prior_logpdf_batch": (C.c_int, [C.c_int32, C.POINTER(PriorDensity), C.c_int32, C.c_int32, _dp, C.c_int64, _dp,
+                                          C.POINTER(DensityTiming)]),
     "rvll_fip_replicates": (C.c_int, [C.c_int32, _dp, _dp, C.c_int64, C.POINTER(C.c_int64), C.c_int32, _dp, C.c_int32, _dp, _dp,
                                       C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, _dp, _dp, _dp, C.c_int64,
                                       C.POINTER(FipMergedTiming)]),

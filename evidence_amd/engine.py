@@ -132,7 +132,8 @@ class GpuRVModel:
         self._s_in_p, self._s_th_p = _abi.as_dp(self._s_in), _abi.as_dp(self._s_th)
         self._s_out_p, self._s_flag_p = _abi.as_dp(self._s_out), _abi.as_ip(self._s_flag)
         self.priordict = None
-        self._live_n = 0                       # rows of the resident live set (live_init)
+        self._device = int(device)             # as given: negative is the device that is current at a call
+        self._live_n = 0                     # rows of the resident live set (live_init)
         self._runs = None                      # (R, n) of the resident ensemble (live_runs_init)
         if priordict is not None:
             self.set_priors(priordict)
@@ -341,6 +342,16 @@ class GpuRVModel:
         out = _result_array(cubes.shape)
         _abi.check(self._lib.rvll_prior_batch(self._h, _abi.as_dp(cubes), cubes.shape[0], _abi.as_dp(out)))
         return out
+
+    def log_prior_batch(self, thetas):
+        """ln pi(theta) [n] of the rows of thetas [n, ndim] under the model's own priors: the density of the transform
+        prior_transform_batch applies, on the model's device (rvll_prior_logpdf_batch; priors.log_density is the numpy
+        definition).  -inf outside the support.  Needs the priors (priordict=)."""
+        if self.priordict is None:
+            raise _abi.RvllError(_abi.E_NOPRIORS, "log_prior_batch needs the priors (priordict=)")
+        from .sensitivity import log_prior_sets
+        thetas = self._theta2d(thetas)
+        return log_prior_sets([[self.priordict[name] for name in self.parnames]], thetas, device=self._device)[:, 0]
 
     def prior_transform(self, cube):
         cube = np.asarray(cube, dtype=np.float64)

@@ -72,7 +72,8 @@ extern "C" {
                                        rvll_marginal_replicates (rvll_marginal_timing),
                                        rvll_region_draw_runs, rvll_region_tile_rows,
                                        rvll_draw_replicates (rvll_draw_timing), rvll_kep_rv_bands,
-                                       rvll_pointwise_replicates (rvll_pointwise_timing), rvll_pointwise_slab_rows */
+                                       rvll_pointwise_replicates (rvll_pointwise_timing), rvll_pointwise_slab_rows,
+                                       rvll_prior_logpdf_batch (rvll_prior_density, rvll_density_timing) */
 
 /* ---- error codes ------------------------------------------------------ */
 #define RVLL_OK             0
@@ -806,6 +807,79 @@ int rvll_pointwise_replicates(int32_t device, const double* logl /*[n_rows]*/, c
                               double* loo /*[nsamples * n_units]*/, double* mean /*[nsamples * n_units]*/,
                               double* var /*[nsamples * n_units]*/, int64_t block_bytes, rvll_pointwise_timing* timing);
 int rvll_pointwise_slab_rows(int32_t* rows);
+
+/* ---- prior densities (post-processing; independent of any model handle) ------------------------------------------- */
+/* The log density of the transform rvll_prior_batch applies, per kind (csrc/rvll_prior_density.h; evidence_amd/priors.py,
+ * log_density, is the numpy definition): -inf outside the support, NaN for a NaN argument.  A descriptor is apart
+ * from rvll_prior, whose table kinds do not carry their shape parameters.  Arguments and supports:
+ *     SKIP               -                                    contributes 0 whatever theta is
+ *     UNIFORM            xmin, xmax                           [xmin, xmax]
+ *     JEFFREYS           xmin, xmax                           [xmin, xmax]
+ *     MODJEFFREYS        x0, xmax                             [0, xmax]
+ *     UNIFORMFREQUENCY   xmin, xmax                           [xmin, xmax]
+ *     NORMAL             loc, scale                           real line
+ *     LOGNORMAL          s, loc, scale                        x > loc
+ *     LOG10NORMAL        mu, sigma                            x > 0
+ *     TRUNCRAYLEIGH      sigma, xmax                          [0, xmax)
+ *     TRUNCUNORMAL       mu, sigma, xmin, xmax, ln dPhi       [xmin, xmax);  dPhi = Phi((xmax-mu)/sigma) - Phi((xmin-mu)/sigma)
+ *     POWERLAW           alpha, xmin, xmax, ln A              [xmin, xmax);  A = (1+alpha) / (xmax^(1+alpha) - xmin^(1+alpha))
+ *     DOUBLEPOWERLAW     alpha, beta, x0, xmin, xmax, ln A    [xmin, xmax);  A as priors.py:295-297
+ *     SINE               lo, hi, ln A                         [lo, hi] = [max(xmin, 0), min(xmax, 180)];  A as priors.py:336
+ *     BINORMAL           mu1, sigma1, mu2, sigma2, A          real line
+ *     ASYMNORMAL         mu, sigma1, sigma2                   real line
+ *     ALPHA              a, Phi(a)                            x > 0
+ *     BETA               a, b, ln B(a, b)                     (0, 1)
+ *     GAMMA              alpha, beta, ln Gamma(alpha)         x > 0
+ *     SORTED_UNIFORM     a, b                                 a <= x_1 <= ... <= x_n <= b over the members of the group
+ *     SORTED_LOGUNIFORM  a, b                                 the same; 0 < a
+ * The members of a sorted group are the descriptors of one set with the same `group` (>= 0; they must be of one kind), in
+ * rising parameter order; the bounds are those of the last member and the joint density, ln n! - n ln(b - a) or ln n! - n ln
+ * ln(b / a) - sum ln x_i, is credited once, -inf when the order is broken.                                              */
+enum {
+    RVLL_DENSITY_SKIP = 0,
+    RVLL_DENSITY_UNIFORM = 1,
+    RVLL_DENSITY_JEFFREYS = 2,
+    RVLL_DENSITY_MODJEFFREYS = 3,
+    RVLL_DENSITY_UNIFORMFREQUENCY = 4,
+    RVLL_DENSITY_NORMAL = 5,
+    RVLL_DENSITY_LOGNORMAL = 6,
+    RVLL_DENSITY_LOG10NORMAL = 7,
+    RVLL_DENSITY_TRUNCRAYLEIGH = 8,
+    RVLL_DENSITY_TRUNCUNORMAL = 9,
+    RVLL_DENSITY_POWERLAW = 10,
+    RVLL_DENSITY_DOUBLEPOWERLAW = 11,
+    RVLL_DENSITY_SINE = 12,
+    RVLL_DENSITY_BINORMAL = 13,
+    RVLL_DENSITY_ASYMNORMAL = 14,
+    RVLL_DENSITY_ALPHA = 15,
+    RVLL_DENSITY_BETA = 16,
+    RVLL_DENSITY_GAMMA = 17,
+    RVLL_DENSITY_SORTED_UNIFORM = 18,
+    RVLL_DENSITY_SORTED_LOGUNIFORM = 19,
+    RVLL_DENSITY__COUNT
+};
+#define RVLL_DENSITY_NARGS 8
+typedef struct rvll_prior_density {
+    int32_t kind;              /* RVLL_DENSITY_*                                                                              */
+    int32_t group;             /* sorted kinds: the group's id (>= 0); ignored by the others                                 */
+    double  args[RVLL_DENSITY_NARGS];
+} rvll_prior_density;
+typedef struct rvll_density_timing {
+    double  kernel_ms;       /* HIP events around the kernels                                                               */
+    double  total_ms;        /* the whole call: checks, allocations, copies, kernels                                        */
+    int64_t rows;            /* B                                                                                           */
+    int64_t elements;        /* densities evaluated: B * n_sets * ndim                                                      */
+    int32_t launches;        /* one a chunk of rows                                                                         */
+    int32_t threads;         /* per workgroup                                                                               */
+} rvll_density_timing;
+/* out[b * n_sets + a] = the sum over d of the log density of sets[a * ndim + d] at theta[b * ndim + d], added in rising d.  A
+ * value depends on its row and its set alone: the same bits in any batching.  Stateless; a negative device is the current
+ * one.  RVLL_E_INVALID for null buffers, B outside [1, 2^30), ndim outside [1, 64], n_sets outside [1, 4096], an unknown
+ * kind, arguments the factories of evidence_amd/priors.py refuse, and a sorted group of mixed kinds.  The rows go to the
+ * device in chunks whose theta and out stay within 256 MiB.                                                                */
+int rvll_prior_logpdf_batch(int32_t device, const rvll_prior_density* sets /*[n_sets * ndim]*/, int32_t n_sets, int32_t ndim,
+                            const double* theta /*[B * ndim]*/, int64_t B, double* out /*[B * n_sets]*/,
+                            rvll_density_timing* timing);
 
 /* ---- FIP periodogram of the merged run's replicates (post-processing; independent of any model handle) ----------- */
 /* Per replicate s of rvll_merge_replicates (same seeds, multiplicities and merged order) the true inclusion probability of
