@@ -199,6 +199,9 @@ constexpr int    kSafeSteps = 8;                        // a Newton iterate cann
 constexpr double kExcursionM = 281474976710656.0;       // 2^48
 constexpr double kLongSolveEcc = 0.9;                   // a planet at or above it may hold a wandering solve: its point goes first
 constexpr int    kF32Steps = 16;                        // reduced-precision modes: a solve not settled by then is done in double
+// ... and below this tol every solve is: a float step smaller than half an ulp of E (2^-22 where |E| reaches pi) rounds to 0 and
+// passes any stop test, at an iterate a float ulp from the root and not within tol of it (tests/test_gpu_reduced_shapes.py)
+constexpr double kF32MinTol = 2.384185791015625e-07;    // 2^-22
 
 // |x| in [2^50, inf), finite (any |x| >= 2^-10 works): r in [-pi/4, pi/4] and the quadrant q (mod 4) with |x| = q pi/2 + r (mod 2 pi)
 RVLL_HD void reduce_huge(double x, double& r, uint32_t& q)

@@ -510,7 +510,8 @@ __device__ __forceinline__ double eval_item(const LoglikeArgs& a, const ItemCtx&
                     E = En;
                     ++steps;
                 } while (!(fabsf(dE) <= tolf) && steps < a.itmax && steps < kF32Steps);     // (NaN-safe: a non-finite step is "not settled")
-                if ((!(fabsf(dE) <= tolf) || f32_astray(E, Mf, tolf)) && steps < a.itmax) {
+                // (a tol below what a float step can show — kF32MinTol, rvll_math.h — is met by no float solve: wave-uniform)
+                if (((!(fabsf(dE) <= tolf) || f32_astray(E, Mf, tolf)) && steps < a.itmax) || a.tol < kF32MinTol) {
                     // not settled after kF32Steps, or "settled" where no root can be (f32_astray): at the eccentricity clamp
                     // the iteration wanders far outside what a float (or its one-step reduction) can follow — such a solve
                     // is done in double from the start, as the parity mode does it (rare: cfg3's priors, 0.01 % of the waves)
@@ -684,7 +685,10 @@ __device__ __forceinline__ void eval_item_pair(const LoglikeArgs& a, const ItemC
         if (__builtin_expect(more, 0)) { do newton(); while (more && steps < kF32Steps); }
         // (every test NaN-safe: a non-finite step counts as moving, and the item is solved in double)
         const bool lateA = !(fabsf(dE8.x) <= tolf.x), lateB = !(fabsf(dE8.y) <= tolf.y);      // more than kSafeSteps steps: WANDERED
-        const bool movA = !(fabsf(dE.x) <= tolf.x) || f32_astray(E.x, Mf.x, tolf.x), movB = !(fabsf(dE.y) <= tolf.y) || f32_astray(E.y, Mf.y, tolf.y);
+        // (and every item where tol is below what a float step can show: kF32MinTol, rvll_math.h — a step that rounds to 0 is no
+        // evidence of it)
+        const bool fine = a.tol < kF32MinTol;
+        const bool movA = !(fabsf(dE.x) <= tolf.x) || f32_astray(E.x, Mf.x, tolf.x) || fine, movB = !(fabsf(dE.y) <= tolf.y) || f32_astray(E.y, Mf.y, tolf.y) || fine;
         // the model term of both from the packed iterate: (s, c) are at the iterate before the last step, and that step is within
         // tol for every item that goes on from here — rotated by it (h^3 / 6 <= 2e-10 dropped) instead of a third reduction
         if (a.tol <= 1e-3) {
