@@ -10,7 +10,9 @@ test_gpu_posterior.py).  lpd and loo are logarithms of ratios of two such sums: 
 exp and log.  With z = t - a and, from the definition's weights, S1 = sum p |z| / P, M1 = sum p z / P, M2 = sum p z^2 / P:
     |lpd err| <= 2.5e-10          |loo err| <= 2.5e-10
     |mean err| <= 1e-10 S1        |var err| <= 2e-10 (M2 + 2 |M1| S1)
-None of them comes from a measurement; the largest ratios to the bounds are printed."""
+None of them comes from a measurement; the largest ratios to the bounds are printed.  The comparison itself is
+tests/pointwise_cases.py's compare (through check), shared with tests/test_gpu_pointwise_tiles.py, which takes the product across
+every tile, slab and block edge."""
 import ctypes as C
 
 import numpy as np
@@ -18,52 +20,12 @@ import pytest
 
 from evidence_amd import _abi, merge, pointwise, run_nested_ensemble
 from evidence_amd.callbacks import wrapped_params
+from pointwise_cases import KEYS, check as _check
 from test_gpu_merge import _51peg
 from test_merge_host import _arrays, _ragged, _synthetic
 from test_pointwise_host import _table
 
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(900)]
-
-KEYS = ("lpd", "loo", "mean", "var")
-
-
-def _sizes(table, logl, birth, run_start, shifts, nrep, **kw):
-    """S1, |M1| and M2 [nrep, U] from the definition's weights."""
-    logwt = merge.replicates_arrays(logl, birth, run_start, nrep, return_logwt=True, **kw)[2]
-    z = table[merge.merge_arrays(logl, birth, run_start)["order"]] - shifts[2]
-    with np.errstate(invalid="ignore"):
-        p = np.exp(logwt)
-    p = p / p.sum(axis=1, keepdims=True)
-    return p @ np.abs(z), np.abs(p @ z), p @ (z * z)
-
-
-def _check(dev, table, logl, birth, run_start, nrep, unit_block=None, **kw):
-    """The first nrep replicates of the device result `dev` against the definition (in blocks of unit_block units: the same
-    bits in less memory), within the bounds of the module docstring."""
-    ref = pointwise.pointwise_arrays(table, logl, birth, run_start, nsamples=nrep, unit_block=unit_block, **kw)
-    assert np.array_equal(ref["shifts"], dev["shifts"]) and np.array_equal(ref["truncated_rows"], dev["truncated_rows"])
-    assert np.array_equal(ref["loo_ess"], dev["loo_ess"])
-    s1, m1, m2 = _sizes(table, logl, birth, run_start, ref["shifts"], nrep, **kw)
-    bound = dict(lpd=np.full_like(s1, 2.5e-10), loo=np.full_like(s1, 2.5e-10), mean=1e-10 * s1, var=2e-10 * (m2 + 2.0 * m1 * s1))
-    empty = np.isneginf(ref["logz"])
-    assert np.array_equal(np.isneginf(dev["logz"][:nrep]), empty)
-    live = ~empty
-    close = np.abs(dev["logz"][:nrep][live] - ref["logz"][live]) <= 1e-12 * np.maximum(1.0, np.abs(ref["logz"][live]))
-    assert np.all(close)
-    worst = {}
-    for key in KEYS:
-        got = dev[key][:nrep]
-        assert got.shape == ref[key].shape
-        assert np.all(np.isnan(got[empty])) and np.all(np.isnan(ref[key][empty]))
-        err = np.abs(got[live] - ref[key][live])
-        with np.errstate(invalid="ignore", divide="ignore"):
-            ratio = np.where(err > 0, err / bound[key][live], 0.0)
-        worst[key] = float(ratio.max()) if ratio.size else 0.0
-    print("largest error over its bound:", worst)
-    for key in KEYS:
-        assert worst[key] <= 1.0, (key, worst[key])
-    assert np.array_equal(dev["waic"], dev["lpd"] - dev["var"], equal_nan=True)
-    return bound, ref
 
 
 @pytest.mark.parametrize("bootstrap", [False, True])
