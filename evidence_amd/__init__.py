@@ -19,6 +19,7 @@ from . import merge
 from . import posterior
 from . import pointwise
 from . import sensitivity
+from . import correlated
 from . import marginals                  # the module; its entry points are marginals.marginals, marginals_arrays, credible_levels
 from .marginals import credible_levels, marginals_arrays
 from .shrinkage import logz_error, replicates
@@ -26,5 +27,5 @@ from .shrinkage import logz_error, replicates
 __all__ = ["GpuRVModel", "EpochTable", "ModelLayout", "compile_layout", "PriorSpec", "PriorError",
            "prior_constructor", "RvllError", "RvllLibraryError", "FLAG_INVALID_ORBIT", "FLAG_NONCONVERGED",
            "FLAG_WANDERED", "run_nested_ensemble", "shrinkage", "replicates", "logz_error", "insertion", "merge", "posterior", "pointwise", "sensitivity", "marginals",
-           "marginals_arrays", "credible_levels"]
+           "marginals_arrays", "credible_levels", "correlated"]
 __version__ = "0.1.0"

@@ -19,7 +19,10 @@ ERROR_NAMES = {
 FLAG_INVALID_ORBIT = 1
 FLAG_NONCONVERGED = 2
 FLAG_WANDERED = 4                  # a Kepler solve took > 8 Newton steps: log-L there is conditioned to ~1e-9 (rvll.h)
+FLAG_NOISE_INVALID = 8             # rvll_celerite_loglike_batch: the noise parameters give no positive definite covariance
 ABI_VERSION = (0, 8)               # RVLL_VERSION_MAJOR / MINOR these bindings were written against
+NOISE_REAL, NOISE_SHO, NOISE_ROTATION = 0, 1, 2
+NOISE_MAX_TERMS, NOISE_MAX_RANK = 4, 4
 
 K_K1, K_LOGK1 = 0, 1
 P_PERIOD, P_LOGPERIOD = 0, 1
@@ -81,6 +84,10 @@ class Prior(C.Structure):
 
 class PriorDensity(C.Structure):
     _fields_ = [("kind", C.c_int32), ("group", C.c_int32), ("args", C.c_double * DENSITY_NARGS)]
+
+
+class NoiseTerm(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("par", Slot * 5)]
 
 
 class DensityTiming(C.Structure):
@@ -263,6 +270,8 @@ PROTOTYPES = {
     "rvll_residuals_batch": (C.c_int, [Handle, _dp, C.c_int64, C.c_uint32, _dp, _dp]),
     "rvll_gls_bands": (C.c_int, [Handle, _dp, C.c_int64, C.c_int32, C.c_uint32, C.c_double, C.c_double, C.c_int32, _dp, C.c_int32,
                                  _dp, _dp, _ip, _ip, _dp, _dp, C.c_int64, _dp]),
+    "rvll_celerite_loglike_batch": (C.c_int, [Handle, _dp, C.c_int64, C.c_int32, C.POINTER(NoiseTerm), C.c_int32, _ip, _dp, _dp,
+                                              _ip, _dp]),
     "rvll_region_draw_runs": (C.c_int, [Handle, _dp, C.POINTER(C.c_int64), C.c_int64, _dp, _dp, _dp, C.POINTER(C.c_uint64), _ip,
                                         C.c_int32, C.c_int64, C.c_int64, C.c_int32, _dp, _dp, _dp, _ip, C.POINTER(C.c_int64),
                                         C.c_int64, _dp, _ip, _ip, _dp, C.POINTER(C.c_int64), _ip]),

@@ -1,0 +1,291 @@
+"""Correlated noise: the log-likelihood of the RV residuals under a celerite covariance.
+
+The likelihood of GpuRVModel is white: a sum over independent epochs with variance svrad² (+ jitter²).  Here the covariance is
+Sigma = diag(var) + K with K[n, m] = sum over terms of k(|t_n - t_m|), `var` what the white likelihood uses, and k one of the
+celerite family (Foreman-Mackey, Agol, Ambikasaran & Angus 2017), whose semiseparable structure lets the Cholesky factor of
+Sigma be found in O(Ne J²) per parameter vector, J the number of columns:
+
+    kind        parameters (under a prefix gp<digits>)       k(x)
+    "real"      _sigma, _tau                                 sigma² exp(-x / tau)                               1 column
+    "sho"       _sigma, _rho, _q                             celerite2's SHOTerm: w0 = 2 pi / rho, S0 = sigma² / (w0 q)    2 columns
+    "rotation"  _sigma, _prot, _q0, _dq, _mix                celerite2's RotationTerm: two SHOs at prot and prot / 2        4 columns
+
+Every parameter is a free parameter of the model (a name in its parnames, with a prior like any other) or a constant in its
+fixedpardict; fixed wins, as in layout.compile_layout.  At most 4 terms and 4 columns in all.
+
+A column is (a, b, c, d, form) with k(x) = exp(-c x)(a cos d x + b sin d x); form 0 is a real column (b = d = 0), forms 1 and 2
+are the cosine and sine halves of one complex term, which share (a, b, c, d) and count once in K.  An SHO with q >= 1/2 is one
+complex term, below 1/2 two real columns; |q - 1/2| is taken as at least 1e-6 on the side q lies on.
+
+This module holds the definitions in numpy — kernel_matrix, log_likelihood_dense (the definition: a dense Cholesky) and
+log_likelihood_recursive (the algorithm of csrc/rvll_celerite.h) — and CorrelatedNoiseModel, which evaluates batches on the
+GPU (rvll_celerite_loglike_batch).  Parameters that give no valid covariance have log-L = -1e30, the reference's sentinel
+(rvmodel:203), and FLAG_NOISE_INVALID.
+"""
+import math
+import re
+from typing import Dict, List, Sequence, Tuple
+
+import numpy as np
+
+from . import _abi
+
+KINDS = {"real": (_abi.NOISE_REAL, ("sigma", "tau")),
+         "sho": (_abi.NOISE_SHO, ("sigma", "rho", "q")),
+         "rotation": (_abi.NOISE_ROTATION, ("sigma", "prot", "q0", "dq", "mix"))}
+RANK = {"real": 1, "sho": 2, "rotation": 4}
+Q_CLAMP = 1.0e-6
+INVALID_LOGL = -1.0e30
+FORM_REAL, FORM_COS, FORM_SIN = 0, 1, 2
+_PREFIX = re.compile(r"gp[0-9]+\Z")
+_TWO_PI = 2.0 * np.pi
+
+
+# ---- names -> slots ----------------------------------------------------------------------------------------------------------
+def resolve_terms(terms: Sequence[Tuple[str, str]], parnames: Sequence[str], fixedpardict: Dict[str, float]):
+    """[(kind, prefix)] -> [(kind, prefix, [(index, value)] per parameter)]: index >= 0 is a position in sorted(parnames), index
+    -1 a constant.  KeyError for a name that is neither free nor fixed, ValueError for an unknown kind, a prefix that is not
+    gp<digits>, more than 4 terms or more than 4 columns."""
+    names = sorted(parnames)
+    index = {n: i for i, n in enumerate(names)}
+    out, rank = [], 0
+    for kind, prefix in terms:
+        if kind not in KINDS:
+            raise ValueError(f"unknown noise term kind {kind!r}: one of {sorted(KINDS)}")
+        if not isinstance(prefix, str) or not _PREFIX.match(prefix):
+            raise ValueError(f"noise term prefix {prefix!r} is not of the form gp<digits>")
+        slots = []
+        for suffix in KINDS[kind][1]:
+            name = f"{prefix}_{suffix}"
+            if name in fixedpardict:                # fixed overrides free (layout.compile_layout; rvmodel:178)
+                slots.append((-1, float(fixedpardict[name])))
+            elif name in index:
+                slots.append((index[name], 0.0))
+            else:
+                raise KeyError(name)
+        rank += RANK[kind]
+        out.append((kind, prefix, slots))
+    if not 1 <= len(out) <= _abi.NOISE_MAX_TERMS:
+        raise ValueError(f"1 to {_abi.NOISE_MAX_TERMS} noise terms, got {len(out)}")
+    if rank > _abi.NOISE_MAX_RANK:
+        raise ValueError(f"the terms have {rank} columns, at most {_abi.NOISE_MAX_RANK}")
+    return out
+
+
+# ---- parameters -> columns (csrc/rvll_celerite.h: cel_column, cel_sho_column; the same operations in the same order) ------------
+def _finite(*v):
+    return all(math.isfinite(x) for x in v)
+
+
+def _sho_columns(amp, w0, q):
+    """An SHO at w0 with quality q and variance amp = S0 w0 q."""
+    if q >= 0.5:
+        qc = 0.5 + Q_CLAMP if q - 0.5 < Q_CLAMP else q
+        f = math.sqrt((2.0 * qc - 1.0) * (2.0 * qc + 1.0))
+        a = amp
+        b = a / f
+        c = w0 / (2.0 * qc)
+        d = c * f
+        return [(a, b, c, d, FORM_COS), (a, b, c, d, FORM_SIN)]
+    qc = 0.5 - Q_CLAMP if 0.5 - q < Q_CLAMP else q
+    f = math.sqrt((1.0 - 2.0 * qc) * (1.0 + 2.0 * qc))
+    h, g = 0.5 * amp, w0 / (2.0 * qc)
+    return [(h * (1.0 + 1.0 / f), 0.0, g * (1.0 - f), 0.0, FORM_REAL), (h * (1.0 - 1.0 / f), 0.0, g * (1.0 + f), 0.0, FORM_REAL)]
+
+
+def term_columns(kind: str, params: Sequence[float]):
+    """The columns [(a, b, c, d, form)] of one term, or None where its parameters are not valid: not finite, sigma < 0, mix < 0,
+    tau, rho, q, prot, q0 + 1/2 or dq not > 0."""
+    p = [float(x) for x in params]
+    if not _finite(*p):
+        return None
+    if kind == "real":
+        sigma, tau = p
+        if not (sigma >= 0.0 and tau > 0.0):
+            return None
+        return [(sigma * sigma, 0.0, 1.0 / tau, 0.0, FORM_REAL)]
+    if kind == "sho":
+        sigma, rho, q = p
+        if not (sigma >= 0.0 and rho > 0.0 and q > 0.0):
+            return None
+        w0 = _TWO_PI / rho
+        return _sho_columns(sigma * sigma, w0, q)                   # S0 w0 q = sigma²
+    if kind == "rotation":
+        sigma, prot, q0, dq, mix = p
+        if not (sigma >= 0.0 and prot > 0.0 and q0 + 0.5 > 0.0 and dq > 0.0 and mix >= 0.0):
+            return None
+        amp = sigma * sigma / (1.0 + mix)
+        cols = []
+        for second in (False, True):
+            q = 0.5 + q0 if second else 0.5 + q0 + dq
+            under = (2.0 * q - 1.0) * (2.0 * q + 1.0)
+            if not under > 0.0:                   # an oscillator at or below 1/2 (q0 <= 0): NaN columns, no valid covariance
+                cols += [(math.nan,) * 4 + (FORM_COS,), (math.nan,) * 4 + (FORM_SIN,)]
+                continue
+            w = (2.0 if second else 1.0) * (2.0 * _TWO_PI) * q / (prot * math.sqrt(under))
+            cols += _sho_columns(mix * amp if second else amp, w, q)       # S w q of either oscillator
+        return cols
+    raise ValueError(f"unknown noise term kind {kind!r}")
+
+
+def _as_columns(columns):
+    cols = np.asarray(columns, dtype=np.float64).reshape(-1, 5)
+    if cols.shape[0] > _abi.NOISE_MAX_RANK:
+        raise ValueError(f"{cols.shape[0]} columns, at most {_abi.NOISE_MAX_RANK}")
+    return cols
+
+
+# ---- the definition ----------------------------------------------------------------------------------------------------------------
+def kernel_matrix(t, columns):
+    """The dense K [Ne, Ne] of the columns at times t: K[n, m] = sum exp(-c x)(a cos d x + b sin d x), x = |t_n - t_m|, over the
+    real columns and the cosine halves (a complex term counts once)."""
+    t = np.asarray(t, dtype=np.float64)
+    x = np.abs(t[:, None] - t[None, :])
+    K = np.zeros_like(x)
+    for a, b, c, d, form in _as_columns(columns):
+        if int(form) != FORM_SIN:
+            K += np.exp(-c * x) * (a * np.cos(d * x) + b * np.sin(d * x))
+    return K
+
+
+def log_likelihood_dense(res, var, t, columns):
+    """The definition: -1/2 z^T z - sum ln L_ii - Ne / 2 ln(2 pi) with L the Cholesky factor of diag(var) + K and L z = res.
+    INVALID_LOGL where columns is None or the matrix is not positive definite; an O(Ne³) reference, not a product path."""
+    res, var = np.asarray(res, dtype=np.float64), np.asarray(var, dtype=np.float64)
+    if columns is None or not np.isfinite(res).all():
+        return INVALID_LOGL
+    cols = _as_columns(columns)
+    if not np.isfinite(cols).all():
+        return INVALID_LOGL
+    try:
+        L = np.linalg.cholesky(np.diag(var) + kernel_matrix(t, cols))
+    except np.linalg.LinAlgError:
+        return INVALID_LOGL
+    z = np.linalg.solve(L, res)
+    return float(-0.5 * (z @ z) - np.log(np.diag(L)).sum() - 0.5 * res.shape[0] * math.log(_TWO_PI))
+
+
+def log_likelihood_recursive(res, var, t, columns):
+    """The same number by the recursion of csrc/rvll_celerite.h: the epochs in stable time order, t from the first of them
+    (exact ties are legal), and per epoch S <- P P^T o (S + D W W^T), f <- P o (f + W z) with P = exp(-c dt), D = A - U S U^T,
+    W = (V - S U) / D, z = r - U f; log-L = -1/2 sum z² / D - 1/2 sum ln D - Ne / 2 ln(2 pi).  INVALID_LOGL where a D is not > 0."""
+    res, var, t = (np.asarray(v, dtype=np.float64) for v in (res, var, t))
+    if columns is None or not np.isfinite(res).all():
+        return INVALID_LOGL
+    cols = _as_columns(columns)
+    J = cols.shape[0]
+    a, b, c, d = cols[:, 0], cols[:, 1], cols[:, 2], cols[:, 3]
+    form = cols[:, 4].astype(int)
+    suma = a[form != FORM_SIN].sum()
+    order = np.argsort(t, kind="stable")
+    ts = t[order] - t[order[0]]
+    S, f, W = np.zeros((J, J)), np.zeros(J), np.zeros(J)
+    D = z = chi = lndet = 0.0
+    with np.errstate(all="ignore"):
+        for n, e in enumerate(order):
+            if n > 0:
+                P = np.exp(-c * (ts[n] - ts[n - 1]))
+                S = np.outer(P, P) * (S + D * np.outer(W, W))
+                f = P * (f + W * z)
+            cs, sn = np.cos(d * ts[n]), np.sin(d * ts[n])
+            U = np.where(form == FORM_SIN, a * sn - b * cs, np.where(form == FORM_COS, a * cs + b * sn, a))
+            V = np.where(form == FORM_SIN, sn, np.where(form == FORM_COS, cs, 1.0))
+            SU = S @ U
+            D = (var[e] + suma) - U @ SU
+            if not D > 0.0:
+                return INVALID_LOGL
+            W = (V - SU) / D
+            z = res[e] - U @ f
+            chi += z * z / D
+            lndet += math.log(D)
+    return float(-0.5 * chi - 0.5 * lndet - 0.5 * res.shape[0] * math.log(_TWO_PI))
+
+
+# ---- the GPU path ---------------------------------------------------------------------------------------------------------------------
+class CorrelatedNoiseModel:
+    """A GpuRVModel's likelihood with celerite noise terms added to its covariance, evaluated on the model's GPU.
+
+    model   a GpuRVModel (precision "fp64") whose parnames / fixedpardict hold the terms' parameters: compile_layout ignores
+            names it does not know, so the model itself is unchanged by them and its priordict covers them like any other name
+    terms   [(kind, prefix)], e.g. [("sho", "gp1")] for gp1_sigma, gp1_rho, gp1_q
+
+    parnames, ndim, log_likelihood(_batch), prior_transform(_batch) and prior_loglike_batch make it a drop-in for the model in
+    callbacks.make_ultranest_callbacks(gp, vectorized=True), callbacks.make_polychord_callbacks(gp) and as
+    run_nested_slice(gp.prior_transform_batch, gp.log_likelihood_batch, gp.ndim, prior_loglike=gp.prior_loglike_batch, ...) or
+    run_nested_ensemble in the same way; the results go through merge, posterior, marginals, fip and sensitivity as they are.
+
+    Not offered: the device walks, the resident live sets, region_runs and the scalar server (low_latency=True) evaluate the
+    white likelihood inside their kernels; do not pass the model's walker / live / region callables along with this likelihood.
+    """
+
+    def __init__(self, model, terms):
+        self.model = model
+        self.parnames = list(model.parnames)
+        self.fixedpardict, self.datadict, self.nplanets, self.table = model.fixedpardict, model.datadict, model.nplanets, model.table
+        self.terms = resolve_terms(terms, self.parnames, model.fixedpardict)
+        self.rank = sum(RANK[kind] for kind, _, _ in self.terms)
+        self.order = np.ascontiguousarray(np.argsort(model.table.time, kind="stable"), dtype=np.int32)
+        self._terms_c = (_abi.NoiseTerm * len(self.terms))()
+        for i, (kind, _, slots) in enumerate(self.terms):
+            self._terms_c[i].kind = KINDS[kind][0]
+            for q, (idx, val) in enumerate(slots):
+                self._terms_c[i].par[q] = _abi.Slot.free(idx) if idx >= 0 else _abi.Slot.fixed(val)
+            for q in range(len(slots), 5):
+                self._terms_c[i].par[q] = _abi.Slot.fixed(0.0)
+
+    @property
+    def ndim(self):
+        return len(self.parnames)
+
+    def _call(self, X, from_cube, timing=None):
+        X = self.model._theta2d(X)
+        n = X.shape[0]
+        out, flags = np.empty(n, dtype=np.float64), np.zeros(n, dtype=np.int32)
+        theta = np.empty((n, self.ndim)) if from_cube else None
+        ms = np.zeros(2)
+        _abi.check(self.model._lib.rvll_celerite_loglike_batch(
+            self.model._h, _abi.as_dp(X), n, int(from_cube), self._terms_c, len(self.terms), _abi.as_ip(self.order),
+            _abi.as_dp(theta) if from_cube else None, _abi.as_dp(out), _abi.as_ip(flags), _abi.as_dp(ms)))
+        if timing is not None:
+            timing.update(residuals_ms=float(ms[0]), solve_ms=float(ms[1]))
+        return theta, out, flags
+
+    def log_likelihood_batch(self, X, return_flags=False, timing=None):
+        """log-L of every row of X [n, ndim] -> float64 [n]; with return_flags also int32 [n] (FLAG_INVALID_ORBIT alone for an
+        invalid orbit, FLAG_NOISE_INVALID for noise parameters without a valid covariance; log-L is -1e30 for both).  timing: a
+        dict that receives residuals_ms and solve_ms."""
+        _, out, flags = self._call(X, False, timing)
+        return (out, flags) if return_flags else out
+
+    def log_likelihood(self, x):
+        x = np.asarray(x, dtype=np.float64)
+        if x.size != self.ndim:
+            raise ValueError(f"expected {self.ndim} parameters, got {x.size}")
+        return float(self.log_likelihood_batch(x.reshape(1, -1))[0])
+
+    def prior_transform_batch(self, cubes):
+        return self.model.prior_transform_batch(cubes)
+
+    def prior_transform(self, cube):
+        return self.model.prior_transform(cube)
+
+    def prior_loglike_batch(self, cubes, return_flags=False, timing=None):
+        """prior(cubes) -> theta -> log-L in one call, theta staying on the device in between: (theta, logl), the bits of
+        prior_transform_batch and of log_likelihood_batch on its result."""
+        theta, out, flags = self._call(cubes, True, timing)
+        return (theta, out, flags) if return_flags else (theta, out)
+
+    def params(self, theta_row):
+        """Per term the values of its parameters for one parameter vector."""
+        th = np.asarray(theta_row, dtype=np.float64).ravel()
+        return [[th[idx] if idx >= 0 else val for idx, val in slots] for _, _, slots in self.terms]
+
+    def columns(self, theta_row):
+        """The definition's columns [J, 5] for one parameter vector, or None where a term's parameters are not valid."""
+        cols: List[tuple] = []
+        for (kind, _, _), p in zip(self.terms, self.params(theta_row)):
+            tc = term_columns(kind, p)
+            if tc is None:
+                return None
+            cols += tc
+        return np.asarray(cols, dtype=np.float64)

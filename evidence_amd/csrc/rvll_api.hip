@@ -521,7 +521,7 @@ int rvll_destroy(rvll_handle* h)
     dev_free(h->d_gather_theta); dev_free(h->d_gather_host_in); dev_free(h->d_gather_host_out);
     dev_free(h->d_live_u); dev_free(h->d_live_theta); dev_free(h->d_live_logl); dev_free(h->d_live_birth); dev_free(h->d_live_idx); dev_free(h->d_live_mom);
     dev_free(h->d_sort_keys); dev_free(h->d_sort_rows); dev_free(h->d_sort_temp);
-    dev_free(h->d_cl_in); dev_free(h->d_cl_work); dev_free(h->d_cl_out); dev_free(h->d_adapt); dev_free(h->d_adapt_in); dev_free(h->d_region);
+    dev_free(h->d_cl_in); dev_free(h->d_cl_work); dev_free(h->d_cl_out); dev_free(h->d_adapt); dev_free(h->d_adapt_in); dev_free(h->d_region); dev_free(h->d_cel);
     if (h->d_clseg) { (void)hipFree(h->d_clseg); h->d_clseg = nullptr; }
     dev_free(h->d_dead_theta); dev_free(h->d_dead_logl); dev_free(h->d_dead_birth); dev_free(h->d_runs_idx); dev_free(h->d_runs_mom);
     if (h->pin_in) (void)hipHostFree(h->pin_in);

@@ -40,8 +40,6 @@ constexpr int kGlsBlock = 64;                             // epochs whose terms 
 constexpr int kGlsSums = 6;
 static_assert(kGlsEpochs % kGlsBlock == 0, "the blocks of a sum must start at multiples of kGlsBlock in the epoch table");
 
-struct DriftSlots { rvll_slot s[5]; };                    // lin, quad, cub, quar, tref
-
 __device__ __forceinline__ double gls_slot(const rvll_slot s, const double* th) { return s.idx >= 0 ? th[s.idx] : s.val; }
 
 __global__ __launch_bounds__(kGlsThreads)
@@ -255,6 +253,8 @@ void peak_kernel(const double* __restrict__ P, long long R, int F, int32_t* __re
     }
 }
 
+}  // namespace
+
 hipError_t launch_residuals(const LoglikeArgs& a, const DriftSlots& ds, unsigned include_mask, double* res, double* var,
                             hipStream_t stream)
 {
@@ -275,6 +275,8 @@ DriftSlots drift_slots(const rvll_handle* h)
     ds.s[4] = h->L.tref;
     return ds;
 }
+
+namespace {
 
 constexpr long long kGlsMaxBlocks = 1ll << 30;
 

@@ -8,6 +8,7 @@
 //   rvll_comm.hip       multi-GPU: RCCL communicators, lanes, all-gathers
 //   rvll_cluster_host.hip  MLFriends clustering of many row sets (rvll_cluster_runs)
 //   rvll_region.hip     MLFriends region sampling (rvll_region_draw_runs): kernels and host side
+//   rvll_celerite.hip   log-L under correlated noise (rvll_celerite_loglike_batch): kernel and host side
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -223,6 +224,11 @@ struct rvll_handle {
     // region sampling (rvll_region_draw_runs): one grow-only block of inputs, per-candidate work, per-run state, outputs, trace
     void* d_region = nullptr;
     size_t region_cap = 0;                                    // bytes
+    // correlated noise (rvll_celerite_loglike_batch): one grow-only block of the epoch tables in time order and a chunk's
+    // residuals, variances and results; the host's copy of the epoch times (fetched at the first call)
+    void* d_cel = nullptr;
+    size_t cel_cap = 0;                                       // bytes
+    std::vector<double> cel_times;
     // the clustered step of the resident ensemble (rvll_live_runs_step_clustered): grow-only block of the per-(run, cluster) segments
     // — (offset, rows) [S][2], fold scales [S][2], mean [S][D], covariance [S][D, D] — and what the last clustered step found, for
     // rvll_live_runs_clusters: per listed run the survivors' labels in rank order [A m], the metric scale [A D], the cluster count,
@@ -257,6 +263,15 @@ struct rvll_handle {
     long long gather_theta_cap = 0;             // in rows
     int gather_last = 0;
 };
+
+namespace rvll {
+// rvll_gls.hip: res = datum - model and var = svrad^2 (+ jitter^2) of every (row, epoch) of a.theta, the planets of include_mask
+// subtracted (rvll_residuals_batch's values); asynchronous on `stream`
+struct DriftSlots { rvll_slot s[5]; };                    // lin, quad, cub, quar, tref
+hipError_t launch_residuals(const LoglikeArgs& a, const DriftSlots& ds, unsigned include_mask, double* res, double* var,
+                            hipStream_t stream);
+DriftSlots drift_slots(const rvll_handle* h);
+}  // namespace rvll
 
 namespace rvll {
 namespace host {

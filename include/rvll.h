@@ -621,6 +621,40 @@ int rvll_gls_bands(rvll_handle* h, const double* theta /*[n_groups * n, ndim]*/,
                    int32_t* peak_index /*[n_groups, n]*/, double* peak_power /*[n_groups, n]*/,
                    double* power_out /*NULL or [n_groups, n, n_freq]*/, int64_t chunk_bytes, double* phase_ms /*NULL or [3]*/);
 
+/* ---- log-likelihood under correlated noise: celerite kernels (evidence_amd/correlated.py) ---- */
+/* The covariance of the residuals above is diag(var) + K, K[n][m] = sum over the terms of k(|t_n - t_m|) (Foreman-Mackey et
+ * al. 2017).  A term's parameters par[] are slots like every other model scalar: theta[idx], or the constant val when idx < 0.
+ *   RVLL_NOISE_REAL      par = sigma, tau                 k = sigma^2 exp(-x / tau)                              1 column
+ *   RVLL_NOISE_SHO       par = sigma, rho, q              celerite2's SHOTerm: w0 = 2 pi / rho, S0 = sigma^2 / (w0 q)   2 columns
+ *   RVLL_NOISE_ROTATION  par = sigma, prot, q0, dq, mix   celerite2's RotationTerm: two SHOs at prot and prot / 2       4 columns
+ * |q - 1/2| of an SHO is taken as at least 1e-6 on the side q lies on (q = 1/2 counts as above).  At most
+ * RVLL_NOISE_MAX_TERMS terms and RVLL_NOISE_MAX_RANK columns in all.                                                        */
+#define RVLL_NOISE_REAL 0
+#define RVLL_NOISE_SHO 1
+#define RVLL_NOISE_ROTATION 2
+#define RVLL_NOISE_MAX_TERMS 4
+#define RVLL_NOISE_MAX_RANK 4
+#define RVLL_FLAG_NOISE_INVALID 8   /* the noise parameters of this row give no positive definite covariance -> logL=-1e30 */
+typedef struct rvll_noise_term { int32_t kind; int32_t reserved; rvll_slot par[5]; } rvll_noise_term;
+
+/* logl[b] = -1/2 r^T (diag(var) + K)^-1 r - 1/2 ln det(diag(var) + K) - Ne/2 ln(2 pi) with r, var = rvll_residuals_batch's of row
+ * b with every planet subtracted, by the O(Ne J^2) factorisation of the semiseparable covariance (csrc/rvll_celerite.h), one row
+ * a lane.  x holds theta rows, or with from_cube = 1 unit-cube rows that go through rvll_dev_upload_cube + rvll_dev_prior first
+ * (theta_out, if not NULL, receives rvll_prior_batch's theta, bit for bit).  order lists the epochs in nondecreasing time (ties
+ * in any order; NULL: the table is in that order already).  flags: RVLL_FLAG_INVALID_ORBIT alone for an invalid orbit (logl
+ * -1e30); RVLL_FLAG_NOISE_INVALID (logl -1e30) for noise parameters that are not finite, sigma < 0, mix < 0, tau, rho, q, prot,
+ * q0 + 1/2 or dq not > 0, or a pivot of the factorisation that is not > 0.  The rows go in chunks whose residuals and variances
+ * take at most 256 MiB; a row's bits depend on that row and the epoch table alone.  phase_ms (may be NULL) receives the
+ * HIP-event times of the residual stage and of the solve.
+ * RVLL_E_INVALID: an order that is not a permutation or whose times decrease, n_terms outside [1, RVLL_NOISE_MAX_TERMS], more
+ * than RVLL_NOISE_MAX_RANK columns, an unknown kind, a slot index >= ndim, null buffers, a negative B.  RVLL_E_UNSUPPORTED: a
+ * handle whose precision is not RVLL_PREC_FP64.  RVLL_E_NOPRIORS: from_cube without rvll_set_priors.                        */
+int rvll_celerite_loglike_batch(rvll_handle* h, const double* x /*[B, ndim]: theta, or unit cubes*/, int64_t B,
+                                int32_t from_cube, const rvll_noise_term* terms, int32_t n_terms,
+                                const int32_t* order /*[Ne] epochs in nondecreasing time, NULL: table order*/,
+                                double* theta_out /*NULL, or [B, ndim] when from_cube*/, double* logl /*[B]*/,
+                                int32_t* flags /*[B]*/, double* phase_ms /*NULL or [2]: residual stage, solve*/);
+
 /* ---- FIP periodogram accumulation (post-processing; independent of any model handle) ------------ */
 /* Replaces the accumulation loop of evidence/fip_criterion.py:305-339.  The caller flattens the posterior
  * samples of all planet models of one run into rows, in the reference's loop order (kmod = 1.., then sample
