@@ -165,10 +165,50 @@ def log_likelihood_dense(res, var, t, columns):
     return float(-0.5 * (z @ z) - np.log(np.diag(L)).sum() - 0.5 * res.shape[0] * math.log(_TWO_PI))
 
 
+PAIR_F = 0.2                                # kCelPairF of csrc/rvll_celerite.h
+
+
+def _pairs(cols):
+    """The near-degenerate SHO pairs among the columns: [(j, s, g, w, u1, u2)] for the pair in columns j, j + 1.  Near Q = 1/2
+    the two columns of an SHO hold +-amp / (2 f) (below 1/2), or a and a / f (above), f = sqrt|4 Q² - 1|, and U S U^T subtracts
+    terms 1 / f² times what it leaves.  Such a pair (f < PAIR_F) is carried in the basis phi1 = exp(-g x) cosh w x,
+    phi2 = exp(-g x) sinh(w x) / w (s = +1, below 1/2: g = (c0 + c1) / 2, w = (c1 - c0) / 2) or the same with cos and sin
+    (s = -1, above: g = c, w = d), in which k(x) = u1 phi1 + u2 phi2 with u1 = a0 + a1 or a, u2 = (a0 - a1) w or b d, all of
+    order amp, V = (1, 0), and the propagator over a gap is the 2 x 2 matrix [[m11, s w² m21], [m21, m11]] with
+    m11 = phi1(gap), m21 = phi2(gap).  The second column of an SHO below 1/2 is the only real column with a < 0."""
+    out = []
+    a, b, c, d, form = (cols[:, i] for i in range(5))
+    for j in range(cols.shape[0] - 1):
+        if form[j] == FORM_REAL and form[j + 1] == FORM_REAL and a[j + 1] < 0.0 and c[j + 1] - c[j] < PAIR_F * (c[j + 1] + c[j]):
+            w = 0.5 * (c[j + 1] - c[j])
+            out.append((j, 1.0, 0.5 * (c[j + 1] + c[j]), w, a[j] + a[j + 1], (a[j] - a[j + 1]) * w))
+        elif form[j] == FORM_COS and form[j + 1] == FORM_SIN and d[j] < PAIR_F * c[j]:
+            out.append((j, -1.0, c[j], d[j], a[j], b[j] * d[j]))
+    return out
+
+
+def _pair_propagator(s, g, w, dt):
+    """(m11, m21) of a pair over a gap dt."""
+    y = w * dt
+    if s < 0.0:
+        E = math.exp(-(g * dt))
+        return E * math.cos(y), E * math.sin(y) / w
+    if y < 0.5:                                  # sinh y / y by its series: (exp(y) - exp(-y)) / 2 cancels
+        E, y2 = math.exp(-(g * dt)), y * y
+        ch = sh = 0.0
+        for k in range(7, 0, -1):
+            ch = ch * y2 / ((2 * k - 1) * (2 * k)) + 1.0
+            sh = sh * y2 / ((2 * k) * (2 * k + 1)) + 1.0
+        return E * ch, E * (dt * sh)
+    p0, p1 = math.exp(-((g - w) * dt)), math.exp(-((g + w) * dt))
+    return 0.5 * (p0 + p1), 0.5 * (p0 - p1) / w
+
+
 def log_likelihood_recursive(res, var, t, columns):
     """The same number by the recursion of csrc/rvll_celerite.h: the epochs in stable time order, t from the first of them
-    (exact ties are legal), and per epoch S <- P P^T o (S + D W W^T), f <- P o (f + W z) with P = exp(-c dt), D = A - U S U^T,
-    W = (V - S U) / D, z = r - U f; log-L = -1/2 sum z² / D - 1/2 sum ln D - Ne / 2 ln(2 pi).  INVALID_LOGL where a D is not > 0."""
+    (exact ties are legal), and per epoch S <- P (S + D W W^T) P^T, f <- P (f + W z) with P = diag exp(-c dt), D = A - U S U^T,
+    W = (V - S U) / D, z = r - U f; log-L = -1/2 sum z² / D - 1/2 sum ln D - Ne / 2 ln(2 pi).  A near-degenerate SHO pair
+    (_pairs) has a 2 x 2 block in P and constant U and V.  INVALID_LOGL where a D is not > 0."""
     res, var, t = (np.asarray(v, dtype=np.float64) for v in (res, var, t))
     if columns is None or not np.isfinite(res).all():
         return INVALID_LOGL
@@ -177,6 +217,7 @@ def log_likelihood_recursive(res, var, t, columns):
     a, b, c, d = cols[:, 0], cols[:, 1], cols[:, 2], cols[:, 3]
     form = cols[:, 4].astype(int)
     suma = a[form != FORM_SIN].sum()
+    pairs = _pairs(cols)
     order = np.argsort(t, kind="stable")
     ts = t[order] - t[order[0]]
     S, f, W = np.zeros((J, J)), np.zeros(J), np.zeros(J)
@@ -184,12 +225,18 @@ def log_likelihood_recursive(res, var, t, columns):
     with np.errstate(all="ignore"):
         for n, e in enumerate(order):
             if n > 0:
-                P = np.exp(-c * (ts[n] - ts[n - 1]))
-                S = np.outer(P, P) * (S + D * np.outer(W, W))
-                f = P * (f + W * z)
+                dt = ts[n] - ts[n - 1]
+                P = np.diag(np.exp(-c * dt))
+                for j, s, g, w, _, _ in pairs:
+                    m11, m21 = _pair_propagator(s, g, w, dt)
+                    P[j:j + 2, j:j + 2] = [[m11, s * w * w * m21], [m21, m11]]
+                S = P @ (S + D * np.outer(W, W)) @ P.T
+                f = P @ (f + W * z)
             cs, sn = np.cos(d * ts[n]), np.sin(d * ts[n])
             U = np.where(form == FORM_SIN, a * sn - b * cs, np.where(form == FORM_COS, a * cs + b * sn, a))
             V = np.where(form == FORM_SIN, sn, np.where(form == FORM_COS, cs, 1.0))
+            for j, _, _, _, u1, u2 in pairs:
+                U[j:j + 2], V[j:j + 2] = (u1, u2), (1.0, 0.0)
             SU = S @ U
             D = (var[e] + suma) - U @ SU
             if not D > 0.0:
@@ -212,7 +259,8 @@ class CorrelatedNoiseModel:
     parnames, ndim, log_likelihood(_batch), prior_transform(_batch) and prior_loglike_batch make it a drop-in for the model in
     callbacks.make_ultranest_callbacks(gp, vectorized=True), callbacks.make_polychord_callbacks(gp) and as
     run_nested_slice(gp.prior_transform_batch, gp.log_likelihood_batch, gp.ndim, prior_loglike=gp.prior_loglike_batch, ...) or
-    run_nested_ensemble in the same way; the results go through merge, posterior, marginals, fip and sensitivity as they are.
+    run_nested_ensemble(gp.prior_transform_batch, gp.log_likelihood_batch, gp.ndim, seeds, walker_runs=gp.slice_walk_runs, ...);
+    the results go through merge, posterior, marginals, fip and sensitivity as they are.
 
     Not offered: the device walks, the resident live sets, region_runs and the scalar server (low_latency=True) evaluate the
     white likelihood inside their kernels; do not pass the model's walker / live / region callables along with this likelihood.
@@ -274,6 +322,33 @@ class CorrelatedNoiseModel:
         prior_transform_batch and of log_likelihood_batch on its result."""
         theta, out, flags = self._call(cubes, True, timing)
         return (theta, out, flags) if return_flags else (theta, out)
+
+    def slice_walk_runs(self, cube, theta, logl, run_start, lstar, chol, wrapped=None, nsteps=10, max_rounds=200, seeds=(),
+                        proposal=None, step_width=None):
+        """walker_runs= of run_nested_ensemble under this likelihood (the model's own slice_walk_runs walks under the white one):
+        rows run_start[r] .. run_start[r + 1] are the walkers of run r, which take nsteps chord moves inside logL > lstar[r] with
+        the whitening factor chol[r], drawn from default_rng(seeds[r]).  The walk is the host's (nested._host_chord_walk); every
+        shrink round of a run is one prior_loglike_batch call.  Returns (cube, theta, logl, ncalls[R])."""
+        from .nested import _evaluator, _host_chord_walk
+        if proposal not in (None, "chord"):
+            raise ValueError("the correlated-noise walk is the chord walk")
+        cube = np.array(self.model._theta2d(cube), dtype=np.float64, order="C")
+        theta = np.array(self.model._theta2d(theta), dtype=np.float64, order="C")
+        logl = np.array(logl, dtype=np.float64).reshape(-1)
+        run_start = np.asarray(run_start, dtype=np.int64).reshape(-1)
+        nrun = run_start.shape[0] - 1
+        if nrun < 0 or run_start[0] != 0 or run_start[-1] != cube.shape[0] or len(lstar) != nrun or len(seeds) != nrun:
+            raise ValueError("run_start must rise from 0 to the number of walkers, with one lstar and one seed per run")
+        evaluate = _evaluator(None, None, self.prior_loglike_batch)
+        wr = None if wrapped is None else np.asarray(wrapped, dtype=bool)
+        ncalls = []
+        for r in range(nrun):
+            rows = slice(int(run_start[r]), int(run_start[r + 1]))
+            rng = np.random.default_rng(int(seeds[r]) & (2 ** 64 - 1))
+            steps = int(nsteps if np.ndim(nsteps) == 0 else nsteps[r])
+            ncalls.append(_host_chord_walk(cube[rows], theta[rows], logl[rows], float(lstar[r]), np.asarray(chol[r], dtype=np.float64),
+                                           wr, steps, rng, evaluate))
+        return cube, theta, logl, ncalls
 
     def params(self, theta_row):
         """Per term the values of its parameters for one parameter vector."""

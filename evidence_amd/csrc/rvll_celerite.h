@@ -13,6 +13,9 @@
 //   cel_step      one epoch: S <- P P^T o (S + D W W^T), f <- P o (f + W z) with P = exp(-c dt) of the gap to the previous epoch,
 //                 D = A - U S U^T, W = (V - S U) / D, z = r - U f, and the sums of z^2 / D and ln D.  Before the first epoch S,
 //                 f, W, D and z are 0 and its gap is 0, so the first epoch takes the same code.
+//   cel_prepare   a near-degenerate SHO pair (|q - 1/2| < 0.01) is rewritten into a sum / difference basis whose block of P is
+//                 2 x 2 and whose U and V are constant; cel_step then carries S and f over the gap with a tridiagonal P
+//                 (cel_advance_pair) where the row has such a pair, and with the diagonal P above (cel_advance) where not.
 //   cel_result    log-L = -1/2 sum z^2 / D - 1/2 sum ln D - Ne / 2 ln(2 pi), or -1e30 and a flag.
 // The times are measured from the first epoch in time order, and both they and the gaps come from a per-epoch table the host
 // builds (rvll_celerite.hip): the kernel takes one sincos per epoch and complex term and one exponential per epoch and distinct c.
@@ -29,7 +32,8 @@ namespace rvll {
 constexpr double kCelTwoPi = 6.283185307179586476925286766559;    // fl(2 pi), as 2 * np.pi
 constexpr double kCelQClamp = 1.0e-6;
 constexpr double kCelInvalid = -1.0e30;                            // the reference's sentinel (rvmodel:203)
-enum { kCelColReal = 0, kCelColCos = 1, kCelColSin = 2 };
+constexpr double kCelPairF = 0.2;                                   // an SHO pair with f = sqrt|4 q^2 - 1| below this changes basis
+enum { kCelColReal = 0, kCelColCos = 1, kCelColSin = 2, kCelColPairA = 3, kCelColPairB = 4 };
 
 struct CelColumn { double a, b, c, d; int form; };                // form: kCelCol*
 
@@ -114,12 +118,80 @@ RVLL_HD void cel_init(CelState<J>& st)
     st.bad = 0;
 }
 
-// One epoch at time t (from the first epoch), dt after the previous one (0 at the first), with residual r and variance var;
-// A = var + sum of the columns' a.
+// The near-degenerate pairs.  Near q = 1/2 the two columns of an SHO hold a = +-amp / (2 f) (below 1/2) or a and b = a / f
+// (above), f = sqrt|4 q^2 - 1|, and U S U^T subtracts terms 1 / f^2 times what it leaves: at the clamp float64 loses
+// (sigma / svrad)^2 2e-12 of log-L.  A pair with f < kCelPairF is therefore carried in the basis
+//     phi1(x) = exp(-g x) cosh w x, phi2(x) = exp(-g x) sinh(w x) / w       (below: g = (c0 + c1) / 2, w = (c1 - c0) / 2)
+//     phi1(x) = exp(-g x) cos w x,  phi2(x) = exp(-g x) sin(w x) / w        (above: g = c, w = d)
+// in which k(x) = u1 phi1 + u2 phi2 with u1 = a0 + a1 or a and u2 = (a0 - a1) w or b d, both of the order of amp (the two
+// differences are exact or harmless: the columns are the definition's, rounding included), U = (u1, u2) and V = (1, 0) are
+// constant, and the pair's block of P is [[m11, s w^2 m21], [m21, m11]] with m11 = phi1(dt), m21 = phi2(dt), s = +-1.
+// cel_prepare rewrites such a pair in place: a = u1 | u2, b = s w^2, c = g, d = w, form = kCelColPairA | kCelColPairB.  It keys on
+// the columns alone: the second column of an SHO below 1/2 is the only real column with a < 0.  true: the row has such a pair.
 template <int J>
-RVLL_HD void cel_step(const CelColumn (&col)[J], double suma, CelState<J>& st, double t, double dt, double r, double var)
+RVLL_HD bool cel_prepare(CelColumn (&col)[J])
 {
-    double P[J], U[J], V[J];
+    bool any = false;
+#pragma unroll
+    for (int j = 0; j + 1 < J; ++j) {
+        CelColumn &p = col[j], &q = col[j + 1];
+        if (p.form == kCelColReal && q.form == kCelColReal && q.a < 0.0 && q.c - p.c < kCelPairF * (q.c + p.c)) {
+            const double w = 0.5 * (q.c - p.c), g = 0.5 * (q.c + p.c), u1 = p.a + q.a, u2 = (p.a - q.a) * w;
+            p.a = u1;
+            q.a = u2;
+            p.b = q.b = w * w;
+            p.c = q.c = g;
+            p.d = q.d = w;
+            p.form = kCelColPairA;
+            q.form = kCelColPairB;
+            any = true;
+        } else if (p.form == kCelColCos && q.form == kCelColSin && p.d < kCelPairF * p.c) {
+            q.a = p.b * p.d;
+            p.b = q.b = -(p.d * p.d);
+            p.form = kCelColPairA;
+            q.form = kCelColPairB;
+            any = true;
+        }
+    }
+    return any;
+}
+
+// m11 = phi1(dt) and m21 = phi2(dt) of a prepared pair.  sinh y / y comes from its series below y = 1/2, where
+// (exp(y) - exp(-y)) / 2 cancels, and from the two exponentials of the columns above it, where exp(-g dt) cosh(y) would be 0 inf.
+RVLL_HD void cel_pair_propagator(const CelColumn& k, double dt, double& m11, double& m21)
+{
+    const double w = k.d, y = w * dt;
+    if (k.b < 0.0) {
+        const double E = exp(-(k.c * dt));
+        double sn, cs;
+        sincos_f64(y, sn, cs);
+        m11 = E * cs;
+        m21 = E * sn / w;
+    } else if (y < 0.5) {
+        const double E = exp(-(k.c * dt)), y2 = y * y;
+        double ch = 1.0 / 87178291200.0, sh = 1.0 / 1307674368000.0;             // 1 / 14!, 1 / 15!: the next terms are < 1e-18
+        ch = __builtin_fma(ch, y2, 1.0 / 479001600.0);  sh = __builtin_fma(sh, y2, 1.0 / 6227020800.0);
+        ch = __builtin_fma(ch, y2, 1.0 / 3628800.0);    sh = __builtin_fma(sh, y2, 1.0 / 39916800.0);
+        ch = __builtin_fma(ch, y2, 1.0 / 40320.0);      sh = __builtin_fma(sh, y2, 1.0 / 362880.0);
+        ch = __builtin_fma(ch, y2, 1.0 / 720.0);        sh = __builtin_fma(sh, y2, 1.0 / 5040.0);
+        ch = __builtin_fma(ch, y2, 1.0 / 24.0);         sh = __builtin_fma(sh, y2, 1.0 / 120.0);
+        ch = __builtin_fma(ch, y2, 0.5);                sh = __builtin_fma(sh, y2, 1.0 / 6.0);
+        ch = __builtin_fma(ch, y2, 1.0);                sh = __builtin_fma(sh, y2, 1.0);
+        m11 = E * ch;
+        m21 = E * (dt * sh);
+    } else {
+        const double p0 = exp(-((k.c - w) * dt)), p1 = exp(-((k.c + w) * dt));
+        m11 = 0.5 * (p0 + p1);
+        m21 = 0.5 * (p0 - p1) / w;
+    }
+}
+
+// U and V of an epoch at time t (from the first epoch), dt after the previous one, and the state carried over the gap:
+// S <- P P^T o (S + D W W^T), f <- P o (f + W z).
+template <int J>
+RVLL_HD void cel_advance(const CelColumn (&col)[J], CelState<J>& st, double t, double dt, double (&U)[J], double (&V)[J])
+{
+    double P[J];
     double sn = 0.0, cs = 1.0;
 #pragma unroll
     for (int j = 0; j < J; ++j) {
@@ -139,7 +211,6 @@ RVLL_HD void cel_step(const CelColumn (&col)[J], double suma, CelState<J>& st, d
             }
         }
     }
-    // S <- P P^T o (S + D W W^T), f <- P o (f + W z)
 #pragma unroll
     for (int j = 0; j < J; ++j) {
         const double dw = st.D * st.W[j];
@@ -148,6 +219,89 @@ RVLL_HD void cel_step(const CelColumn (&col)[J], double suma, CelState<J>& st, d
             st.S[cel_tri<J>(j, k)] = (P[j] * P[k]) * __builtin_fma(dw, st.W[k], st.S[cel_tri<J>(j, k)]);
         st.f[j] = P[j] * __builtin_fma(st.W[j], st.z, st.f[j]);
     }
+}
+
+// The same for a row with a prepared pair: P is tridiagonal, row j of P X = al_j X_j + up_j X_(j+1) + dn_j X_(j-1) with up and dn
+// 0 outside a pair's block, so every index is a constant and S <- P (S + D W W^T) P^T, f <- P (f + W z) stay in registers.
+template <int J>
+RVLL_HD void cel_advance_pair(const CelColumn (&col)[J], CelState<J>& st, double t, double dt, double (&U)[J], double (&V)[J])
+{
+    double al[J], up[J], dn[J];
+    double sn = 0.0, cs = 1.0, m21 = 0.0;
+#pragma unroll
+    for (int j = 0; j < J; ++j) {
+        const int form = col[j].form;
+        up[j] = dn[j] = 0.0;
+        if (form == kCelColSin) {
+            al[j] = j > 0 ? al[j - 1] : 1.0;
+            U[j] = __builtin_fma(col[j].a, sn, -(col[j].b * cs));
+            V[j] = sn;
+        } else if (form == kCelColPairB) {
+            al[j] = j > 0 ? al[j - 1] : 1.0;
+            dn[j] = m21;
+            U[j] = col[j].a;
+            V[j] = 0.0;
+        } else if (form == kCelColPairA) {
+            cel_pair_propagator(col[j], dt, al[j], m21);
+            up[j] = col[j].b * m21;
+            U[j] = col[j].a;
+            V[j] = 1.0;
+        } else {
+            al[j] = exp(-(col[j].c * dt));
+            if (form == kCelColCos) {
+                sincos_f64(col[j].d * t, sn, cs);
+                U[j] = __builtin_fma(col[j].a, cs, col[j].b * sn);
+                V[j] = cs;
+            } else {
+                U[j] = col[j].a;
+                V[j] = 1.0;
+            }
+        }
+    }
+    double T[J * (J + 1) / 2], R[J][J], g[J];
+#pragma unroll
+    for (int j = 0; j < J; ++j) {
+        const double dw = st.D * st.W[j];
+#pragma unroll
+        for (int k = j; k < J; ++k) T[cel_tri<J>(j, k)] = __builtin_fma(dw, st.W[k], st.S[cel_tri<J>(j, k)]);
+        g[j] = __builtin_fma(st.W[j], st.z, st.f[j]);
+    }
+#pragma unroll
+    for (int j = 0; j < J; ++j) {
+#pragma unroll
+        for (int k = 0; k < J; ++k) {
+            double x = al[j] * T[j <= k ? cel_tri<J>(j, k) : cel_tri<J>(k, j)];
+            if (j + 1 < J) x = __builtin_fma(up[j], T[j + 1 <= k ? cel_tri<J>(j + 1, k) : cel_tri<J>(k, j + 1)], x);
+            if (j > 0) x = __builtin_fma(dn[j], T[j - 1 <= k ? cel_tri<J>(j - 1, k) : cel_tri<J>(k, j - 1)], x);
+            R[j][k] = x;
+        }
+        double y = al[j] * g[j];
+        if (j + 1 < J) y = __builtin_fma(up[j], g[j + 1], y);
+        if (j > 0) y = __builtin_fma(dn[j], g[j - 1], y);
+        st.f[j] = y;
+    }
+#pragma unroll
+    for (int j = 0; j < J; ++j) {
+#pragma unroll
+        for (int k = j; k < J; ++k) {
+            double x = al[k] * R[j][k];
+            if (k + 1 < J) x = __builtin_fma(up[k], R[j][k + 1], x);
+            if (k > 0) x = __builtin_fma(dn[k], R[j][k - 1], x);
+            st.S[cel_tri<J>(j, k)] = x;
+        }
+    }
+}
+
+// One epoch at time t (from the first epoch), dt after the previous one (0 at the first), with residual r and variance var;
+// A = var + sum of the columns' a (taken before cel_prepare); pair: what cel_prepare returned for the row.
+template <int J>
+RVLL_HD void cel_step(const CelColumn (&col)[J], double suma, bool pair, CelState<J>& st, double t, double dt, double r, double var)
+{
+    double U[J], V[J];
+    if (J >= 2 && pair)
+        cel_advance_pair<J>(col, st, t, dt, U, V);
+    else
+        cel_advance<J>(col, st, t, dt, U, V);
     // D = A - U S U^T, W = (V - S U) / D, z = r - U f
     double SU[J];
     double usu = 0.0, uf = 0.0;
@@ -170,6 +324,13 @@ RVLL_HD void cel_step(const CelColumn (&col)[J], double suma, CelState<J>& st, d
     st.lndet += log(D);
     if (r != r) st.bad |= 1;
     if (!(D > 0.0)) st.bad |= 2;
+}
+
+// The same for columns as cel_column left them, without cel_prepare: every row on the diagonal path.
+template <int J>
+RVLL_HD void cel_step(const CelColumn (&col)[J], double suma, CelState<J>& st, double t, double dt, double r, double var)
+{
+    cel_step<J>(col, suma, false, st, t, dt, r, var);
 }
 
 // cte = -Ne / 2 ln(2 pi).  valid: every column's parameters were.

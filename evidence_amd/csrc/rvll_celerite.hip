@@ -61,6 +61,7 @@ void celerite_kernel(const double* __restrict__ theta, int D, long long B, const
         valid &= cel_column(plan.kind[j], plan.sub[j], p, col[j]);
         if (col[j].form != kCelColSin) suma += col[j].a;             // a complex term's a counts once
     }
+    const bool pair = cel_prepare<J>(col);                            // a near-degenerate SHO pair changes basis (rvll_celerite.h)
     CelState<J> st;
     cel_init(st);
     const int le = lane & (kCelEpochs - 1), lr = lane >> 5;           // the tile load: this lane's epoch, and which row of a pair
@@ -78,7 +79,7 @@ void celerite_kernel(const double* __restrict__ theta, int D, long long B, const
         }
         __syncthreads();
         for (int e = 0; e < ec; ++e)
-            cel_step<J>(col, suma, st, ts[e0 + e], dts[e0 + e], sh_r[lane * kCelStride + e], sh_v[lane * kCelStride + e]);
+            cel_step<J>(col, suma, pair, st, ts[e0 + e], dts[e0 + e], sh_r[lane * kCelStride + e], sh_v[lane * kCelStride + e]);
     }
     if (row < B) {
         double l;

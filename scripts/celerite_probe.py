@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """The correlated-noise likelihood at the cfg3 shape: B = 16384 parameter vectors x 200 epochs of the synthetic
-workload 3, with one noise term of J = 1 (real), 2 (sho) and 4 (rotation) columns whose parameters are free.
+workload 3, with one noise term of J = 1 (real), 2 (sho) and 4 (rotation) columns whose parameters are free, and the last two
+again with Q within 0.005 of 1/2, where the solve carries the SHO's two columns in the pair basis.
     device      correlated.CorrelatedNoiseModel.log_likelihood_batch after a warm-up call: HIP-event time of the residual stage
                 (launch_residuals: keprv_kernel + residual_kernel) and of the solve (celerite_kernel<J>), and rows/s of the whole
                 call with its upload and download, best of REPEATS calls
@@ -26,6 +27,10 @@ DENSE_ROWS = 64
 TERMS = [(1, "real", {"gp1_sigma": (1.0, 3.0), "gp1_tau": (5.0, 50.0)}),
          (2, "sho", {"gp1_sigma": (1.0, 3.0), "gp1_rho": (5.0, 50.0), "gp1_q": (0.6, 5.0)}),
          (4, "rotation", {"gp1_sigma": (1.0, 3.0), "gp1_prot": (5.0, 50.0), "gp1_q0": (0.5, 3.0), "gp1_dq": (0.1, 2.0),
+                          "gp1_mix": (0.1, 1.0)}),
+         # every row in the pair basis of csrc/rvll_celerite.h (|q - 1/2| < 0.01), on both sides of 1/2; the rotation's faster oscillator
+         (2, "sho", {"gp1_sigma": (1.0, 3.0), "gp1_rho": (5.0, 50.0), "gp1_q": (0.495, 0.505)}),
+         (4, "rotation", {"gp1_sigma": (1.0, 3.0), "gp1_prot": (5.0, 50.0), "gp1_q0": (1e-6, 5e-3), "gp1_dq": (0.1, 2.0),
                           "gp1_mix": (0.1, 1.0)})]
 
 
@@ -77,7 +82,8 @@ def main(B, out):
             ok = (flags[:DENSE_ROWS] == 0) & (want > -1e29)
             worst = float(np.max(np.abs(got[:DENSE_ROWS] - want)[ok] / np.maximum(1.0, np.abs(want[ok]))))
             worst_all = max(worst_all, worst)
-            say(f"  J = {J} ({kind:8s}):  residual stage {t['residuals_ms']:8.3f} ms   solve {t['solve_ms']:8.3f} ms   call "
+            pair = " near 1/2" if any(n.endswith(("_q", "_q0")) and hi < 0.51 for n, (_, hi) in ranges.items()) else ""
+            say(f"  J = {J} ({kind:8s}{pair}):  residual stage {t['residuals_ms']:8.3f} ms   solve {t['solve_ms']:8.3f} ms   call "
                 f"{1e3 * call_s:8.3f} ms = {B / call_s:.3e} rows/s   flagged rows {int((flags != 0).sum())}")
             say(f"      definition (numpy Cholesky, scaled from {DENSE_ROWS} rows x {B // DENSE_ROWS}): {dense_s:8.2f} s = "
                 f"{B / dense_s:.3e} rows/s   call / definition {call_s / dense_s:.2e}   largest |device - definition| / "

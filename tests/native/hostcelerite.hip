@@ -23,9 +23,10 @@ void run(const int* kind, const int* sub, const double* par, int ne, const doubl
         valid &= rvll::cel_column(kind[j], sub[j], par + 5 * j, col[j]);
         if (col[j].form != rvll::kCelColSin) suma += col[j].a;
     }
+    const bool pair = rvll::cel_prepare<J>(col);
     rvll::CelState<J> st;
     rvll::cel_init(st);
-    for (int n = 0; n < ne; ++n) rvll::cel_step<J>(col, suma, st, ts[n], dts[n], res[n], var[n]);
+    for (int n = 0; n < ne; ++n) rvll::cel_step<J>(col, suma, pair, st, ts[n], dts[n], res[n], var[n]);
     int32_t f;
     rvll::cel_result<J>(st, valid, cte, *logl, f);
     *flag = f; }

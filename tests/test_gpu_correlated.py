@@ -2,7 +2,10 @@
 definition (correlated.log_likelihood_dense) applied to the model's own residuals, at the project's parity bound
 |delta| <= 1e-10 max(1, |log-L|): every term kind, Q on both sides of and at the 1/2 clamp, every edge of the LDS epoch tile and
 of the row blocks, a table that is not in time order with exact ties and a 3000-day gap; that a row's bits depend on the row
-alone; the white limit; the flags and the refusals; and the evidence of a linear model in closed form.
+alone; the white limit; the flags and the refusals; and the evidence of a linear model in closed form.  Against the definition
+in long double (correlated_cases.dense_reference), every row compared: every composition of columns with Q on a different side of
+1/2 from lane to lane and invalid rows between them, log-uniform draws over a prior's decades on four tables, the band around
+Q = 1/2 at sigma up to 100 svrad, and tables in time order (order = NULL), in decreasing time and with every epoch at one time.
 
 Every agreement case prints its largest difference; profiles/celerite_probe.txt records the largest one seen."""
 import os
@@ -261,9 +264,10 @@ def test_callbacks_take_the_wrapper(gpu_required):
         assert np.array_equal(prior1(cubes[2]), theta[2]) and loglike1(theta[2]) == (want[2], [])
 
 
-def test_evidence_of_a_linear_model_in_closed_form(gpu_required):
+def _linear_case():
     """0 planets, 40 epochs, a fixed SHO term, free offset and linear drift under uniform priors 12 posterior sigma wide on each
-    side of the generalised-least-squares solution: ln Z = log-L(beta) + 1/2 ln det(2 pi (A^T Sigma^-1 A)^-1) - ln(prior volume)."""
+    side of the generalised-least-squares solution: ln Z = log-L(beta) + 1/2 ln det(2 pi (A^T Sigma^-1 A)^-1) - ln(prior volume).
+    -> (noise, table, priors, truth, (y, A, beta, svrad, t, cols))"""
     ne = 40
     rng = np.random.default_rng(40)
     t = 55000.0 + np.sort(rng.uniform(0.0, 120.0, ne))
@@ -283,6 +287,11 @@ def test_evidence_of_a_linear_model_in_closed_form(gpu_required):
              - np.log(np.prod(hi - lo)))
     table = EpochTable.from_arrays(["a"], t, y, svrad, np.zeros(ne, dtype=np.int32))
     pri = {"a_offset": P.Uniform(lo[0], hi[0]), "drift_lin": P.Uniform(lo[1], hi[1])}
+    return noise, table, pri, truth, (y, A, beta, svrad, t, cols)
+
+
+def test_evidence_of_a_linear_model_in_closed_form(gpu_required):
+    noise, table, pri, truth, (y, A, beta, svrad, t, cols) = _linear_case()
     with GpuRVModel(noise, table, list(pri), priordict=pri) as model:
         gp = correlated.CorrelatedNoiseModel(model, [("sho", "gp1")])
         assert gp.parnames == ["a_offset", "drift_lin"]
@@ -294,3 +303,169 @@ def test_evidence_of_a_linear_model_in_closed_form(gpu_required):
         print(f"ln Z {r.logz:.4f} +- {r.logzerr:.4f}, truth {truth:.4f}")
     for r in out:
         assert abs(r.logz - truth) < 4 * r.logzerr + 0.05, (r.logz, r.logzerr, truth)
+
+
+def test_evidence_of_a_linear_model_through_run_nested_ensemble(gpu_required):
+    """The wrapper as a drop-in for run_nested_ensemble: its own slice_walk_runs walks under the correlated likelihood."""
+    from evidence_amd.nested import run_nested_ensemble
+    noise, table, pri, truth, _ = _linear_case()
+    with GpuRVModel(noise, table, list(pri), priordict=pri) as model:
+        gp = correlated.CorrelatedNoiseModel(model, [("sho", "gp1")])
+        r, = run_nested_ensemble(gp.prior_transform_batch, gp.log_likelihood_batch, gp.ndim, [1], nlive=400, dlogz=0.01,
+                                 walker_runs=gp.slice_walk_runs)
+    print(f"ln Z {r.logz:.4f} +- {r.logzerr:.4f}, truth {truth:.4f}")
+    assert abs(r.logz - truth) < 4 * r.logzerr + 0.05, (r.logz, r.logzerr, truth)
+
+
+# ---- lane-mixed forms, the prior's range, the band at Q = 1/2 and the tables, against the long-double reference -----------------------
+B_MIXED = 128                                # two waves of rows
+NE_WIDE = 2 * cc.EPOCH_BLOCK + 1             # three epoch tiles, the last with one epoch
+SUFFIXES = sorted({s for _, names in correlated.KINDS.values() for s in names})
+WIDE_TABLES = {"ne65": lambda: cc.make_table(NE_WIDE), "ne64": lambda: cc.make_table(2 * cc.EPOCH_BLOCK),
+               "ne96": lambda: cc.make_table(3 * cc.EPOCH_BLOCK), "cadence": cc.cadence_table, "sorted": cc.sorted_table,
+               "decreasing": cc.decreasing_table, "ties": cc.ties_table}
+ALONE = (0, 1, 2, 3, 4, 5, 6, 71)            # one row of every entry of cc.Q_SIDES and one of the second wave, none of them invalid
+
+
+class _Models:
+    """One model a (table, planets): every parameter of gp1 to gp4 free, so that one handle serves every composition."""
+
+    def __init__(self):
+        self.open = {}
+
+    def get(self, table_id, planets):
+        if (table_id, planets) not in self.open:
+            table = WIDE_TABLES[table_id]()
+            ne = table.time.size
+            names, fixed, linpar = [f"{i}_offset" for i in table.insts], {}, None
+            if planets:
+                names += PLANET_NAMES + [f"{i}_jitter" for i in table.insts] + ["drift_lin", "linpar_fwhm"]
+                fixed = {"planet1_epoch": 55000.0, "planet2_epoch": 55001.5}
+                linpar = {"fwhm": np.random.default_rng(ne).normal(0.0, 1.0, ne)}
+            names += [f"gp{k}_{s}" for k in (1, 2, 3, 4) for s in SUFFIXES]
+            self.open[table_id, planets] = GpuRVModel(fixed, table, names, linpar_dict=linpar)
+        return self.open[table_id, planets]
+
+    def close(self):
+        for m in self.open.values():
+            m.close()
+
+
+@pytest.fixture(scope="module")
+def models():
+    m = _Models()
+    yield m
+    m.close()
+
+
+def _evaluate(model, terms, values, seed):
+    """The rows of a generator on a model: X, the device's log-L and flags, the long-double reference on the model's own
+    residuals (NaN where the definition has no covariance) and which rows are valid."""
+    n = len(next(iter(values.values())))
+    X = _theta(model, n, seed)
+    for name, v in values.items():
+        X[:, model.parnames.index(name)] = v
+    gp = correlated.CorrelatedNoiseModel(model, terms)
+    res, var = model.residuals_batch(X)
+    cols, valid = cc.rows_columns(terms, values)
+    assert np.array_equal(gp.columns(X[0]), cols[0])
+    want = cc.dense_reference(res, var, model.table.time, cols)
+    assert np.array_equal(np.isfinite(want), valid)
+    got, flags = gp.log_likelihood_batch(X, return_flags=True)
+    return gp, X, got, flags, want, valid
+
+
+def _hold(label, got, flags, want, valid, bound=cc.PARITY):
+    """Every row counts: the valid ones within the bound with no flag, the others refused."""
+    err = cc.ref_err(got[valid], want[valid])
+    print(f"{label}: max rel err {err.max():.3e} over {valid.sum()} rows against long double")
+    assert err.max() <= bound, (label, int(np.flatnonzero(valid)[err.argmax()]), err.max())
+    assert not flags[valid].any()
+    assert (got[~valid] == -1e30).all() and (flags[~valid] == _abi.FLAG_NOISE_INVALID).all()
+    return float(err.max())
+
+
+@pytest.mark.parametrize("composition", list(cc.COMPOSITIONS))
+def test_lane_mixed_forms(gpu_required, models, composition):
+    """Neighbouring lanes run different forms (Q on every side of 1/2, invalid rows between them) in every composition."""
+    for planets in (False, True):
+        model = models.get("ne65", planets)
+        terms, values = cc.mixed_rows(composition, B_MIXED, seed=2, svmin=model.table.svrad.min())
+        gp, X, got, flags, want, valid = _evaluate(model, terms, values, seed=21)
+        assert (~valid).sum() == B_MIXED // cc.INVALID_EVERY
+        _hold(f"mixed {composition} planets {planets}", got, flags, want, valid)
+        # a row alone gives the bits it had in the batch; so does the batch reversed, row by row
+        for i in ALONE:
+            assert valid[i] and gp.log_likelihood(X[i]) == got[i], (composition, i)
+        back, bflags = gp.log_likelihood_batch(np.ascontiguousarray(X[::-1]), return_flags=True)
+        assert np.array_equal(back[::-1], got) and np.array_equal(bflags[::-1], flags)
+        # an invalid row leaves its neighbours alone: the batch with those rows repaired has the other rows' bits
+        mended = X.copy()
+        bad = np.flatnonzero(~valid)
+        mended[bad] = X[bad - 1]
+        again, aflags = gp.log_likelihood_batch(mended, return_flags=True)
+        assert np.array_equal(again[valid], got[valid]) and np.array_equal(again[bad], got[bad - 1]) and not aflags.any()
+
+
+@pytest.mark.parametrize("composition", ["2", "12", "22", "211", "rotation"])
+@pytest.mark.parametrize("table_id", ["ne65", "ne64", "ne96", "cadence"])
+def test_the_priors_range(gpu_required, models, table_id, composition):
+    """Log-uniform draws over a prior's decades: d t up to 2e6 in the sincos, exp(-c dt) through underflow to 0, c of 1e5 a day,
+    sigma up to 30 svrad."""
+    for planets in (False, True):
+        model = models.get(table_id, planets)
+        terms, values = cc.wide_rows(composition, B_MIXED, seed=3, svmin=model.table.svrad.min())
+        _, _, got, flags, want, valid = _evaluate(model, terms, values, seed=31)
+        assert valid.all()
+        _hold(f"wide {composition} {table_id} planets {planets}", got, flags, want, valid)
+
+
+@pytest.mark.parametrize("composition", ["sho", "rotation"])
+def test_the_band_around_q_one_half(gpu_required, models, composition):
+    """sigma up to 100 svrad within 1e-4 of Q = 1/2 (cc.band_rows): the pair basis of csrc/rvll_celerite.h holds the bound where the
+    two nearly cancelling columns lost 6.4e-9."""
+    for planets in (False, True):
+        model = models.get("ne65", planets)
+        terms, values = cc.band_rows(model.table.svrad.min())[composition]
+        _, _, got, flags, want, valid = _evaluate(model, terms, values, seed=41)
+        assert valid.all()
+        _hold(f"band {composition} planets {planets}", got, flags, want, valid)
+
+
+def test_tables_in_time_order_decreasing_and_all_ties(gpu_required, models):
+    # a table already in time order: order = NULL is the identity, bit for bit; NULL on a table that is not in order is refused
+    model = models.get("sorted", True)
+    terms, values = cc.mixed_rows("211", B_MIXED, seed=4, svmin=model.table.svrad.min())
+    gp, X, got, flags, want, valid = _evaluate(model, terms, values, seed=51)
+    assert np.array_equal(gp.order, np.arange(model.table.time.size))
+    _hold("sorted 211", got, flags, want, valid)
+    out, fl = np.empty(B_MIXED), np.zeros(B_MIXED, dtype=np.int32)
+
+    def null_order(m, g, x):
+        return m._lib.rvll_celerite_loglike_batch(m._h, _abi.as_dp(x), B_MIXED, 0, g._terms_c, len(g.terms), None, None, _abi.as_dp(out),
+                                                  _abi.as_ip(fl), None)
+    assert null_order(model, gp, X) == _abi.OK
+    assert np.array_equal(out, got) and np.array_equal(fl, flags)
+    unsorted = models.get("ne65", True)
+    ugp = correlated.CorrelatedNoiseModel(unsorted, terms)
+    assert null_order(unsorted, ugp, _theta(unsorted, B_MIXED, seed=52)) == _abi.E_INVALID
+    # the same table listed in decreasing time
+    model = models.get("decreasing", True)
+    for which, composition in (("mixed", "22"), ("wide", "12")):
+        terms, values = getattr(cc, which + "_rows")(composition, B_MIXED, seed=5, svmin=model.table.svrad.min())
+        gp, X, got, flags, want, valid = _evaluate(model, terms, values, seed=53)
+        assert np.array_equal(gp.order, np.arange(model.table.time.size)[::-1])
+        _hold(f"decreasing {which} {composition}", got, flags, want, valid)
+    # every epoch at one time: every gap is 0 and Sigma = diag(var) + sum(a) 1 1^T
+    for planets in (False, True):
+        model = models.get("ties", planets)
+        for composition in ("1", "2", "rotation"):
+            terms, values = cc.mixed_rows(composition, B_MIXED, seed=6, svmin=model.table.svrad.min())
+            gp, X, got, flags, want, valid = _evaluate(model, terms, values, seed=54)
+            _hold(f"ties {composition} planets {planets}", got, flags, want, valid)
+            res, var = model.residuals_batch(X)
+            i = int(np.flatnonzero(valid)[0])
+            suma = sum(v[i] ** 2 for k, v in values.items() if k.endswith("_sigma"))
+            S = np.diag(var[i]) + suma
+            plain = -0.5 * res[i] @ np.linalg.solve(S, res[i]) - 0.5 * np.linalg.slogdet(S)[1] - 0.5 * res.shape[1] * np.log(2 * np.pi)
+            assert cc.rel_err(got[i], plain) <= 1e-9             # (the columns' sum of a is sigma² to 1e-9 at the clamp)
