@@ -325,7 +325,7 @@ def load():
             f"or `make -C evidence_amd/csrc`. evidence_amd has no CPU fallback.")
     # The HIP runtime maps a process's streams onto GPU_MAX_HW_QUEUES hardware queues (default 4) and reads the variable when it
     # starts.  A handle has seven streams; when a copy stream of the streamed host batches shares the kernels' queue, every
-    # chunk's kernels wait for a download (csrc/rvll_api.hip, stream_reserve: 3.3 against 2.0 ms at 262144 rows).  The count
+    # chunk's kernels wait for a download (csrc/rvll_batch.hip, stream_reserve: 3.3 against 2.0 ms at 262144 rows).  The count
     # is the caller's choice: evidence_amd and librvll never set it, and results do not depend on it.
     global HW_QUEUES_NOTE
     hip_already = _hip_runtime_loaded()

@@ -61,8 +61,6 @@ int report_error(int code, const char* fmt, ...)
 }  // namespace rvll
 
 using rvll::host::dev_free;
-using rvll::host::kDownloadStagedMin;
-using rvll::host::kDeadStagedMin;
 
 namespace {
 
@@ -111,10 +109,6 @@ int server_stop(rvll_handle* h)
 }
 
 int resolve_fused(rvll_handle* h);
-void stream_free(rvll_handle* h);
-int download_rows(rvll_handle* h, void* dst, const void* src_dev, size_t bytes);
-// device -> pageable host copies from here on go through download_rows: arrays the caller makes per call (above glibc's mmap threshold
-// every array is a fresh mapping), and the dead points' one download per run into an array made for it
 
 int use_device(rvll_handle* h)
 {
@@ -527,7 +521,7 @@ int rvll_destroy(rvll_handle* h)
     if (h->pin_in) (void)hipHostFree(h->pin_in);
     if (h->pin_out) (void)hipHostFree(h->pin_out);
     if (h->pin_defer) (void)hipHostFree(h->pin_defer);
-    stream_free(h);
+    rvll::host::stream_free(h);
     dev_free(h->d_walk_steps); dev_free(h->d_walk_wid); dev_free(h->d_walk_start); dev_free(h->d_walk_cost); dev_free(h->d_walk_order); dev_free(h->d_walk_wflag);
     dev_free(h->d_walk_basis);
     dev_free(h->d_rounds); dev_free(h->d_walk_dirs);
@@ -686,49 +680,6 @@ int rvll_dev_reserve(rvll_handle* h, int64_t B)
     return ensure_capacity(h, B);
 }
 
-int rvll_dev_upload_theta(rvll_handle* h, const double* theta, int64_t B)
-{
-    int rc = rvll_dev_reserve(h, B);
-    if (rc) return rc;
-    if (B == 0) return RVLL_OK;
-    if (!theta) return fail(RVLL_E_INVALID, "theta is null");
-    const size_t nbytes = sizeof(double) * (size_t)B * (size_t)h->L.ndim;
-    rc = sync_other_lanes(h);                                       // other lanes may still be reading the old theta
-    if (rc) return rc;
-    if (nbytes <= rvll_handle::kPinBytes) {
-        // small: stage through pinned memory (a true asynchronous DMA; the caller's buffer is free at once,
-        // and every host-buffer call ends in a stream sync before the staging buffer is written again)
-        HIP_TRY(hipStreamSynchronize(h->compute));
-        memcpy(h->pin_in, theta, nbytes);
-        HIP_TRY(hipMemcpyAsync(h->d_theta, h->pin_in, nbytes, hipMemcpyHostToDevice, h->compute));
-        h->theta_async = true;
-        return RVLL_OK;
-    }
-    HIP_TRY(hipMemcpyAsync(h->d_theta, theta, nbytes, hipMemcpyHostToDevice, h->compute));
-    HIP_TRY(hipStreamSynchronize(h->compute));
-    return RVLL_OK;
-}
-
-int rvll_dev_upload_cube(rvll_handle* h, const double* cube, int64_t B)
-{
-    int rc = rvll_dev_reserve(h, B);
-    if (rc) return rc;
-    if (B == 0) return RVLL_OK;
-    if (!cube) return fail(RVLL_E_INVALID, "cube is null");
-    const size_t nbytes = sizeof(double) * (size_t)B * (size_t)h->L.ndim;
-    if (nbytes <= rvll_handle::kPinBytes) {
-        // small: stage through pinned memory (a true asynchronous DMA; the caller's buffer is free at once,
-        // and every host-buffer call ends in a stream sync before the staging buffer is written again)
-        HIP_TRY(hipStreamSynchronize(h->compute));
-        memcpy(h->pin_in, cube, nbytes);
-        HIP_TRY(hipMemcpyAsync(h->d_cube, h->pin_in, nbytes, hipMemcpyHostToDevice, h->compute));
-        return RVLL_OK;
-    }
-    HIP_TRY(hipMemcpyAsync(h->d_cube, cube, nbytes, hipMemcpyHostToDevice, h->compute));
-    HIP_TRY(hipStreamSynchronize(h->compute));
-    return RVLL_OK;
-}
-
 int rvll_dev_fill_cube(rvll_handle* h, int64_t B, uint64_t seed)
 {
     int rc = rvll_dev_reserve(h, B);
@@ -742,7 +693,7 @@ int rvll_dev_prior(rvll_handle* h, int64_t B)
     int rc = use_device(h);
     if (rc) return rc;
     if (!h->have_priors) return fail(RVLL_E_NOPRIORS, "rvll_set_priors has not been called");
-    if (B < 0 || B > h->cap) return fail(RVLL_E_INVALID, "B %lld outside reserved capacity %lld", (long long)B, h->cap);
+    RVLL_TRY(rvll::host::check_capacity(h, B));
     rc = sync_other_lanes(h);                                       // other lanes may still be reading the old theta
     if (rc) return rc;
     rvll::PriorArgs a{h->d_cube, h->d_theta, (long long)B, h->L.ndim, h->d_priors, h->d_heavy, h->n_heavy};
@@ -755,7 +706,7 @@ int rvll_dev_loglike(rvll_handle* h, int64_t B)
 {
     int rc = use_device(h);
     if (rc) return rc;
-    if (B < 0 || B > h->cap) return fail(RVLL_E_INVALID, "B %lld outside reserved capacity %lld", (long long)B, h->cap);
+    RVLL_TRY(rvll::host::check_capacity(h, B));
     if (B == 0) return RVLL_OK;
     const int lane = h->logl_cur;
     if (lane != 0 && h->theta_async) {        // theta was produced on lane 0's stream: order this lane behind it
@@ -785,7 +736,7 @@ int rvll_dev_prior_loglike(rvll_handle* h, int64_t B)
     int rc = use_device(h);
     if (rc) return rc;
     if (!h->have_priors) return fail(RVLL_E_NOPRIORS, "rvll_set_priors has not been called");
-    if (B < 0 || B > h->cap) return fail(RVLL_E_INVALID, "B %lld outside reserved capacity %lld", (long long)B, h->cap);
+    RVLL_TRY(rvll::host::check_capacity(h, B));
     if (B == 0) return RVLL_OK;
     // One launch (the prior transform in the log-L tile's staging step) needs every Beta / Gamma prior to have a
     // verified table (the slim stage); otherwise: the prior kernels, then the log-L kernel.
@@ -808,49 +759,6 @@ int rvll_dev_prior_loglike(rvll_handle* h, int64_t B)
     h->theta_async = true;
     h->logl_last = 0;
     h->fused_pending = B;                      // whoever touches the results next looks at the defer word first
-    return RVLL_OK;
-}
-
-int rvll_dev_download(rvll_handle* h, int64_t B, double* theta, double* logL, int32_t* flags)
-{
-    int rc = use_device(h);
-    if (rc) return rc;
-    if (B < 0 || B > h->cap) return fail(RVLL_E_INVALID, "B %lld outside reserved capacity %lld", (long long)B, h->cap);
-    if (h->logl_last != 0) HIP_TRY(hipStreamSynchronize(h->lanes[h->logl_last]));   // read through lane 0's stream
-    if (B > 0) {
-        const size_t nt = theta ? sizeof(double) * (size_t)B * (size_t)h->L.ndim : 0;
-        const size_t nl = logL ? sizeof(double) * (size_t)B : 0;
-        const size_t nf = flags ? sizeof(int32_t) * (size_t)B : 0;
-        if (nt + nl + nf <= rvll_handle::kPinBytes) {          // small: one pinned landing zone, one sync
-            char* p = static_cast<char*>(h->pin_out);
-            if (nt) HIP_TRY(hipMemcpyAsync(p, h->d_theta, nt, hipMemcpyDeviceToHost, h->compute));
-            if (nl) HIP_TRY(hipMemcpyAsync(p + nt, h->d_logL2[h->logl_last], nl, hipMemcpyDeviceToHost, h->compute));
-            if (nf) HIP_TRY(hipMemcpyAsync(p + nt + nl, h->d_flags2[h->logl_last], nf, hipMemcpyDeviceToHost, h->compute));
-            HIP_TRY(hipStreamSynchronize(h->compute));
-            if (nt) memcpy(theta, p, nt);
-            if (nl) memcpy(logL, p + nt, nl);
-            if (nf) memcpy(flags, p + nt + nl, nf);
-            return RVLL_OK;
-        }
-        if (theta) {
-            // A device-to-host copy into pageable memory runs at 50 GB/s once the runtime has pinned the destination
-            // range and cached that — which it cannot for a range it has never seen: 38 MB of theta into a fresh numpy
-            // array take 20-28 ms (1.5 GB/s), and numpy arrays above 32 MB are fresh mappings every time (glibc's mmap
-            // threshold stops growing there; below it the heap hands the same block out again and the copy is fast:
-            // profiles/r02_d2h_probe.txt).  Large downloads therefore go through pinned staging blocks, the workers
-            // copying chunk c to its place while chunks c + 1 .. c + 3 land (download_rows; round 2: two 1 MiB blocks on
-            // the calling thread, 6 ms for those 38 MB).
-            if (nt < kDownloadStagedMin) {
-                HIP_TRY(hipMemcpyAsync(theta, h->d_theta, nt, hipMemcpyDeviceToHost, h->compute));
-            } else {
-                rc = download_rows(h, theta, h->d_theta, nt);
-                if (rc) return rc;
-            }
-        }
-        if (logL)  HIP_TRY(hipMemcpyAsync(logL, h->d_logL2[h->logl_last], nl, hipMemcpyDeviceToHost, h->compute));
-        if (flags) HIP_TRY(hipMemcpyAsync(flags, h->d_flags2[h->logl_last], nf, hipMemcpyDeviceToHost, h->compute));
-    }
-    HIP_TRY(hipStreamSynchronize(h->compute));
     return RVLL_OK;
 }
 
@@ -910,7 +818,7 @@ int rvll_dev_time_loglike(rvll_handle* h, int64_t B, int32_t warmup, int32_t ite
     int rc = use_device(h);
     if (rc) return rc;
     if (!out || iters < 1 || warmup < 0) return fail(RVLL_E_INVALID, "bad timing arguments");
-    if (B < 1 || B > h->cap) return fail(RVLL_E_INVALID, "B %lld outside reserved capacity %lld", (long long)B, h->cap);
+    RVLL_TRY(rvll::host::check_capacity(h, B, 1));
     rvll::LoglikeArgs a;
     rc = sync_other_lanes(h);
     if (rc) return rc;
@@ -965,7 +873,7 @@ int rvll_dev_trace_loglike(rvll_handle* h, int64_t B, int32_t warmup, uint64_t* 
 {
     int rc = use_device(h);
     if (rc) return rc;
-    if (B < 1 || B > h->cap) return fail(RVLL_E_INVALID, "B %lld outside reserved capacity %lld", (long long)B, h->cap);
+    RVLL_TRY(rvll::host::check_capacity(h, B, 1));
     if (h->L.precision != RVLL_PREC_FP64) return fail(RVLL_E_UNSUPPORTED, "the trace kernel exists for fp64 only");
     rc = sync_other_lanes(h);
     if (rc) return rc;
@@ -995,7 +903,7 @@ int rvll_dev_trace_loglike(rvll_handle* h, int64_t B, int32_t warmup, uint64_t* 
     return status;
 }
 
-// ---- host-buffer hot calls -------------------------------------------------------
+// ---- the one-launch batch's deferral, the scalar-call server ------------------------------------
 }  // extern "C"
 
 namespace {
@@ -1089,243 +997,6 @@ int scalar_call(rvll_handle* h, unsigned op, const double* theta, double* logL, 
     return RVLL_OK;
 }
 
-
-// ---- large host batches: a pipeline of chunks, the host's copies on worker threads (round 3) --------------------------
-// A 262144-point cube -> theta -> log-L call moves 80 MB between the caller's pageable arrays and the device.  Through copy
-// commands on pageable memory that is ONE host thread at ~12 GB/s (the runtime's staging copy on the way up, ours — into a
-// freshly mapped result array, page faults included — on the way down): 6.5 ms around 1.2 ms of kernels (the
-// "cliff").  Here the batch goes in chunks of 16384 rows through pinned staging blocks: worker threads copy chunk c + 2 in
-// and chunk c - 1 out while the DMA engines and the kernels work on chunk c (uploads, kernels and downloads each on a stream of
-// their own, chained by events: the link carries both directions at once).
-// The same kernels on the same rows: the same bits (tests/test_gpu_boundary.py runs every size class).
-constexpr long long kStreamChunkRows = 16384;
-// Streamed from 24 MB of rows on (165565 points at 19 parameters).  Below, the two-chunk route copies straight from and to the
-// caller's arrays and is level or ahead (131072 rows: 1.04 - 1.08 ms against 1.0 - 1.2 ms); above, the caller's arrays are
-// fresh mappings every call (glibc's 32 MB mmap threshold), the runtime's cache of pinned ranges misses, and that route
-// collapses (262144 rows: 3.5 - 4.1 ms against 1.9 - 2.2 ms; profiles/r03_stream_probe.txt).  RVLL_STREAM_MIN (points): measurement switch.
-long long stream_min_points(const rvll_handle* h)
-{
-    if (const char* e = getenv("RVLL_STREAM_MIN")) return std::max(1ll, atoll(e));
-    return (long long)((kStreamMinBytes + sizeof(double) * (size_t)h->L.ndim - 1) / (sizeof(double) * (size_t)h->L.ndim));
-}
-
-void stream_free(rvll_handle* h)
-{
-    delete h->pool;
-    h->pool = nullptr;
-    for (int s = 0; s < kStageSlots; ++s) {
-        if (h->stage_in[s]) (void)hipHostFree(h->stage_in[s]);
-        if (h->stage_out[s]) (void)hipHostFree(h->stage_out[s]);
-        for (hipEvent_t* e : {&h->stage_ev[s], &h->stage_up[s], &h->stage_done[s]}) { if (*e) (void)hipEventDestroy(*e); *e = nullptr; }
-        h->stage_in[s] = h->stage_out[s] = nullptr;
-    }
-    if (h->stream_up) (void)hipStreamDestroy(h->stream_up);
-    if (h->stream_down) (void)hipStreamDestroy(h->stream_down);
-    h->stream_up = h->stream_down = nullptr;
-    h->stage_in_bytes = h->stage_out_bytes = 0;
-}
-
-// workers, events and staging blocks for chunks of `rows` rows (grown on demand, kept with the handle)
-int stream_reserve(rvll_handle* h, long long rows)
-{
-    const size_t D = (size_t)h->L.ndim;
-    const size_t in_bytes = sizeof(double) * D * (size_t)rows;
-    const size_t out_bytes = (sizeof(double) * (D + 1) + sizeof(int32_t)) * (size_t)rows;
-    if (!h->pool) {
-        // (2, 4 and 8 workers measure the same within the run-to-run spread — the GPU side of the pipeline is the longer one)
-        int n = (int)std::min(4u, std::max(2u, std::thread::hardware_concurrency() / 2));
-        if (const char* e = getenv("RVLL_COPY_THREADS")) n = std::max(1, std::min(32, atoi(e)));
-        try {
-            h->pool = new CopyPool(n);
-        } catch (const std::exception& e) {             // (no memory, or the system refuses more threads)
-            h->pool = nullptr;
-            return fail(RVLL_E_NOMEM, "cannot start %d copy workers: %s", n, e.what());
-        }
-    }
-    for (int s = 0; s < kStageSlots; ++s)
-        for (hipEvent_t* e : {&h->stage_ev[s], &h->stage_up[s], &h->stage_done[s]})
-            if (!*e) HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
-    if (!h->stream_up) {
-        // The runtime maps a process's streams onto GPU_MAX_HW_QUEUES hardware queues (default 4; this handle alone has seven
-        // streams), and a copy's completion marker holds up whatever else shares its queue.  When one of the two copy streams
-        // lands on the kernels' queue, every chunk's kernels wait for the previous chunk's download: 3.3 against 2.0 ms at
-        // 262144 rows — and which stream lands where depends on what the process has done before (inside bench.py streams made
-        // here collided and the handle's spare lanes did not; in the standalone probe it was the other way round; stream
-        // priorities changed nothing).  The queue count is the caller's choice (include/rvll.h, rvll_runtime_info); results
-        // are the same either way.
-        HIP_TRY(hipStreamCreateWithFlags(&h->stream_up, hipStreamNonBlocking));
-        HIP_TRY(hipStreamCreateWithFlags(&h->stream_down, hipStreamNonBlocking));
-    }
-    if (in_bytes > h->stage_in_bytes || out_bytes > h->stage_out_bytes) {
-        for (int s = 0; s < kStageSlots; ++s) {
-            if (h->stage_in[s]) (void)hipHostFree(h->stage_in[s]);
-            if (h->stage_out[s]) (void)hipHostFree(h->stage_out[s]);
-            h->stage_in[s] = h->stage_out[s] = nullptr;
-        }
-        h->stage_in_bytes = h->stage_out_bytes = 0;
-        for (int s = 0; s < kStageSlots; ++s) {
-            HIP_TRY(hipHostMalloc(&h->stage_in[s], in_bytes, hipHostMallocDefault));
-            HIP_TRY(hipHostMalloc(&h->stage_out[s], out_bytes, hipHostMallocDefault));
-        }
-        h->stage_in_bytes = in_bytes;
-        h->stage_out_bytes = out_bytes;
-    }
-    return RVLL_OK;
-}
-
-// A large device array into the caller's pageable memory: chunks through the pinned staging blocks on the download stream, up to
-// three in flight, each copied on to its place by the workers as it lands (a copy command straight into pageable memory runs
-// at 50 GB/s into a range the runtime has pinned and cached, at 1.5 - 7 GB/s into one it has never seen — and a result array
-// usually is one; round 2 staged through two 1 MiB blocks on the calling thread: 6 ms for 38 MB).  Work queued on lane 0's
-// stream before the call is waited for first.
-int download_rows(rvll_handle* h, void* dst, const void* src_dev, size_t bytes)
-{
-    if (!bytes) return RVLL_OK;
-    int rc = stream_reserve(h, kStreamChunkRows);
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(h->compute));
-    const size_t chunk = h->stage_out_bytes & ~(size_t)4095;
-    const int n = (int)((bytes + chunk - 1) / chunk);
-    CopyPool& pool = *h->pool;
-    CopyPool::Ticket tout[kStageSlots];
-    char* to = static_cast<char*>(dst);
-    const char* from = static_cast<const char*>(src_dev);
-    auto settle = [&](int code) {
-        for (int s = 0; s < kStageSlots; ++s) CopyPool::wait(&tout[s]);
-        (void)hipStreamSynchronize(h->stream_down);
-        pool.busy(false);
-        return code;
-    };
-#define DOWN_TRY(expr) do { const hipError_t err_ = (expr); if (err_ != hipSuccess) { settle(0); HIP_TRY(err_); } } while (0)
-    auto fetch = [&](int c) -> hipError_t {
-        const int s = c % kStageSlots;
-        const size_t off = (size_t)c * chunk;
-        hipError_t e = hipMemcpyAsync(h->stage_out[s], from + off, std::min(chunk, bytes - off), hipMemcpyDeviceToHost, h->stream_down);
-        return e != hipSuccess ? e : hipEventRecord(h->stage_ev[s], h->stream_down);
-    };
-    pool.busy(true);
-    for (int c = 0; c < std::min(n, kStageSlots - 1); ++c) DOWN_TRY(fetch(c));
-    for (int c = 0; c < n; ++c) {
-        const int s = c % kStageSlots;
-        const size_t off = (size_t)c * chunk;
-        DOWN_TRY(hipEventSynchronize(h->stage_ev[s]));
-        pool.copy(to + off, h->stage_out[s], std::min(chunk, bytes - off), &tout[s]);
-        const int next = c + kStageSlots - 1;               // its block held chunk c - 1: wait until the workers have emptied it
-        if (next < n) {
-            CopyPool::wait(&tout[next % kStageSlots]);
-            DOWN_TRY(fetch(next));
-        }
-    }
-#undef DOWN_TRY
-    return settle(RVLL_OK);
-}
-
-// rows of `in` (unit-cube rows if in_is_cube, else theta rows) -> [theta_out], logL, [flags], all host arrays of B rows
-int stream_host_batch(rvll_handle* h, const double* in, bool in_is_cube, int64_t B, double* theta_out, double* logL, int32_t* flags)
-{
-    long long rows = kStreamChunkRows;
-    if (const char* e = getenv("RVLL_STREAM_CHUNK")) rows = std::max(256, atoi(e));      // measurement switch
-    int rc = rvll_dev_reserve(h, B);
-    if (rc) return rc;
-    rc = sync_other_lanes(h);
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(h->compute));
-    rc = stream_reserve(h, rows);
-    if (rc) return rc;
-    const long long D = h->L.ndim;
-    const int n = (int)((B + rows - 1) / rows);
-    CopyPool& pool = *h->pool;
-    CopyPool::Ticket tin[kStageSlots], tout[kStageSlots];
-    auto lo_of = [&](int c) { return (long long)c * rows; };
-    auto hi_of = [&](int c) { return std::min<long long>(B, (long long)(c + 1) * rows); };
-    auto copy_in = [&](int c) {
-        if (c < n) pool.copy(h->stage_in[c % kStageSlots], in + lo_of(c) * D, sizeof(double) * (size_t)((hi_of(c) - lo_of(c)) * D), &tin[c % kStageSlots]);
-    };
-    auto copy_out = [&](int c) {
-        const long long lo = lo_of(c), m = hi_of(c) - lo;
-        const char* so = static_cast<const char*>(h->stage_out[c % kStageSlots]);
-        CopyPool::Ticket* t = &tout[c % kStageSlots];
-        if (theta_out) pool.copy(theta_out + lo * D, so, sizeof(double) * (size_t)(m * D), t);
-        pool.copy(logL + lo, so + sizeof(double) * (size_t)(rows * D), sizeof(double) * (size_t)m, t);
-        if (flags) pool.copy(flags + lo, so + sizeof(double) * (size_t)(rows * (D + 1)), sizeof(int32_t) * (size_t)m, t);
-    };
-    hipStream_t s_up = h->stream_up, s_down = h->stream_down;
-    int lag = 2;    // the calling thread runs this many chunks ahead of the results it waits for (1: the next chunk's commands were
-                    // issued only when the last-but-one's results had landed, and the kernels waited for that: 2.3 -> 1.8 ms at 262144 rows)
-    if (const char* e = getenv("RVLL_STREAM_LAG")) lag = std::max(1, std::min(2, atoi(e)));   // measurement switch
-    // whatever happens, leave with no copy in flight into or out of the caller's arrays and the workers asleep
-    auto settle = [&](int code) {
-        for (int s = 0; s < kStageSlots; ++s) { CopyPool::wait(&tin[s]); CopyPool::wait(&tout[s]); }
-        (void)hipStreamSynchronize(s_up);
-        (void)hipStreamSynchronize(h->compute);
-        (void)hipStreamSynchronize(s_down);
-        pool.busy(false);
-        return code;
-    };
-#define STREAM_TRY(expr) do { const hipError_t err_ = (expr); if (err_ != hipSuccess) { settle(0); HIP_TRY(err_); } } while (0)
-    const bool timing = getenv("RVLL_STREAM_TIMING") != nullptr;                          // measurement switch: where the calling thread waits
-    double waited[4] = {0., 0., 0., 0.};
-    auto now = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t_start = timing ? now() : 0.;
-    pool.busy(true);
-    copy_in(0);
-    copy_in(1);
-    double* dev_in = in_is_cube ? h->d_cube : h->d_theta;
-    for (int c = 0; c < n; ++c) {
-        const int s = c % kStageSlots;
-        const long long lo = lo_of(c), m = hi_of(c) - lo;
-        double t0 = timing ? now() : 0.;
-        CopyPool::wait(&tin[s]);                            // the chunk's rows are in their pinned block ...
-        if (timing) { const double t1 = now(); waited[0] += t1 - t0; t0 = t1; }
-        CopyPool::wait(&tout[s]);                           // ... and the results of the chunk that used the block before are out of theirs
-        if (timing) { const double t1 = now(); waited[1] += t1 - t0; t0 = t1; }
-        // up | kernels | down on three streams, so that chunk c + 1 comes up and chunk c - 1 goes down (the link is full duplex)
-        // under the kernels of chunk c
-        STREAM_TRY(hipMemcpyAsync(dev_in + lo * D, h->stage_in[s], sizeof(double) * (size_t)(m * D), hipMemcpyHostToDevice, s_up));
-        STREAM_TRY(hipEventRecord(h->stage_up[s], s_up));
-        STREAM_TRY(hipStreamWaitEvent(h->compute, h->stage_up[s], 0));
-        if (in_is_cube) {
-            rvll::PriorArgs pa{h->d_cube + lo * D, h->d_theta + lo * D, m, h->L.ndim, h->d_priors, h->d_heavy, h->n_heavy};
-            STREAM_TRY(rvll::launch_prior(pa, h->compute));
-        }
-        rvll::LoglikeArgs a;
-        int cu = 0;
-        rc = build_args(h, h->d_theta + lo * D, h->d_logL2[0] + lo, h->d_flags2[0] + lo, m, &a, &cu);
-        if (rc) return settle(rc);
-        STREAM_TRY(launch_form(a, cu, h->compute));
-        STREAM_TRY(hipEventRecord(h->stage_done[s], h->compute));
-        STREAM_TRY(hipStreamWaitEvent(s_down, h->stage_done[s], 0));
-        char* so = static_cast<char*>(h->stage_out[s]);
-        hipStream_t st = s_down;
-        if (theta_out) STREAM_TRY(hipMemcpyAsync(so, h->d_theta + lo * D, sizeof(double) * (size_t)(m * D), hipMemcpyDeviceToHost, st));
-        STREAM_TRY(hipMemcpyAsync(so + sizeof(double) * (size_t)(rows * D), h->d_logL2[0] + lo, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, st));
-        if (flags) STREAM_TRY(hipMemcpyAsync(so + sizeof(double) * (size_t)(rows * (D + 1)), h->d_flags2[0] + lo, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost, st));
-        STREAM_TRY(hipEventRecord(h->stage_ev[s], st));
-        if (timing) { const double t1 = now(); waited[2] += t1 - t0; t0 = t1; }
-        if (c >= lag) {
-            STREAM_TRY(hipEventSynchronize(h->stage_ev[(c - lag) % kStageSlots]));
-            if (timing) { const double t1 = now(); waited[3] += t1 - t0; t0 = t1; }
-            copy_out(c - lag);
-        }
-        copy_in(c + 2);     // (its block was last read by the upload of chunk c - 2, whose event has been waited for)
-    }
-    for (int c = std::max(0, n - lag); c < n; ++c) {
-        STREAM_TRY(hipEventSynchronize(h->stage_ev[c % kStageSlots]));
-        copy_out(c);
-    }
-#undef STREAM_TRY
-    h->theta_async = false;
-    h->logl_last = 0;
-    if (timing) {
-        const double t1 = now();
-        settle(0);
-        fprintf(stderr, "stream %lld rows, %d chunks, %d workers: %.0f us to the last event, %.0f us in all; waited for rows in %.0f, results out %.0f, "
-                "issue %.0f, events %.0f us\n", (long long)B, n, pool.size(), t1 - t_start, now() - t_start, waited[0], waited[1], waited[2], waited[3]);
-        return RVLL_OK;
-    }
-    return settle(RVLL_OK);
-}
-
 }  // namespace
 
 extern "C" {
@@ -1339,254 +1010,6 @@ int rvll_scalar_server(rvll_handle* h, int32_t enable)
     h->srv_enabled = enable != 0;
     return RVLL_OK;
 }
-
-int rvll_loglike_batch(rvll_handle* h, const double* theta, int64_t B, double* logL, int32_t* flags)
-{
-    if (!h) return fail(RVLL_E_INVALID, "null handle");
-    if (B == 1 && h->srv_enabled && theta && logL)
-        return scalar_call(h, getenv("RVLL_SERVER_NOOP") ? rvll::kServerNoop : rvll::kServerLogLike, theta, logL, flags, nullptr);
-    if (B < 0) return fail(RVLL_E_INVALID, "B < 0");
-    if (B == 0) return use_device(h);
-    if (!theta || !logL) return fail(RVLL_E_INVALID, "theta/logL is null");
-    const size_t nin = sizeof(double) * (size_t)B * (size_t)h->L.ndim;
-    const size_t nout = (sizeof(double) + sizeof(int32_t)) * (size_t)B;
-    // theta rows that fit the pinned block (6898 points at 19 parameters) go there by memcpy and are read by the kernel
-    // over PCIe: 10 us less than an upload command at 512 .. 4096 points (RVLL_ZERO_COPY_IN_KB: measurement switch)
-    size_t zc_in_max = rvll_handle::kPinBytes;
-    if (const char* e = getenv("RVLL_ZERO_COPY_IN_KB")) zc_in_max = std::min((size_t)std::max(0, atoi(e)) * 1024, rvll_handle::kPinBytes);
-    if (nin <= zc_in_max && nout <= rvll_handle::kPinBytes) {
-        // scalar / small-batch callback: zero-copy.  The kernel reads theta straight from mapped pinned host
-        // memory and writes log-L and flags back into it — no copy commands, one launch, one sync.
-        int rc = use_device(h);
-        if (rc) return rc;
-        HIP_TRY(hipStreamSynchronize(h->compute));
-        memcpy(h->pin_in, theta, nin);
-        double* out_l = static_cast<double*>(h->pin_out_dev);
-        int32_t* out_f = reinterpret_cast<int32_t*>(out_l + B);
-        rvll::LoglikeArgs a;
-        int cu = 0;
-        rc = build_args(h, static_cast<const double*>(h->pin_in_dev), out_l, out_f, B, &a, &cu);
-        if (rc) return rc;
-        HIP_TRY(launch_form(a, cu, h->compute));
-        HIP_TRY(hipStreamSynchronize(h->compute));
-        memcpy(logL, h->pin_out, sizeof(double) * (size_t)B);
-        if (flags) memcpy(flags, static_cast<char*>(h->pin_out) + sizeof(double) * (size_t)B, sizeof(int32_t) * (size_t)B);
-        return RVLL_OK;
-    }
-    // (theta -> log-L has no large download: the runtime's own staged upload from pageable memory is as fast as ours and the
-    //  chunked route below wins at every size, fresh arrays or kept ones — profiles/r03_stream_probe.txt; streamed only by switch)
-    if (getenv("RVLL_STREAM_LOGLIKE") && B >= stream_min_points(h)) return stream_host_batch(h, theta, false, B, nullptr, logL, flags);
-    int nsplit = B >= kSplitMinPoints ? (int)std::min<long long>(kSplitMaxChunks, std::max<long long>(2, B / kSplitChunkPoints)) : 1;
-    if (const char* e = getenv("RVLL_SPLIT")) nsplit = std::max(1, std::min(64, atoi(e)));   // measurement switch
-    if (nsplit > 1 && B >= 2 * nsplit) {
-        // Large host batch: chunks alternate between two streams.  A copy from pageable memory occupies the
-        // calling thread while the runtime stages it, so the upload of chunk i+1 overlaps the kernel of chunk i;
-        // all chunks write into the same log-L / flags buffers and come back with one download.
-        int rc = rvll_dev_reserve(h, B);
-        if (rc) return rc;
-        rc = sync_other_lanes(h);
-        if (rc) return rc;
-        HIP_TRY(hipStreamSynchronize(h->compute));
-        const long long D = h->L.ndim;
-        // on an error in the middle of the loop, copies from the caller's buffers may still be in flight on either
-        // stream: wait for both before handing the buffers back
-        auto settle = [&]() { (void)hipStreamSynchronize(h->lanes[0]); (void)hipStreamSynchronize(h->lanes[1]); };
-        // results that fit the pinned block leave the kernels as stores into mapped host memory (as in the small-batch
-        // path): no download commands behind the last kernel, one memcpy on the host
-        const bool out_pinned = nout <= rvll_handle::kPinBytes && !getenv("RVLL_NO_PINNED_OUT");
-        double* out_l = out_pinned ? static_cast<double*>(h->pin_out_dev) : h->d_logL2[0];
-        int32_t* out_f = out_pinned ? reinterpret_cast<int32_t*>(static_cast<double*>(h->pin_out_dev) + B) : h->d_flags2[0];
-        for (int c = 0; c < nsplit; ++c) {
-            const long long lo = B * c / nsplit, hi = B * (c + 1) / nsplit;
-            hipStream_t st = h->lanes[c & 1];
-            { const hipError_t err_ = hipMemcpyAsync(h->d_theta + lo * D, theta + lo * D, sizeof(double) * (size_t)((hi - lo) * D),
-                                                     hipMemcpyHostToDevice, st);
-              if (err_ != hipSuccess) { settle(); HIP_TRY(err_); } }
-            rvll::LoglikeArgs a;
-            int cu = 0;
-            rc = build_args(h, h->d_theta + lo * D, out_l + lo, out_f + lo, hi - lo, &a, &cu);
-            if (rc) { settle(); return rc; }
-            { const hipError_t err_ = launch_form(a, cu, st); if (err_ != hipSuccess) { settle(); HIP_TRY(err_); } }
-        }
-        HIP_TRY(hipStreamSynchronize(h->lanes[1]));
-        h->theta_async = false;
-        h->logl_last = 0;
-        if (!out_pinned) return rvll_dev_download(h, B, nullptr, logL, flags);
-        HIP_TRY(hipStreamSynchronize(h->lanes[0]));
-        memcpy(logL, h->pin_out, sizeof(double) * (size_t)B);
-        if (flags) memcpy(flags, static_cast<char*>(h->pin_out) + sizeof(double) * (size_t)B, sizeof(int32_t) * (size_t)B);
-        return RVLL_OK;
-    }
-    if (nout <= rvll_handle::kPinBytes && !getenv("RVLL_NO_PINNED_OUT")) {
-        // one upload, one launch whose results are stores into mapped pinned host memory, one synchronisation
-        int rc = rvll_dev_reserve(h, B);
-        if (rc) return rc;
-        rc = sync_other_lanes(h);
-        if (rc) return rc;
-        HIP_TRY(hipStreamSynchronize(h->compute));     // the pinned block may still be read by an earlier call's copy
-        HIP_TRY(hipMemcpyAsync(h->d_theta, theta, nin, hipMemcpyHostToDevice, h->compute));
-        double* out_l = static_cast<double*>(h->pin_out_dev);
-        rvll::LoglikeArgs a;
-        int cu = 0;
-        rc = build_args(h, h->d_theta, out_l, reinterpret_cast<int32_t*>(out_l + B), B, &a, &cu);
-        if (rc) { (void)hipStreamSynchronize(h->compute); return rc; }
-        { const hipError_t err_ = launch_form(a, cu, h->compute); if (err_ != hipSuccess) { (void)hipStreamSynchronize(h->compute); HIP_TRY(err_); } }
-        HIP_TRY(hipStreamSynchronize(h->compute));
-        h->theta_async = false;
-        memcpy(logL, h->pin_out, sizeof(double) * (size_t)B);
-        if (flags) memcpy(flags, static_cast<char*>(h->pin_out) + sizeof(double) * (size_t)B, sizeof(int32_t) * (size_t)B);
-        return RVLL_OK;
-    }
-    int rc = rvll_dev_upload_theta(h, theta, B);
-    if (rc) return rc;
-    rc = rvll_dev_loglike(h, B);
-    if (rc) return rc;
-    return rvll_dev_download(h, B, nullptr, logL, flags);
-}
-
-int rvll_prior_batch(rvll_handle* h, const double* cube, int64_t B, double* theta)
-{
-    if (!h) return fail(RVLL_E_INVALID, "null handle");
-    if (B < 0) return fail(RVLL_E_INVALID, "B < 0");
-    if (h && !h->have_priors) return fail(RVLL_E_NOPRIORS, "rvll_set_priors has not been called");
-    if (B == 1 && h->srv_enabled && cube && theta) return scalar_call(h, rvll::kServerPrior, cube, nullptr, nullptr, theta);
-    if (B == 0) return use_device(h);
-    if (!cube || !theta) return fail(RVLL_E_INVALID, "cube/theta is null");
-    const size_t nrow = sizeof(double) * (size_t)B * (size_t)h->L.ndim;
-    if (nrow <= 384 * 1024 && !getenv("RVLL_NO_PINNED_OUT")) {
-        // a vectorized prior callback of up to 2586 points (19 parameters; beyond, the two host memcpys cost more than they save): the prior kernels read the cube from and write
-        // theta to mapped pinned host memory — no copy command in either direction
-        int rc = use_device(h);
-        if (rc) return rc;
-        HIP_TRY(hipStreamSynchronize(h->compute));
-        memcpy(h->pin_in, cube, nrow);
-        rvll::PriorArgs a{static_cast<const double*>(h->pin_in_dev), static_cast<double*>(h->pin_out_dev), (long long)B,
-                          h->L.ndim, h->d_priors, h->d_heavy, h->n_heavy};
-        HIP_TRY(rvll::launch_prior(a, h->compute));
-        HIP_TRY(hipStreamSynchronize(h->compute));
-        memcpy(theta, h->pin_out, nrow);
-        return RVLL_OK;
-    }
-    int rc = rvll_dev_upload_cube(h, cube, B);
-    if (rc) return rc;
-    rc = rvll_dev_prior(h, B);
-    if (rc) return rc;
-    return rvll_dev_download(h, B, theta, nullptr, nullptr);
-}
-
-int rvll_prior_loglike_batch(rvll_handle* h, const double* cube, int64_t B,
-                             double* theta_out, double* logL, int32_t* flags)
-{
-    if (!h) return fail(RVLL_E_INVALID, "null handle");
-    if (B < 0) return fail(RVLL_E_INVALID, "B < 0");
-    if (h && !h->have_priors) return fail(RVLL_E_NOPRIORS, "rvll_set_priors has not been called");
-    if (B == 0) return use_device(h);
-    if (!cube || !logL) return fail(RVLL_E_INVALID, "cube/logL is null");
-    if (B == 1 && h->srv_enabled)             // the scalar pair prior(cube) + loglike(theta) as ONE request of the server
-        return scalar_call(h, rvll::kServerPriorLogLike, cube, logL, flags, theta_out);
-    const size_t nin = sizeof(double) * (size_t)B * (size_t)h->L.ndim;
-    const size_t nout = (sizeof(double) + sizeof(int32_t)) * (size_t)B;
-    if (nin + nout + 16 <= rvll_handle::kPinBytes && h->all_direct && !getenv("RVLL_NO_PINNED_OUT")) {
-        // a sampler's proposal round (up to 6393 points at 19 parameters): the fused kernel reads the cube from mapped
-        // pinned host memory and stores theta, log-L and flags into it — no copy command in either direction
-        int rc = rvll_dev_reserve(h, B);
-        if (rc) return rc;
-        HIP_TRY(hipStreamSynchronize(h->compute));
-        memcpy(h->pin_in, cube, nin);
-        rc = sync_other_lanes(h);
-        if (rc) return rc;
-        double* out_l = static_cast<double*>(h->pin_out_dev);
-        int32_t* out_f = reinterpret_cast<int32_t*>(out_l + B);
-        rvll::LoglikeArgs a;
-        rc = build_args(h, h->d_theta, out_l, out_f, B, &a);
-        if (rc) return rc;
-        // (flags end on a multiple of 4 bytes; theta starts on the next multiple of 16)
-        const size_t theta_off = (nout + 15) & ~(size_t)15;
-        if (theta_off + nin > rvll_handle::kPinBytes) return fail(RVLL_E_INVALID, "pinned block too small");
-        make_fused(h, static_cast<const double*>(h->pin_in_dev),
-                   reinterpret_cast<double*>(static_cast<char*>(h->pin_out_dev) + theta_off), &a);
-        *h->pin_defer = 0;
-        HIP_TRY(rvll::launch_prior_loglike(a, h->compute));
-        char* host_out = static_cast<char*>(h->pin_out);
-        HIP_TRY(hipStreamSynchronize(h->compute));
-        if (__atomic_load_n(h->pin_defer, __ATOMIC_ACQUIRE) != 0) {
-            // an element fell outside the slim stage's tables (rvll_tile.h): the full prior kernels take the batch
-            *h->pin_defer = 0;
-            rc = rvll_dev_upload_cube(h, cube, B);
-            if (rc) return rc;
-            rc = rvll_dev_prior(h, B);
-            if (rc) return rc;
-            h->logl_cur = 0;
-            rc = rvll_dev_loglike(h, B);
-            if (rc) return rc;
-            return rvll_dev_download(h, B, theta_out, logL, flags);
-        }
-        memcpy(logL, host_out, sizeof(double) * (size_t)B);
-        if (flags) memcpy(flags, host_out + sizeof(double) * (size_t)B, sizeof(int32_t) * (size_t)B);
-        if (theta_out) memcpy(theta_out, host_out + theta_off, nin);
-        return RVLL_OK;
-    }
-    if (B >= stream_min_points(h)) return stream_host_batch(h, cube, true, B, theta_out, logL, flags);
-    // measured (profiles/r01_split_probe.txt): two halves help from 16384 points (+15 %) to 65536 (+35 %); more chunks
-    // lose to the per-copy fixed costs, and at 262144 points the large pageable downloads on two streams collapse
-    int nsplit = (B >= kSplitMinPoints && B <= 131072) ? 2 : 1;
-    if (const char* e = getenv("RVLL_SPLIT")) nsplit = std::max(1, std::min(64, atoi(e)));   // measurement switch
-    if (nsplit > 1 && B >= 2 * nsplit) {
-        // Large host batch: chunks alternate between two streams, software-pipelined by one chunk.  Copies from /
-        // to pageable memory occupy the calling thread, so while it stages the upload of chunk c+1 and the
-        // download of chunk c-1, the GPU runs the kernels of chunk c.
-        int rc = rvll_dev_reserve(h, B);
-        if (rc) return rc;
-        rc = sync_other_lanes(h);
-        if (rc) return rc;
-        HIP_TRY(hipStreamSynchronize(h->compute));
-        const long long D = h->L.ndim;
-        auto bounds = [&](int c, long long* lo, long long* hi) { *lo = B * c / nsplit; *hi = B * (c + 1) / nsplit; };
-        // an error in the middle leaves copies to / from the caller's buffers in flight: settle both streams first
-        auto settle = [&](int code) { (void)hipStreamSynchronize(h->lanes[0]); (void)hipStreamSynchronize(h->lanes[1]); return code; };
-#define SPLIT_TRY(expr) do { const hipError_t err_ = (expr); if (err_ != hipSuccess) { settle(0); HIP_TRY(err_); } } while (0)
-        auto fetch = [&](int c) -> int {
-            long long lo, hi;
-            bounds(c, &lo, &hi);
-            hipStream_t st = h->lanes[c & 1];
-            if (theta_out) SPLIT_TRY(hipMemcpyAsync(theta_out + lo * D, h->d_theta + lo * D, sizeof(double) * (size_t)((hi - lo) * D), hipMemcpyDeviceToHost, st));
-            SPLIT_TRY(hipMemcpyAsync(logL + lo, h->d_logL2[0] + lo, sizeof(double) * (size_t)(hi - lo), hipMemcpyDeviceToHost, st));
-            if (flags) SPLIT_TRY(hipMemcpyAsync(flags + lo, h->d_flags2[0] + lo, sizeof(int32_t) * (size_t)(hi - lo), hipMemcpyDeviceToHost, st));
-            return RVLL_OK;
-        };
-        for (int c = 0; c < nsplit; ++c) {
-            long long lo, hi;
-            bounds(c, &lo, &hi);
-            hipStream_t st = h->lanes[c & 1];
-            SPLIT_TRY(hipMemcpyAsync(h->d_cube + lo * D, cube + lo * D, sizeof(double) * (size_t)((hi - lo) * D), hipMemcpyHostToDevice, st));
-            rvll::PriorArgs pa{h->d_cube + lo * D, h->d_theta + lo * D, hi - lo, h->L.ndim, h->d_priors, h->d_heavy, h->n_heavy};
-            SPLIT_TRY(rvll::launch_prior(pa, st));
-            rvll::LoglikeArgs a;
-            int cu = 0;
-            rc = build_args(h, h->d_theta + lo * D, h->d_logL2[0] + lo, h->d_flags2[0] + lo, hi - lo, &a, &cu);
-            if (rc) return settle(rc);
-            SPLIT_TRY(launch_form(a, cu, st));
-            if (c > 0) { rc = fetch(c - 1); if (rc) return settle(rc); }
-        }
-        rc = fetch(nsplit - 1);
-        if (rc) return settle(rc);
-#undef SPLIT_TRY
-        HIP_TRY(hipStreamSynchronize(h->compute));
-        HIP_TRY(hipStreamSynchronize(h->lanes[1]));
-        h->theta_async = false;
-        h->logl_last = 0;
-        return RVLL_OK;
-    }
-    int rc = rvll_dev_upload_cube(h, cube, B);
-    if (rc) return rc;
-    // measured (profiles/r01_fused_probe.txt): one launch saves ~1 us up to a few thousand points; beyond that
-    // the separate prior kernels win by ~5 % because their work spreads over the whole chip instead of
-    // running as a short serial prologue of every log-L workgroup
-    rc = rvll_dev_prior_loglike(h, B);
-    if (rc) return rc;
-    return rvll_dev_download(h, B, theta_out, logL, flags);
-}
-
 
 int rvll_set_wander_exact(rvll_handle* h, int32_t on)
 {
@@ -1734,6 +1157,10 @@ int build_args(rvll_handle* h, const double* d_theta, double* d_logL, int32_t* d
     return ::build_args(h, d_theta, d_logL, d_flags, B, out, cu_grid);
 }
 void make_fused(const rvll_handle* h, const double* d_cube, double* d_theta_out, rvll::LoglikeArgs* a) { ::make_fused(h, d_cube, d_theta_out, a); }
-int download_rows(rvll_handle* h, void* dst, const void* src_dev, size_t bytes) { return ::download_rows(h, dst, src_dev, bytes); }
+hipError_t launch_form(const rvll::LoglikeArgs& a, int cu_grid, hipStream_t stream) { return ::launch_form(a, cu_grid, stream); }
+int scalar_call(rvll_handle* h, unsigned op, const double* theta, double* logL, int32_t* flags, double* theta_out)
+{
+    return ::scalar_call(h, op, theta, logL, flags, theta_out);
+}
 }  // namespace host
 }  // namespace rvll

@@ -1,5 +1,5 @@
 // Worker threads for the HOST side of large host-buffer calls: the copies between the caller's pageable arrays and the pinned
-// staging blocks (rvll_api.hip, stream_host_batch and download_rows).  Plain C++17, no HIP: tests/test_copypool_native.py runs
+// staging blocks (rvll_batch.hip, stream_host_batch and download_rows).  Plain C++17, no HIP: tests/test_copypool_native.py runs
 // it on the CPU under ThreadSanitizer and AddressSanitizer.
 //
 // One pool per handle, made by the first call that needs it.  The workers sleep on a condition variable between calls; while

@@ -1,7 +1,9 @@
 // rvll_host.h — what the host-side translation units of librvll.so share: the handle behind the C-ABI's opaque
 // pointer, the error macro, and the helpers of rvll_api.hip the other units call.  Internal; not part of the ABI.
-//   rvll_api.hip        the ABI core: create / destroy, priors, resident and host-buffer batch calls, scalar-call server,
-//                       streamed host batches, curves, self tests
+//   rvll_api.hip        the ABI core: create / destroy, priors, launch geometry, resident batch calls, scalar-call server, curves,
+//                       self tests
+//   rvll_batch.hip      the host-buffer batch calls and their transports, streamed host batches, resident uploads and download
+//   rvll_batch_route.h  which transport a host-buffer call takes and where its bytes lie: arithmetic without a HIP call
 //   rvll_walk_host.hip  the sampler's proposal step: the device walk in its forms (rvll_slice_walk*)
 //   rvll_live_host.hip  the resident live set and ensemble (rvll_live_*, rvll_live_runs_*): the stages of a resident step
 //   rvll_step_groups.h  the walker groups of a resident ensemble step: index arithmetic without a HIP call
@@ -27,6 +29,7 @@
 #pragma GCC visibility pop
 #include "rvll_kernels.h"
 #include "rvll_copypool.h"
+#include "rvll_batch_route.h"   // kPinBytes, kSplit*, kStream*, kDownloadStagedMin
 
 namespace rvll {
 // sets the thread's last-error string (rvll_last_error) and returns `code`
@@ -57,10 +60,7 @@ void dev_free(T*& p) { if (p) { (void)hipFree(p); p = nullptr; } }
 }  // namespace rvll
 
 constexpr int kMaxLanes = 4;
-// rvll_loglike_batch: host batches from kSplitMinPoints on go up in overlapped chunks of about kSplitChunkPoints
-constexpr long long kSplitMinPoints = 16384, kSplitChunkPoints = 16384, kSplitMaxChunks = 8;   // profiles/r02_split_probe.txt
 constexpr int kWalkWords = 14;                // counters of the walk kernel: calls, tile slots, 4 phase bins + workgroups + longest life + 4 tile phases (diagnostic build), the queue
-constexpr size_t kStreamMinBytes = 24u << 20;   // cube -> theta -> log-L host batches whose rows take this much are streamed (stream_host_batch)
 constexpr long long kFusedMaxPoints = 4096;   // rvll_prior_loglike_batch: one launch up to here, two beyond
 
 using rvll::CopyPool;
@@ -120,7 +120,7 @@ struct rvll_handle {
     int32_t* d_flags2[kMaxLanes] = {};          // per lane, like log-L
 
     // pinned host staging for small transfers (scalar / small-batch callbacks)
-    static constexpr size_t kPinBytes = 1u << 20;
+    static constexpr size_t kPinBytes = ::kPinBytes;
     void* pin_in = nullptr;
     void* pin_out = nullptr;
     void* pin_in_dev = nullptr;      // device-visible aliases of the two pinned buffers (zero-copy path)
@@ -282,7 +282,18 @@ int sync_other_lanes(rvll_handle* h);
 int build_args(rvll_handle* h, const double* d_theta, double* d_logL, int32_t* d_flags, long long B, rvll::LoglikeArgs* out,
                int* cu_grid = nullptr);
 void make_fused(const rvll_handle* h, const double* d_cube, double* d_theta_out, rvll::LoglikeArgs* a);
-int download_rows(rvll_handle* h, void* dst, const void* src_dev, size_t bytes);
+hipError_t launch_form(const rvll::LoglikeArgs& a, int cu_grid, hipStream_t stream);   // the tile form, or the CU-wide form on cu_grid > 0 workgroups
+// one request through the scalar-call server (started on demand): op is a kServer* request of rvll_kernels.h
+int scalar_call(rvll_handle* h, unsigned op, const double* theta, double* logL, int32_t* flags, double* theta_out);
+// a batch size of the device-resident forms: least .. reserved capacity
+inline int check_capacity(const rvll_handle* h, long long B, long long least = 0)
+{
+    if (B >= least && B <= h->cap) return RVLL_OK;
+    return report_error(RVLL_E_INVALID, "B %lld outside reserved capacity %lld", B, h->cap);
+}
+// rvll_batch.hip
+int download_rows(rvll_handle* h, void* dst, const void* src_dev, size_t bytes);   // a large device array into pageable host memory
+void stream_free(rvll_handle* h);                   // the copy workers, staging blocks, events and streams of the streamed transports
 void comm_release(rvll_handle* h);                  // rvll_comm.hip: destroy the handle's communicators
 // rvll_cluster_host.hip: the clustering's device blocks (d_cl_in: cube, scale, run_start, seeds, block table; d_cl_work: forest,
 // per-run maxima; d_cl_out: radius2, nclusters, labels) and its core on inputs already there (asynchronous)
@@ -312,7 +323,7 @@ inline unsigned long long wrapped_mask(const int32_t* wrapped, int D)
     if (wrapped) for (int d = 0; d < D && d < 64; ++d) if (wrapped[d]) m |= 1ull << d;
     return m;
 }
-constexpr size_t kDownloadStagedMin = 32u << 20, kDeadStagedMin = 8u << 20;
+constexpr size_t kDeadStagedMin = 8u << 20;
 
 // rvll_walk_host.hip: what the resident live set (rvll_live_host.hip) needs of the walk
 // Run mode of a walk (rvll_slice_walk_runs): the walkers of several independent runs in one walk.  Every row's run is in

@@ -2,7 +2,7 @@
 """Soak of the host-buffer entry points across their size classes (run on the GPU box).  rvll_loglike_batch,
 rvll_prior_batch and rvll_prior_loglike_batch pick a transport by the size of the call — scalar server, zero-copy
 through the mapped pinned blocks, pinned landing zone for the results, overlapped chunks on two streams, staged
-downloads (evidence_amd/csrc/rvll_api.hip) — and the rows of a batch are independent, so every call on a slice of
+downloads (evidence_amd/csrc/rvll_batch.hip, the choice in rvll_batch_route.h) — and the rows of a batch are independent, so every call on a slice of
 one big table must return exactly the bits of the same rows computed once through the device-resident path.
 Sizes: every threshold the library has, one row either side of it, then random sizes for --seconds."""
 import argparse, os, sys, time

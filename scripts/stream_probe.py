@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Large host-buffer calls: the streamed route (chunks through pinned blocks, the host's copies on worker threads;
-rvll_api.hip, stream_host_batch) against the routes it replaces (RVLL_STREAM_MIN / RVLL_STREAM_LOGLIKE: measurement
+rvll_batch.hip, stream_host_batch) against the routes it replaces (RVLL_STREAM_MIN / RVLL_STREAM_LOGLIKE: measurement
 switches), with the caller's input array the same one every call (the runtime pins and caches its pages) and a fresh
 one every call (what a sampler does), and what a fresh 40 MB result array costs by itself.  Run on the GPU box."""
 import os, sys, time

@@ -101,7 +101,7 @@ def pair_waves(rows, n_epochs, form, pb, start_rounds=None, window=4096):
     """Which items the pair path (itmax > 16) solves in one wave, as loglike_tile deals them (rvll_tile.h:1186-1258): a wave
     number per flattened (row, epoch) item, and (item, wave) of the copies that ride along — a lane of the CU-wide form beyond the
     tile's last item is pointed at item (0, 0) of the tile (:1227) and takes part in its wave's stop test.
-      "tile": tiles of pb rows, LDS windows of `window` items cut at point-local positions (:1183-1187, rvll_api.hip:177-178);
+      "tile": tiles of pb rows, LDS windows of `window` items cut at point-local positions (:1183-1187, rvll_api.hip:171-172);
               in a window thread t of 256 takes items t + 512 k and t + 256 + 512 k (:1247-1248), 64 threads a wave
       "cu":   one window; tickets are drawn in twos (:1196), ticket k is wave round (k + r0) mod rounds (:1206-1207, :1218-1219)
               with r0 the tile's start round (start_rounds, tile_decode :857-859)"""
@@ -290,7 +290,7 @@ def emulate(case, precision, tol=1e-4, itmax=10000, sincos=sincos_numpy, info=No
     else:
         item = res * res / (2 * var)                                            # :589 / :618
     # tile_logdet (:976-997, logdet_finish :962-974) is the same code in every precision: sum_j ln sqrt(var_j) in fp64, as the
-    # logarithm of a (mantissa product, exponent sum); a.cte (rvll_api.hip:420) - acc (tile_point_result :1076)
+    # logarithm of a (mantissa product, exponent sum); a.cte (rvll_api.hip:414) - acc (tile_point_result :1076)
     acc = 0.5 * np.log(var).sum(axis=1) + item.sum(axis=1)
     out = -0.5 * ne * np.log(2 * np.pi) - acc
     if len(lay.planets) > 0:

@@ -303,7 +303,7 @@ def test_large_host_batches_go_up_in_overlapped_chunks(gpu_required, n, monkeypa
 @pytest.mark.parametrize("chunk,workers,lag", [(4096, 3, 2), (16384, 8, 2), (30000, 1, 1)])
 def test_streamed_host_batches_are_the_device_resident_bits(gpu_required, monkeypatch, chunk, workers, lag):
     """Host batches of 24 MB of rows and more go through pinned staging blocks in chunks, the host's copies on worker threads
-    (csrc/rvll_api.hip, stream_host_batch): the same kernels on the same rows.  Forced here for every size (ragged last
+    (csrc/rvll_batch.hip, stream_host_batch): the same kernels on the same rows.  Forced here for every size (ragged last
     chunk, fewer rows than a chunk, fewer chunks than the pipeline is deep), into fresh, recycled and caller-owned arrays."""
     n = 230_001                                                           # 35 MB of rows: a recycled result block (engine.py)
     w = make_workload(3)
@@ -405,9 +405,33 @@ def test_scalar_server_answers_polychord_style_calls(gpu_required):
         assert np.array_equal(m3.log_likelihood_batch(case.theta[:10]), want[:10])
 
 
+def _every_threshold_one_row_either_side(m, cube, rng, byte_thresholds):
+    """All three host-buffer entry points on slices of `cube`, of every size one below, at and one above each byte threshold
+    divided by each row size, against one pass of the whole table through the device-resident path: the same bits."""
+    nbig, D = len(cube), m.ndim
+    m.dev_upload_cube(cube); m.dev_prior(nbig); m.dev_loglike(nbig)
+    theta, logl, flags = (a.copy() for a in m.dev_download(nbig, theta=True, flags=True))
+    sizes = {1, 2, 63, 64, 65, 4095, 4096, 4097, 16383, 16384, 16385, 65535, 65536, 65537, 131071, 131072, 131073, nbig}
+    for T in byte_thresholds:
+        for r in (8 * D, 16 * D, 12, 8 * D + 12, 16 * D + 12):
+            n = T // r
+            sizes.update((n - 1, n, n + 1, n + 2))                         # ("up to n rows", "from n + 1 rows on")
+    sizes = sorted(k for k in sizes if 1 <= k <= nbig)
+    for n in sizes:
+        o = int(rng.integers(0, nbig - n + 1))
+        got, fl = m.log_likelihood_batch(theta[o:o + n], return_flags=True)
+        assert np.array_equal(got, logl[o:o + n]) and np.array_equal(fl, flags[o:o + n]), ("loglike", n)
+        assert np.array_equal(m.prior_transform_batch(cube[o:o + n]), theta[o:o + n]), ("prior", n)
+        th, got, fl = m.prior_loglike_batch(cube[o:o + n], return_flags=True)
+        assert np.array_equal(th, theta[o:o + n]) and np.array_equal(got, logl[o:o + n]) and \
+            np.array_equal(fl, flags[o:o + n]), ("prior_loglike", n)
+    return sizes
+
+
 def test_every_transport_threshold_one_row_either_side(gpu_required):
     """The three host-buffer entry points choose a transport by the size of the call (scalar server, zero-copy through
-    the mapped pinned blocks, pinned landing zone, overlapped chunks, staged downloads: csrc/rvll_api.hip).  Rows are
+    the mapped pinned blocks, pinned landing zone, overlapped chunks, staged downloads: csrc/rvll_batch_route.h chooses,
+    csrc/rvll_batch.hip runs).  Rows are
     independent, so a call on any slice of one table returns the bits of those rows computed once through the
     device-resident path — at every threshold, one row below and one above (scripts/host_call_soak.py soaks the same
     with random sizes; profiles/r02_host_call_soak.txt)."""
@@ -417,22 +441,21 @@ def test_every_transport_threshold_one_row_either_side(gpu_required):
     cube = w.sample_cube(nbig, seed=43)
     cube[::997] *= 1e-9                                                   # rows hard against the cube's walls
     with GpuRVModel(w.fixedpardict, w.table, w.parnames, priordict=w.priordict()) as m:
-        D = m.ndim
-        m.dev_upload_cube(cube); m.dev_prior(nbig); m.dev_loglike(nbig)
-        theta, logl, flags = (a.copy() for a in m.dev_download(nbig, theta=True, flags=True))
-        sizes = {1, 2, 63, 64, 65, 4095, 4096, 4097, 16383, 16384, 16385, 65535, 65536, 65537, 131071, 131072, 131073, nbig}
-        for T in (64 << 10, 384 << 10, 1 << 20, 8 << 20, 24 << 20):       # (the last: where streamed chunks take over)
-            for r in (8 * D, 16 * D, 12, 8 * D + 12, 16 * D + 12):
-                n = T // r
-                sizes.update(k for k in (n - 1, n, n + 1) if 1 <= k <= nbig)
-        for n in sorted(sizes):
-            o = int(rng.integers(0, nbig - n + 1))
-            got, fl = m.log_likelihood_batch(theta[o:o + n], return_flags=True)
-            assert np.array_equal(got, logl[o:o + n]) and np.array_equal(fl, flags[o:o + n]), ("loglike", n)
-            assert np.array_equal(m.prior_transform_batch(cube[o:o + n]), theta[o:o + n]), ("prior", n)
-            th, got, fl = m.prior_loglike_batch(cube[o:o + n], return_flags=True)
-            assert np.array_equal(th, theta[o:o + n]) and np.array_equal(got, logl[o:o + n]) and \
-                np.array_equal(fl, flags[o:o + n]), ("prior_loglike", n)
+        _every_threshold_one_row_either_side(m, cube, rng, (64 << 10, 384 << 10, 1 << 20, 8 << 20, 24 << 20))   # (the last: where
+                                                                                                                # streamed chunks take over)
+
+
+_MANY_PLANET_RANGES = {"jitter": (0.0, 5.0), "offset": (-5.0, 5.0), "ecc": (0.0, 0.6), "k1": (0.1, 10.0), "ma0": (0.0, 2 * np.pi),
+                       "omega": (0.0, 2 * np.pi), "period": (2.0, 500.0)}
+
+
+def _many_planet_model(nplanets):
+    """(fixed parameters, parameter names) of a two-instrument model of nplanets planets: 5 nplanets + 4 free parameters, each within
+    _MANY_PLANET_RANGES[its kind]"""
+    names = ["harps_jitter", "harps_offset", "hires_jitter", "hires_offset"]
+    for n in range(1, nplanets + 1):
+        names += [f"planet{n}_{k}" for k in ("ecc", "k1", "ma0", "omega", "period")]
+    return {f"planet{n}_epoch": 51000.0 for n in range(1, nplanets + 1)}, sorted(names)
 
 
 def test_scalar_server_with_more_parameters_than_its_polling_wave_has_lanes(gpu_required):
@@ -442,21 +465,10 @@ def test_scalar_server_with_more_parameters_than_its_polling_wave_has_lanes(gpu_
     row included (nothing in a slot changes but the request), and a 13-parameter model next to it exercises the one-read path."""
     w = make_workload(3)
     rng = np.random.default_rng(9)
-    two_pi = 2 * np.pi
 
     def model_of(nplanets):
-        names = ["harps_jitter", "harps_offset", "hires_jitter", "hires_offset"]
-        for n in range(1, nplanets + 1):
-            names += [f"planet{n}_{k}" for k in ("ecc", "k1", "ma0", "omega", "period")]
-        names = sorted(names)
-        fixed = {f"planet{n}_epoch": 51000.0 for n in range(1, nplanets + 1)}
-        cols = []
-        for name in names:
-            kind = name.split("_")[1]
-            lo, hi = {"jitter": (0.0, 5.0), "offset": (-5.0, 5.0), "ecc": (0.0, 0.6), "k1": (0.1, 10.0), "ma0": (0.0, two_pi),
-                      "omega": (0.0, two_pi), "period": (2.0, 500.0)}[kind]
-            cols.append(rng.uniform(lo, hi, 40))
-        return fixed, names, np.column_stack(cols)
+        fixed, names = _many_planet_model(nplanets)
+        return fixed, names, np.column_stack([rng.uniform(*_MANY_PLANET_RANGES[name.split("_")[1]], 40) for name in names])
 
     for nplanets in (14, 2):
         fixed, names, theta = model_of(nplanets)
@@ -469,3 +481,63 @@ def test_scalar_server_with_more_parameters_than_its_polling_wave_has_lanes(gpu_
             again = np.array([m.log_likelihood(theta[7]) for _ in range(5)])
             m.scalar_server(False)
             assert np.array_equal(got, want) and (again == want[7]).all(), nplanets
+
+
+def test_every_transport_threshold_at_74_parameters(gpu_required):
+    """Every row-count threshold of the host-buffer calls moves with the parameter count (csrc/rvll_batch_route.h divides byte
+    limits by the row size).  The same check as at 19 parameters on a 14-planet model, 74 free parameters with uniform priors:
+    zero-copy log-L up to 1771 rows, zero-copy prior up to 664, fused zero-copy up to 1736, streamed chunks from 24 MB of rows
+    (42510 rows: 42509 rows are 496 bytes short of it), staged theta downloads from 32 MB (56680 rows)."""
+    from evidence_amd import priors as P
+    nbig, D = 57_000, 74
+    assert ((1 << 20) // (8 * D), (384 << 10) // (8 * D), ((1 << 20) - 16) // (8 * D + 12)) == (1771, 664, 1736)
+    assert (-(-(24 << 20) // (8 * D)), -(-(32 << 20) // (8 * D))) == (42510, 56680)
+    w = make_workload(3)
+    rng = np.random.default_rng(74)
+    fixed, names = _many_planet_model(14)
+    pri = {name: P.Uniform(*_MANY_PLANET_RANGES[name.split("_")[1]]) for name in names}
+    cube = rng.random((nbig, D))
+    cube[::997] *= 1e-9                                                   # rows hard against the cube's walls
+    with GpuRVModel(fixed, w.table, names, priordict=pri) as m:
+        assert m.ndim == D
+        sizes = _every_threshold_one_row_either_side(m, cube, rng, (64 << 10, 384 << 10, 1 << 20, 8 << 20, 24 << 20, 32 << 20))
+    for edge in (1771, 664, 1736, 42509, 56679):                          # the last row of one transport and the first of the next
+        assert {edge - 1, edge, edge + 1, edge + 2} <= set(sizes)
+
+
+def test_host_buffer_calls_check_their_arguments_in_one_order(gpu_required):
+    """The three host-buffer entry points share one argument prologue (csrc/rvll_batch.hip): null handle, B < 0, missing priors
+    where the call needs them, B == 0, null arrays, and only then the scalar-call server.  Every case here is answered before any
+    launch."""
+    from evidence_amd import _abi
+    case = golden.config_case(3)
+    w = make_workload(3)
+    x, out, out2, fl = np.full(64, 0.5), np.zeros(64), np.zeros(64), np.zeros(1, np.int32)
+    dp, ip = _abi.as_dp, _abi.as_ip
+
+    def calls(m, B, inp=x, logl=out, theta=out2):
+        """(rvll_loglike_batch, rvll_prior_batch, rvll_prior_loglike_batch) return codes; None stands for a null array"""
+        lib, h = m._lib, m._h
+        a = lambda v: None if v is None else dp(v)
+        return (lib.rvll_loglike_batch(h, a(inp), B, a(logl), ip(fl)), lib.rvll_prior_batch(h, a(inp), B, a(theta)),
+                lib.rvll_prior_loglike_batch(h, a(inp), B, a(theta), a(logl), ip(fl)))
+
+    OK, INV, NOP = _abi.OK, _abi.E_INVALID, _abi.E_NOPRIORS
+    with GpuRVModel(case.fixed, case.table, case.parnames) as bare, \
+            GpuRVModel(w.fixedpardict, w.table, w.parnames, priordict=w.priordict()) as m:
+        for server in (False, True):
+            bare.scalar_server(server); m.scalar_server(server)
+            assert calls(m, -1) == (INV, INV, INV) and calls(m, -1, None, None, None) == (INV, INV, INV)
+            assert calls(bare, -1) == (INV, INV, INV)                     # B < 0 is reported before the missing priors
+            assert calls(bare, 1)[1:] == (NOP, NOP) and calls(bare, 0, None, None, None) == (OK, NOP, NOP)
+            assert calls(bare, 1, None)[1:] == (NOP, NOP)                 # ... and the missing priors before a null array
+            assert calls(m, 0, None, None, None) == (OK, OK, OK)
+            assert calls(m, 1, inp=None) == (INV, INV, INV)
+            assert calls(m, 1, logl=None)[::2] == (INV, INV)
+            assert calls(m, 1, theta=None)[1] == INV
+            assert calls(bare, 1, inp=None)[0] == INV and calls(bare, 1, logl=None)[0] == INV
+        # and the handles still answer
+        cube = w.sample_cube(2, seed=1)
+        th, ll = m.prior_loglike_batch(cube)
+        th1, ll1 = m.prior_loglike(cube[1])                               # (through the server, which is still on)
+        assert np.array_equal(th1, th[1]) and ll1 == ll[1]
