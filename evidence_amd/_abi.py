@@ -272,6 +272,8 @@ PROTOTYPES = {
                                  _dp, _dp, _ip, _ip, _dp, _dp, C.c_int64, _dp]),
     "rvll_celerite_loglike_batch": (C.c_int, [Handle, _dp, C.c_int64, C.c_int32, C.POINTER(NoiseTerm), C.c_int32, _ip, _dp, _dp,
                                               _ip, _dp]),
+    "rvll_celerite_predict_batch": (C.c_int, [Handle, _dp, C.c_int64, C.POINTER(NoiseTerm), C.c_int32, _ip, _dp, C.c_int64, C.c_int32,
+                                              _dp, _dp, _dp, _dp, _dp, _dp, _ip, _dp]),
     "rvll_region_draw_runs": (C.c_int, [Handle, _dp, C.POINTER(C.c_int64), C.c_int64, _dp, _dp, _dp, C.POINTER(C.c_uint64), _ip,
                                         C.c_int32, C.c_int64, C.c_int64, C.c_int32, _dp, _dp, _dp, _ip, C.POINTER(C.c_int64),
                                         C.c_int64, _dp, _ip, _ip, _dp, C.POINTER(C.c_int64), _ip]),

@@ -19,12 +19,15 @@ complex term, below 1/2 two real columns; |q - 1/2| is taken as at least 1e-6 on
 
 This module holds the definitions in numpy — kernel_matrix, log_likelihood_dense (the definition: a dense Cholesky) and
 log_likelihood_recursive (the algorithm of csrc/rvll_celerite.h) — and CorrelatedNoiseModel, which evaluates batches on the
-GPU (rvll_celerite_loglike_batch).  Parameters that give no valid covariance have log-L = -1e30, the reference's sentinel
+GPU (rvll_celerite_loglike_batch).  The GP those terms define, given the data: predict_dense is the definition
+of alpha = Sigma^-1 r and of the conditional mean and variance at the data epochs and at query times, predict_recursive the
+sweeps of csrc/rvll_celerite_predict.h in numpy, and CorrelatedNoiseModel.predict_batch / activity_corrected the GPU path
+(rvll_celerite_predict_batch).  Parameters that give no valid covariance have log-L = -1e30, the reference's sentinel
 (rvmodel:203), and FLAG_NOISE_INVALID.
 """
 import math
 import re
-from typing import Dict, List, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -248,6 +251,192 @@ def log_likelihood_recursive(res, var, t, columns):
     return float(-0.5 * chi - 0.5 * lndet - 0.5 * res.shape[0] * math.log(_TWO_PI))
 
 
+# ---- prediction: the conditional mean and variance of the GP given the data ---------------------------------------------
+class Prediction(NamedTuple):
+    """alpha = Sigma^-1 r, the mean and variance of the latent GP at the data epochs (table order), and at the query times (the
+    caller's order; None without query times)."""
+    alpha: np.ndarray
+    mean_data: np.ndarray
+    var_data: np.ndarray
+    mean: Optional[np.ndarray]
+    var: Optional[np.ndarray]
+
+
+class GpPrediction(NamedTuple):
+    """What CorrelatedNoiseModel.predict_batch returns."""
+    residual: np.ndarray
+    mean_data: np.ndarray
+    var_data: np.ndarray
+    mean: Optional[np.ndarray]
+    var: Optional[np.ndarray]
+    logl: np.ndarray
+    flags: np.ndarray
+
+
+def _kernel_values(x, cols):
+    """k(x) of the columns at lags x >= 0 (any shape).  The two columns of an SHO below 1/2 (the second is the only real column
+    with a < 0) are +-amp / (2 f) near 1/2 and cancel to amp: they enter as exp(-c0 x) ((a0 + a1) + a1 expm1(-(c1 - c0) x)), the
+    same function of the same columns, which keeps the digits kernel_matrix's plain sum loses there."""
+    k = np.zeros_like(x)
+    J, j = cols.shape[0], 0
+    while j < J:
+        a, b, c, d, form = cols[j]
+        if int(form) == FORM_REAL and j + 1 < J and int(cols[j + 1, 4]) == FORM_REAL and cols[j + 1, 0] < 0.0:
+            a1, c1 = cols[j + 1, 0], cols[j + 1, 2]
+            k += np.exp(-c * x) * ((a + a1) + a1 * np.expm1(-(c1 - c) * x))
+            j += 2
+            continue
+        if int(form) != FORM_SIN:
+            k += np.exp(-c * x) * (a * np.cos(d * x) + b * np.sin(d * x))
+        j += 1
+    return k
+
+
+def predict_dense(res, var, t, columns, times=None):
+    """The definition: alpha = Sigma^-1 r with Sigma = diag(var) + K, mean(x) = K(x, t) alpha and
+    var(x) = k(0) - K(x, t) Sigma^-1 K(t, x), at the data epochs and at `times`.  Every time is taken as its float64 difference
+    from the first epoch in time order, as the log-L path takes them.  An O(Ne³) reference, not a product path."""
+    res, var, t = (np.asarray(v, dtype=np.float64) for v in (res, var, t))
+    cols = _as_columns(columns)
+    ts = t - t.min()
+    K = _kernel_values(np.abs(ts[:, None] - ts[None, :]), cols)
+    Sigma = np.diag(var) + K
+    alpha = np.linalg.solve(Sigma, res)
+    k0 = _kernel_values(np.zeros(1), cols)[0]
+    mean_data = K @ alpha
+    var_data = k0 - np.einsum("nm,mn->n", K, np.linalg.solve(Sigma, K))
+    if times is None:
+        return Prediction(alpha, mean_data, var_data, None, None)
+    xs = np.asarray(times, dtype=np.float64).reshape(-1) - t.min()
+    Kx = _kernel_values(np.abs(xs[:, None] - ts[None, :]), cols)
+    return Prediction(alpha, mean_data, var_data, Kx @ alpha, k0 - np.einsum("xn,nx->x", Kx, np.linalg.solve(Sigma, Kx.T)))
+
+
+def _generators(cols, pairs, t, dt):
+    """U and V at time t (from the first epoch) and the propagator P [J, J] over a gap dt >= 0, in the row's basis: diagonal
+    exp(-c dt), with the 2 x 2 block and the constant U = (u1, u2), V = (1, 0) of every prepared pair (_pairs)."""
+    a, b, c, d = cols[:, 0], cols[:, 1], cols[:, 2], cols[:, 3]
+    form = cols[:, 4].astype(int)
+    P = np.diag(np.exp(-c * dt))
+    cs, sn = np.cos(d * t), np.sin(d * t)
+    U = np.where(form == FORM_SIN, a * sn - b * cs, np.where(form == FORM_COS, a * cs + b * sn, a))
+    V = np.where(form == FORM_SIN, sn, np.where(form == FORM_COS, cs, 1.0))
+    for j, s, g, w, u1, u2 in pairs:
+        m11, m21 = _pair_propagator(s, g, w, dt)
+        P[j:j + 2, j:j + 2] = [[m11, s * w * w * m21], [m21, m11]]
+        U[j:j + 2], V[j:j + 2] = (u1, u2), (1.0, 0.0)
+    return U, V, P
+
+
+def _basis_kernel(cols, pairs, x):
+    """k(x) at one lag x >= 0 in the row's basis: u1 phi1(x) + u2 phi2(x) for a prepared pair, whose plain columns cancel."""
+    k, taken = 0.0, set()
+    for j, s, g, w, u1, u2 in pairs:
+        m11, m21 = _pair_propagator(s, g, w, x)
+        k += u1 * m11 + u2 * m21
+        taken |= {j, j + 1}
+    for j, (a, b, c, d, form) in enumerate(cols):
+        if j not in taken and int(form) != FORM_SIN:
+            k += math.exp(-c * x) * (a * math.cos(d * x) + b * math.sin(d * x))
+    return k
+
+
+def predict_recursive(res, var, t, columns, times=None, mutate=None):
+    """predict_dense's numbers in O((Ne + M) J²) (O(M Ne J) for the variance at the query times) by the sweeps of
+    csrc/rvll_celerite_predict.h, in the basis log_likelihood_recursive works in:
+        forward    the factor: W_n, D_n, z_n of every epoch in time order
+        backward   g = 0, M = 0 after the last epoch; alpha_n = z_n / D_n - W_n . g, m = M W_n, Z_nn = 1 / D_n + W_n . m
+                   (the diagonal of Sigma^-1), G_n = g + U_n alpha_n, then g <- P_n^T G_n and
+                   M <- P_n^T (M + Z_nn U U^T - U m^T - m U^T) P_n; mean_data_n = r_n - var_n alpha_n,
+                   var_data_n = var_n - var_n² Z_nn; a query x in [t_(n-1), t_n) takes V(x) . P(t_n - x)^T G_n
+        forward    F_n = P_n F_(n-1) + V_n alpha_n; a query x in [t_n, t_(n+1)) adds U(x) . P(x - t_n) F_n
+        variance   var(x) = sum a - sum w_n² / D_n with w = L^-1 k(x) by forward substitution through W and D
+    Returns None where the factorisation fails (a pivot not > 0).  mutate: a defect to inject, for the tests that show the
+    cases can tell ("drop_tie", "transpose", "last_g", "no_forward")."""
+    res, var, t = (np.asarray(v, dtype=np.float64) for v in (res, var, t))
+    if columns is None or not np.isfinite(res).all():
+        return None
+    cols = _as_columns(columns)
+    if not np.isfinite(cols).all():
+        return None
+    J, ne = cols.shape[0], t.shape[0]
+    form = cols[:, 4].astype(int)
+    suma = cols[form != FORM_SIN, 0].sum()
+    pairs = _pairs(cols)
+    order = np.argsort(t, kind="stable")
+    ts = t[order] - t[order[0]]
+    dts = np.diff(ts, prepend=ts[0])
+    if mutate == "drop_tie":                                     # a tie treated as a gap of a second
+        dts = np.where((dts == 0.0) & (np.arange(ne) > 0), 1.0 / 86400.0, dts)
+    r, v = res[order], var[order]
+    Us, Vs, Ps = np.empty((ne, J)), np.empty((ne, J)), np.empty((ne, J, J))
+    Ws, Ds, zs = np.empty((ne, J)), np.empty(ne), np.empty(ne)
+    S, f, W = np.zeros((J, J)), np.zeros(J), np.zeros(J)
+    D = z = 0.0
+    with np.errstate(all="ignore"):
+        for n in range(ne):
+            U, V, P = _generators(cols, pairs, ts[n], dts[n])
+            S = P @ (S + D * np.outer(W, W)) @ P.T
+            f = P @ (f + W * z)
+            SU = S @ U
+            D = (v[n] + suma) - U @ SU
+            if not D > 0.0:
+                return None
+            W = (V - SU) / D
+            z = r[n] - U @ f
+            Us[n], Vs[n], Ps[n], Ws[n], Ds[n], zs[n] = U, V, P, W, D, z
+        if times is None:
+            xs = np.empty(0)
+        else:
+            xs = np.asarray(times, dtype=np.float64).reshape(-1) - t[order[0]]
+        qorder = np.argsort(xs, kind="stable")
+        n0 = np.searchsorted(ts, xs, side="right") - 1             # the last epoch at or before the query, -1 before the first
+        mean = np.zeros(xs.shape[0])
+        # backward
+        alpha, zdiag = np.empty(ne), np.empty(ne)
+        g, M = np.zeros(J), np.zeros((J, J))
+        for n in range(ne - 1, -1, -1):
+            U, P, W = Us[n], Ps[n], Ws[n]
+            if mutate == "transpose" and pairs:
+                P = P.T
+            alpha[n] = zs[n] / Ds[n] - W @ g
+            m = M @ W
+            zdiag[n] = 1.0 / Ds[n] + W @ m
+            G = g + U * alpha[n]
+            for q in qorder[n0[qorder] == n - 1]:
+                _, Vx, Px = _generators(cols, pairs, xs[q], ts[n] - xs[q])
+                mean[q] = Vx @ (Px.T @ G)
+            g = P.T @ (g if (mutate == "last_g" and n == ne - 1) else G)
+            M = P.T @ (M + zdiag[n] * np.outer(U, U) - np.outer(U, m) - np.outer(m, U)) @ P
+        # forward
+        F = np.zeros(J)
+        for n in range(ne):
+            F = Ps[n] @ F + Vs[n] * alpha[n]
+            if mutate == "no_forward":
+                continue
+            for q in qorder[n0[qorder] == n]:
+                Ux, _, Px = _generators(cols, pairs, xs[q], xs[q] - ts[n])
+                mean[q] += Ux @ (Px @ F)
+        # the variance at the query times
+        vq = np.empty(xs.shape[0])
+        for q in range(xs.shape[0]):
+            f, w, acc = np.zeros(J), 0.0, 0.0
+            W = np.zeros(J)
+            for n in range(ne):
+                f = Ps[n] @ (f + W * w)
+                w = _basis_kernel(cols, pairs, abs(xs[q] - ts[n])) - Us[n] @ f
+                W = Ws[n]
+                acc += w * w / Ds[n]
+            vq[q] = suma - acc
+    out_alpha, mean_data, var_data = np.empty(ne), np.empty(ne), np.empty(ne)
+    out_alpha[order] = alpha
+    mean_data[order] = r - v * alpha
+    var_data[order] = v - v * v * zdiag
+    if times is None:
+        return Prediction(out_alpha, mean_data, var_data, None, None)
+    return Prediction(out_alpha, mean_data, var_data, mean, vq)
+
+
 # ---- the GPU path ---------------------------------------------------------------------------------------------------------------------
 class CorrelatedNoiseModel:
     """A GpuRVModel's likelihood with celerite noise terms added to its covariance, evaluated on the model's GPU.
@@ -260,7 +449,8 @@ class CorrelatedNoiseModel:
     callbacks.make_ultranest_callbacks(gp, vectorized=True), callbacks.make_polychord_callbacks(gp) and as
     run_nested_slice(gp.prior_transform_batch, gp.log_likelihood_batch, gp.ndim, prior_loglike=gp.prior_loglike_batch, ...) or
     run_nested_ensemble(gp.prior_transform_batch, gp.log_likelihood_batch, gp.ndim, seeds, walker_runs=gp.slice_walk_runs, ...);
-    the results go through merge, posterior, marginals, fip and sensitivity as they are.
+    the results go through merge, posterior, marginals, fip and sensitivity as they are.  predict_batch gives the GP itself for
+    finished draws: its mean and variance at the data epochs and at query times; activity_corrected the velocities without it.
 
     Not offered: the device walks, the resident live sets, region_runs and the scalar server (low_latency=True) evaluate the
     white likelihood inside their kernels; do not pass the model's walker / live / region callables along with this likelihood.
@@ -304,6 +494,41 @@ class CorrelatedNoiseModel:
         dict that receives residuals_ms and solve_ms."""
         _, out, flags = self._call(X, False, timing)
         return (out, flags) if return_flags else out
+
+    def predict_batch(self, thetas, times=None, return_var=False, timing=None):
+        """The GP given the data, for every row of thetas [n, ndim] (rvll_celerite_predict_batch; the definition is
+        predict_dense on the model's residuals): a GpPrediction with residual, mean_data and var_data [n, Ne] in table order, mean
+        [n, M] at `times` in the order given (None without times), var [n, M] with return_var (None without: it costs
+        O(M Ne J) a row where the rest costs O((Ne + M) J²)), and logl and flags [n], the bits of log_likelihood_batch.  A row
+        with a flag is NaN in every array.  timing: a dict that receives residuals_ms, factor_ms, sweeps_ms and variance_ms."""
+        X = self.model._theta2d(thetas)
+        n, ne = X.shape[0], self.order.shape[0]
+        tq = None if times is None else np.ascontiguousarray(np.asarray(times, dtype=np.float64).reshape(-1))
+        m = 0 if tq is None else tq.shape[0]
+        want_var = bool(return_var) and tq is not None
+        residual, mean_data, var_data = (np.empty((n, ne)) for _ in range(3))
+        mean = None if tq is None else np.empty((n, m))
+        var = np.empty((n, m)) if want_var else None
+        logl, flags, ms = np.empty(n), np.zeros(n, dtype=np.int32), np.zeros(4)
+        _abi.check(self.model._lib.rvll_celerite_predict_batch(
+            self.model._h, _abi.as_dp(X), n, self._terms_c, len(self.terms), _abi.as_ip(self.order),
+            _abi.as_dp(tq) if m else None, m, int(want_var), _abi.as_dp(residual), _abi.as_dp(mean_data), _abi.as_dp(var_data),
+            _abi.as_dp(mean) if m else None, _abi.as_dp(var) if want_var and m else None, _abi.as_dp(logl), _abi.as_ip(flags),
+            _abi.as_dp(ms)))
+        if timing is not None:
+            timing.update(residuals_ms=float(ms[0]), factor_ms=float(ms[1]), sweeps_ms=float(ms[2]), variance_ms=float(ms[3]))
+        return GpPrediction(residual, mean_data, var_data, mean, var, logl, flags)
+
+    def activity_corrected(self, theta):
+        """The velocities with the GP's mean at the data epochs taken out, model.table.vrad - mean_data [Ne], for one theta: the
+        series to fold or to feed a periodogram.  ValueError where theta has no valid orbit or covariance."""
+        theta = np.asarray(theta, dtype=np.float64)
+        if theta.size != self.ndim:
+            raise ValueError(f"expected {self.ndim} parameters, got {theta.size}")
+        p = self.predict_batch(theta.reshape(1, -1))
+        if p.flags[0]:
+            raise ValueError(f"theta has no prediction (flags {int(p.flags[0])})")
+        return np.asarray(self.model.table.vrad, dtype=np.float64) - p.mean_data[0]
 
     def log_likelihood(self, x):
         x = np.asarray(x, dtype=np.float64)

@@ -16,6 +16,7 @@
 //   cel_prepare   a near-degenerate SHO pair (|q - 1/2| < 0.01) is rewritten into a sum / difference basis whose block of P is
 //                 2 x 2 and whose U and V are constant; cel_step then carries S and f over the gap with a tridiagonal P
 //                 (cel_advance_pair) where the row has such a pair, and with the diagonal P above (cel_advance) where not.
+//   CelPlan       where a kernel finds a row's term parameters in theta; cel_plan_columns makes the row's prepared columns from it
 //   cel_result    log-L = -1/2 sum z^2 / D - 1/2 sum ln D - Ne / 2 ln(2 pi), or -1e30 and a flag.
 // The times are measured from the first epoch in time order, and both they and the gaps come from a per-epoch table the host
 // builds (rvll_celerite.hip): the kernel takes one sincos per epoch and complex term and one exponential per epoch and distinct c.
@@ -156,6 +157,39 @@ RVLL_HD bool cel_prepare(CelColumn (&col)[J])
     return any;
 }
 
+// Per column its term's kind and parameters, and which of the term's columns it is: how a kernel finds a row's columns in theta.
+struct CelPlan {
+    int32_t kind[RVLL_NOISE_MAX_RANK], sub[RVLL_NOISE_MAX_RANK];
+    rvll_slot par[RVLL_NOISE_MAX_RANK][5];
+};
+
+// The workspace the prediction's sweeps share (rvll_celerite_predict.hip): [epoch in time order][field][row of the chunk], an
+// epoch's fields W_0 .. W_(J-1) and then these.  The factor sweep leaves W, D, z, r and var; the backward sweep puts alpha where z
+// was, the variance at the epoch where var was, and the mean at the epoch.
+enum { kCelWsD = 0, kCelWsZ = 1, kCelWsR = 2, kCelWsVar = 3, kCelWsMean = 4, kCelWsExtra = 5 };
+
+// A row's columns from its theta, prepared: suma the sum of the columns' a (a complex term's counts once), pair what cel_prepare
+// returned.  false: a term's parameters are not valid.
+template <int J>
+RVLL_HD bool cel_plan_columns(const CelPlan& plan, const double* th, CelColumn (&col)[J], double& suma, bool& pair)
+{
+    bool valid = true;
+    suma = 0.0;
+#pragma unroll
+    for (int j = 0; j < J; ++j) {
+        double p[5];
+#pragma unroll
+        for (int q = 0; q < 5; ++q) {
+            const rvll_slot s = plan.par[j][q];
+            p[q] = s.idx >= 0 ? th[s.idx] : s.val;
+        }
+        valid &= cel_column(plan.kind[j], plan.sub[j], p, col[j]);
+        if (col[j].form != kCelColSin) suma += col[j].a;
+    }
+    pair = cel_prepare<J>(col);
+    return valid;
+}
+
 // m11 = phi1(dt) and m21 = phi2(dt) of a prepared pair.  sinh y / y comes from its series below y = 1/2, where
 // (exp(y) - exp(-y)) / 2 cancels, and from the two exponentials of the columns above it, where exp(-g dt) cosh(y) would be 0 inf.
 RVLL_HD void cel_pair_propagator(const CelColumn& k, double dt, double& m11, double& m21)
@@ -188,6 +222,8 @@ RVLL_HD void cel_pair_propagator(const CelColumn& k, double dt, double& m11, dou
 
 // U and V of an epoch at time t (from the first epoch), dt after the previous one, and the state carried over the gap:
 // S <- P P^T o (S + D W W^T), f <- P o (f + W z).
+// cel_gap of rvll_celerite_predict.h computes the same U, V and P for the prediction's sweeps, which run on the W this factor
+// leaves: a change to U, V or P here or in cel_advance_pair goes there too (tests/test_predict_host.py holds the two together).
 template <int J>
 RVLL_HD void cel_advance(const CelColumn (&col)[J], CelState<J>& st, double t, double dt, double (&U)[J], double (&V)[J])
 {
@@ -223,6 +259,7 @@ RVLL_HD void cel_advance(const CelColumn (&col)[J], CelState<J>& st, double t, d
 
 // The same for a row with a prepared pair: P is tridiagonal, row j of P X = al_j X_j + up_j X_(j+1) + dn_j X_(j-1) with up and dn
 // 0 outside a pair's block, so every index is a constant and S <- P (S + D W W^T) P^T, f <- P (f + W z) stay in registers.
+// The first loop below is copied in cel_gap of rvll_celerite_predict.h (see cel_advance): keep the two the same.
 template <int J>
 RVLL_HD void cel_advance_pair(const CelColumn (&col)[J], CelState<J>& st, double t, double dt, double (&U)[J], double (&V)[J])
 {

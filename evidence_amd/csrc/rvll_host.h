@@ -11,6 +11,7 @@
 //   rvll_cluster_host.hip  MLFriends clustering of many row sets (rvll_cluster_runs)
 //   rvll_region.hip     MLFriends region sampling (rvll_region_draw_runs): kernels and host side
 //   rvll_celerite.hip   log-L under correlated noise (rvll_celerite_loglike_batch): kernel and host side
+//   rvll_celerite_predict.hip  GP prediction under correlated noise (rvll_celerite_predict_batch): kernels and host side
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -224,7 +225,7 @@ struct rvll_handle {
     // region sampling (rvll_region_draw_runs): one grow-only block of inputs, per-candidate work, per-run state, outputs, trace
     void* d_region = nullptr;
     size_t region_cap = 0;                                    // bytes
-    // correlated noise (rvll_celerite_loglike_batch): one grow-only block of the epoch tables in time order and a chunk's
+    // correlated noise (rvll_celerite_loglike_batch, rvll_celerite_predict_batch): one grow-only block of the epoch tables in time order and a chunk's
     // residuals, variances and results; the host's copy of the epoch times (fetched at the first call)
     void* d_cel = nullptr;
     size_t cel_cap = 0;                                       // bytes
@@ -271,6 +272,19 @@ struct DriftSlots { rvll_slot s[5]; };                    // lin, quad, cub, qua
 hipError_t launch_residuals(const LoglikeArgs& a, const DriftSlots& ds, unsigned include_mask, double* res, double* var,
                             hipStream_t stream);
 DriftSlots drift_slots(const rvll_handle* h);
+
+// rvll_celerite.hip, shared with rvll_celerite_predict.hip: the checks and the plan of the noise terms, the epoch tables in time
+// order, the grow-only block h->d_cel, and the factor sweep (with ws: the sweep that also stores what the prediction needs)
+struct CelPlan;
+constexpr int kCelRows = 64;                              // rows a workgroup: one wave
+constexpr long long kCelChunkBytes = 256ll << 20;         // what a chunk of rows may take on the device
+size_t cel_up8(size_t n);
+int cel_make_plan(rvll_handle* h, const rvll_noise_term* terms, int32_t n_terms, CelPlan& plan, int& J);
+int cel_time_tables(rvll_handle* h, const int32_t* order, std::vector<int32_t>& ord, std::vector<double>& tab);
+int cel_reserve(rvll_handle* h, size_t total);
+hipError_t launch_celerite_factor(int J, const double* theta, int D, long long R, const double* res, const double* var, int Ne,
+                                  const int32_t* ord, const double* ts, const double* dts, const CelPlan& plan, double cte,
+                                  double* logl, int32_t* flags, double* ws, long long rp, hipStream_t stream);
 }  // namespace rvll
 
 namespace rvll {

@@ -105,6 +105,32 @@ def curve_bands(results, model, times, planet=None, exclude_planet=None, ndraws=
     return out
 
 
+def gp_bands(gp, thetas, times, quantiles=QUANTILES, return_var=True):
+    """The band of a correlated-noise model's GP over posterior draws: gp a correlated.CorrelatedNoiseModel, thetas [n, ndim]
+    (n <= 4096) what draws.samples returns for one replicate, times [T].  Every row's conditional mean at `times` comes from
+    gp.predict_batch on the device; per time the quantiles `quantiles` and the mean of those n means over the rows
+    (bands_definition, on the host; a row without a valid orbit or covariance is NaN and is left out).  With return_var also
+    total_sd [T] = sqrt(mean over the rows of var + variance over the rows of the mean, ddof 0): the GP's own uncertainty and the
+    posterior's spread of its mean together; it costs the O(T Ne J) a row of predict_batch's return_var.  A dict: band [Q, T],
+    mean [T], n_valid [T], total_sd [T] (None without return_var), times and quantiles."""
+    times = np.ascontiguousarray(np.atleast_1d(times), dtype=np.float64)
+    levels = check_levels(quantiles)
+    thetas = np.asarray(thetas, dtype=np.float64)
+    if thetas.ndim != 2:
+        raise ValueError("thetas must be [draws, ndim]: one replicate of draws.samples")
+    pred = gp.predict_batch(thetas, times, return_var=return_var)
+    q, mean, nv = bands_definition(pred.mean[None], levels)
+    total_sd = None
+    if return_var:
+        ok = ~np.isnan(pred.mean)
+        cnt = np.maximum(ok.sum(axis=0), 1)
+        m = np.where(ok, pred.mean, 0.0).sum(axis=0) / cnt
+        spread = np.where(ok, (pred.mean - m) ** 2, 0.0).sum(axis=0) / cnt
+        own = np.where(ok, pred.var, 0.0).sum(axis=0) / cnt
+        total_sd = np.where(ok.any(axis=0), np.sqrt(np.maximum(own + spread, 0.0)), np.nan)
+    return dict(band=q[0], mean=mean[0], n_valid=nv[0], total_sd=total_sd, times=times, quantiles=levels)
+
+
 def _slot(spec, theta):
     return float(theta[spec.index]) if spec.is_free else float(spec.value)
 

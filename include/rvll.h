@@ -655,6 +655,29 @@ int rvll_celerite_loglike_batch(rvll_handle* h, const double* x /*[B, ndim]: the
                                 double* theta_out /*NULL, or [B, ndim] when from_cube*/, double* logl /*[B]*/,
                                 int32_t* flags /*[B]*/, double* phase_ms /*NULL or [2]: residual stage, solve*/);
 
+/* The GP those terms define, given the data (evidence_amd/correlated.py: predict_dense): with r, var and
+ * Sigma = diag(var) + K as above and alpha = Sigma^-1 r,
+ *   residual[b][n]   r, the datum minus the full deterministic model
+ *   mean_data[b][n]  the mean of the latent GP at epoch n given all data, r_n - var_n alpha_n
+ *   var_data[b][n]   its variance, var_n - var_n^2 (Sigma^-1)_nn
+ *   mean[b][i]       sum over n of k(|times[i] - t_n|) alpha_n, the mean at a query time
+ *   var[b][i]        k(0) - K(x, t) Sigma^-1 K(t, x) at x = times[i]; only with want_var, O(M Ne J) a row where everything else
+ *                    is O((Ne + M) J^2)
+ * [B, Ne] in the order of the epoch table, [B, M] in the order of times, which need not be sorted; every time enters as its
+ * float64 difference from the first epoch in time order.  logl and flags are rvll_celerite_loglike_batch's, bit for bit; a row
+ * with a flag has NaN in every array.  The rows go in chunks whose device buffers take at most 256 MiB (at least 64 rows); a
+ * row's bits depend on that row, the epoch table and the query times alone.  phase_ms (may be NULL) receives the HIP-event
+ * times of the residual stage, the factor sweep, the backward and forward sweeps, and the variance at the query times.
+ * RVLL_E_INVALID: what rvll_celerite_loglike_batch refuses, a negative M, a time that is not finite, var without want_var, null
+ * buffers.  RVLL_E_UNSUPPORTED: a handle whose precision is not RVLL_PREC_FP64.                                              */
+int rvll_celerite_predict_batch(rvll_handle* h, const double* theta /*[B, ndim]*/, int64_t B, const rvll_noise_term* terms,
+                                int32_t n_terms, const int32_t* order /*[Ne] epochs in nondecreasing time, NULL: table order*/,
+                                const double* times /*[M], NULL when M = 0*/, int64_t M, int32_t want_var,
+                                double* residual /*[B, Ne] or NULL*/, double* mean_data /*[B, Ne]*/, double* var_data /*[B, Ne] or NULL*/,
+                                double* mean /*[B, M], NULL when M = 0*/, double* var /*[B, M] with want_var, else NULL*/,
+                                double* logl /*[B]*/, int32_t* flags /*[B]*/,
+                                double* phase_ms /*NULL or [4]: residuals, factor, sweeps, grid variance*/);
+
 /* ---- FIP periodogram accumulation (post-processing; independent of any model handle) ------------ */
 /* Replaces the accumulation loop of evidence/fip_criterion.py:305-339.  The caller flattens the posterior
  * samples of all planet models of one run into rows, in the reference's loop order (kmod = 1.., then sample

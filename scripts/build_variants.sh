@@ -15,7 +15,7 @@ while [ $# -ge 2 ]; do
   others=""
   for o in rvll_api rvll_batch rvll_walk_host rvll_live_host rvll_comm rvll_walk_stepout rvll_fip rvll_live rvll_rounds_runs rvll_cluster \
            rvll_cluster_host rvll_shrinkage rvll_insertion rvll_adapt rvll_merge_setup rvll_merge rvll_posterior rvll_fip_merged \
-           rvll_marginal rvll_region rvll_draws rvll_bands rvll_gls rvll_pointwise rvll_prior_density rvll_celerite; do others="$others ../../build/obj/$o.o"; done
+           rvll_marginal rvll_region rvll_draws rvll_bands rvll_gls rvll_pointwise rvll_prior_density rvll_celerite rvll_celerite_predict; do others="$others ../../build/obj/$o.o"; done
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -fPIC -shared -o ../diag/librvll_$name.so $others $B/rvll_kernels.o $B/rvll_walk.o -ldl
   echo "built evidence_amd/diag/librvll_$name.so ($defs)"
 done
