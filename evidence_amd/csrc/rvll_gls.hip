@@ -23,6 +23,13 @@
 //   peak_kernel       one wave a row: the first index of the largest power (a NaN power counts as the largest, as numpy.argmax
 //                     has it) and the power there; -1 and NaN for a row that is NaN throughout (an invalid orbit).
 // No floating-point atomics, no inline assembly.  The order statistics over a group's rows are launch_bands' (rvll_bands.hip).
+//
+// What holds the powers (tests/test_gpu_gls_windows.py): windows of 512 absolute frequency indices, each within 8 delta
+// of its own row and window of the long-double definition, on the default grid f0 = df = 1 / (8 span) up to k = 2^18 + 2 (so
+// df * (double)k0 at k0 = 262144 and phases of 1e5 rad), on tables of 4 to 513 epochs in and out of time order.  A frequency at
+// which every epoch has the same sine or cosine in exact arithmetic (an alias of f = 0 or of the half sampling rate on an evenly
+// spaced table) is not guarded beyond den > 0: CC, SS and D are rounding residue there, the power is a NaN or a number without
+// meaning, as the definition's is, and where the NaNs fall depends on the order of the sums.
 #include "rvll_host.h"
 #include "rvll_math.h"
 

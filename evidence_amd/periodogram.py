@@ -15,7 +15,16 @@ periodogram — as a posterior band over equal-weight draws with its scatter ove
                                CC = Σ w cos² φ - C², SS = Σ w sin² φ - S², CS = Σ w cos φ sin φ - C S, D = CC SS - CS²,
                                p = (SS YC² + CC YS² - 2 CS YC YS) / (YY D),
                            NaN where YY D is not > 0 and for a NaN row.  GpuRVModel.gls_bands / gls_batch (rvll_gls_bands;
-                           csrc/rvll_gls.hip) evaluate it on the device.
+                           csrc/rvll_gls.hip) evaluate it on the device; tests/test_gpu_gls_windows.py holds them to this
+                           definition in long double window by window of 512 frequencies, each row within 8 times the
+                           float64 noise of its own window, on the default grid up to 2^18 + 3 frequencies.
+                           Degenerate frequencies are not guarded: where every epoch has the same sine or cosine in exact
+                           arithmetic (an evenly spaced table has such aliases of f = 0 and of half its sampling rate on
+                           the default grid) CC, SS and D are rounding residue, and the power is NaN or a number without
+                           meaning — in float64, in long double and on the device, each at its own entries.  The ratio
+                           D / (CC SS) does not tell them apart (it is 1, -inf or NaN there, against 7e-5 at a sound
+                           frequency of a 4-epoch table), so no threshold is applied; choose pmin above twice the spacing
+                           of an evenly spaced table, and see peaks_definition for what a NaN does to the peaks.
 """
 import numpy as np
 
