@@ -5,6 +5,7 @@
 //   rvll_batch.hip      the host-buffer batch calls and their transports, streamed host batches, resident uploads and download
 //   rvll_batch_route.h  which transport a host-buffer call takes and where its bytes lie: arithmetic without a HIP call
 //   rvll_walk_host.hip  the sampler's proposal step: the device walk in its forms (rvll_slice_walk*)
+//   rvll_walk_plan.h    the walk's switches, geometry, arena layout and row order: arithmetic without a HIP call
 //   rvll_live_host.hip  the resident live set and ensemble (rvll_live_*, rvll_live_runs_*): the stages of a resident step
 //   rvll_step_groups.h  the walker groups of a resident ensemble step: index arithmetic without a HIP call
 //   rvll_comm.hip       multi-GPU: RCCL communicators, lanes, all-gathers
@@ -21,6 +22,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -153,7 +155,7 @@ struct rvll_handle {
     unsigned long long* d_walk_ncalls = nullptr;
     int32_t *d_walk_steps = nullptr, *d_walk_wid = nullptr, *d_walk_start = nullptr;   // [walk_cap] each
     int32_t *d_walk_cost = nullptr, *d_walk_order = nullptr;                            // [walk_cap] each (two-part walks)
-    int32_t* d_walk_wflag = nullptr;            // [walk_cap] 1: the walker's last accepted candidate had a wandering solve (walk_core puts its log-L right)
+    int32_t* d_walk_wflag = nullptr;            // [walk_cap] 1: the walker's last accepted candidate had a wandering solve (redo_wandering puts its log-L right)
     // run mode of the walk (rvll_slice_walk_runs): per row its run (its index inside the run goes in d_walk_wid), per run
     // lstar, seed and whitening factor
     long long runs_rows_cap = 0, runs_cap = 0;
@@ -166,10 +168,10 @@ struct rvll_handle {
     int walk_spec = 4;                          // candidates a walker may evaluate ahead per iteration (rvll_set_walk_speculation)
     int walk_prop = 0;                          // the walk's proposal (rvll_set_walk_proposal): RVLL_PROPOSAL_CHORD / _STEPOUT ...
     double walk_width = 1.;                     // ... and the stepout bracket's width
-    double* d_walk_basis = nullptr;             // stepout: [slots, ndim, ndim] the basis of every walker slot (walk_core)
+    double* d_walk_basis = nullptr;             // stepout: [slots, ndim, ndim] the basis of every walker slot (basis_for)
     size_t walk_basis_cap = 0;                  // ... in doubles
     // the walk as rounds of launches (rvll_rounds.hip; walk_rounds in rvll_walk_host.hip): one arena with every group's walker
-    // state, candidate slots and counters; a progress word per group in mapped pinned memory
+    // state, candidate slots and counters (rounds_arena, rvll_walk_plan.h); a progress word per group in mapped pinned memory
     int walk_spec_rounds = 8;                   // ... and per round of the rounds form, while a round is below the latency floor
     void* d_rounds = nullptr;
     double* d_walk_dirs = nullptr;              // [K, nsteps, D] the directions of all moves of the walk in progress
@@ -179,7 +181,7 @@ struct rvll_handle {
     unsigned long long* pin_rounds_dev = nullptr;
     hipEvent_t ev_rounds = nullptr;             // orders the groups' streams behind lane 0
     hipEvent_t ev_chain[kMaxLanes] = {};        // group g's step of a round has been issued to the device (the next group's step waits for it)
-    hipStream_t rounds_streams[kMaxLanes] = {}; // the groups' streams, at DIFFERENT priorities (walk_rounds)
+    hipStream_t rounds_streams[kMaxLanes] = {}; // the groups' streams, at DIFFERENT priorities (rounds_streams)
     int walk_rounds_used = 0;                   // rounds the last walk took (0: it ran in one of the single-kernel forms)
     long long walk_evaluated = 0;               // tile slots the last rvll_slice_walk evaluated (>= its ncalls)
     unsigned long long walk_phase[6] = {};      // diagnostic build (make walktrace): 100 MHz ticks per phase, summed over workgroups; workgroups
@@ -266,6 +268,31 @@ struct rvll_handle {
 };
 
 namespace rvll {
+namespace host {
+// A grow-only device buffer: *p holds *cap elements (of a void buffer: bytes); fewer than `need` of them: lane 0 is waited for (what
+// it has queued may use the old buffer), the buffer freed and one of `room` elements (0: need) allocated.  *cap is 0 in between,
+// so that a failed allocation leaves an empty buffer behind, not a stale capacity.
+template <typename T, typename N>
+int grow(rvll_handle* h, T** p, N* cap, size_t need, size_t room = 0)
+{
+    if (need <= (size_t)*cap) return RVLL_OK;
+    HIP_TRY(hipStreamSynchronize(h->compute));
+    dev_free(*p);
+    *cap = 0;
+    room = room ? room : need;
+    HIP_TRY(hipMalloc(p, room * sizeof(std::conditional_t<std::is_void<T>::value, char, T>)));
+    *cap = (N)room;
+    return RVLL_OK;
+}
+// ... one of several buffers that share a capacity (zeroed by the caller meanwhile): anew, n elements
+template <typename T>
+int renew(rvll_handle* h, T** p, size_t n)
+{
+    size_t none = 0;
+    return grow(h, p, &none, n);
+}
+}  // namespace host
+
 // rvll_gls.hip: res = datum - model and var = svrad^2 (+ jitter^2) of every (row, epoch) of a.theta, the planets of include_mask
 // subtracted (rvll_residuals_batch's values); asynchronous on `stream`
 struct DriftSlots { rvll_slot s[5]; };                    // lin, quad, cub, quar, tref

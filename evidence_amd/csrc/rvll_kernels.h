@@ -109,7 +109,7 @@ struct WalkArgs {
     int32_t* cost;                // [K] or null, out: candidates every row used in this launch
     int rows_per_wg;              // the "rows" form (launch_slice_walk_rows): rows every workgroup owns for the whole launch
     int32_t* wflag;               // [K] or null, out: 1 where the walker's LAST accepted candidate carried RVLL_FLAG_WANDERED (its log-L is
-                                  // then put right by the host with the exact redo, which the walk's tiles leave out: walk_core)
+                                  // then put right by the host with the exact redo, which the walk's tiles leave out: redo_wandering in rvll_walk_host.hip)
     // RUN MODE (rvll_slice_walk_runs): the walkers of several independent runs in one launch.  run = null: one run, the
     // scalars seed / lstar and chol above (the kernels' instantiation without run mode: nothing below is read).  Otherwise
     // row g belongs to run run[g], accepts against run_lstar[run[g]], draws with run_seed[run[g]] and whitens with

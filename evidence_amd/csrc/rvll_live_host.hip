@@ -100,13 +100,7 @@ int live_load(rvll_handle* h, const double* cube, int64_t N, double* logl_out)
 // the sorts' scratch d_sort_temp grown to `need` bytes
 int sort_temp_reserve(rvll_handle* h, size_t need)
 {
-    if (need <= h->sort_temp_bytes) return RVLL_OK;
-    HIP_TRY(hipStreamSynchronize(h->compute));
-    dev_free(h->d_sort_temp);
-    h->sort_temp_bytes = 0;
-    HIP_TRY(hipMalloc(&h->d_sort_temp, need));
-    h->sort_temp_bytes = need;
-    return RVLL_OK;
+    return grow(h, &h->d_sort_temp, &h->sort_temp_bytes, need);
 }
 
 // ---- the stages of a resident step (DESIGN §4d "Resident ensemble", §4e): rvll_live_step and the two ensemble steps list them ------

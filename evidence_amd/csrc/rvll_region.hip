@@ -383,13 +383,7 @@ int rvll_region_draw_runs(rvll_handle* h, const double* survivors, const int64_t
     const size_t total = o;
     if (total > kRegionMaxBytes)
         return report_error(RVLL_E_NOMEM, "rvll_region_draw_runs: %zu bytes of device memory exceed the region sampler's budget", total);
-    if (total > h->region_cap) {
-        HIP_TRY(hipStreamSynchronize(h->compute));
-        dev_free(h->d_region);
-        h->region_cap = 0;
-        HIP_TRY(hipMalloc(&h->d_region, total));
-        h->region_cap = total;
-    }
+    RVLL_TRY(grow(h, &h->d_region, &h->region_cap, total));
     // the batch buffers take every kept candidate of a round (reserved now: growing them frees them)
     rc = rvll_dev_reserve(h, (int64_t)std::max<size_t>(S, 1));
     if (rc) return rc;
